@@ -9,7 +9,10 @@ resident in HBM: forward (4 x BiLSTM-320 encoder, CTC head, location-aware atten
 cross-entropy losses + backward + [RCCL all-reduce of the flat gradient] + global-norm clip + Adadelta.
 Workload = BASELINE.json configs[1]: config/librispeech_asr.yaml, B=16 x T=1200 frames of 160-dim
 fbank+delta per GPU, L=180 tokens, bf16 MFMA contractions with fp32 accumulate, dropout on.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0: frames/s and ms_per_step of the timed steps.  A plain run does only that; `--full` adds the
+per-kernel figures (`roofline`, `roofline_gemm`, `roofline_conv`, `stage_ms_per_step`) and the CPU baseline (`cpu_baseline`).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs); that step starts from the
+seeded initial weights and optimizer state, so runs with the same arguments agree up to the order of the gradient sums.
 """
 import argparse
 import json
@@ -43,9 +46,17 @@ def parse():
     ap.add_argument('--shape', default='fixed', choices=['fixed', 'librispeech'], help="librispeech: 8 buckets per GPU with SURVEY 8d's length model clip(N(1270,480),150,2450) and the reference's halving rule (B = 8 once the longest utterance exceeds 800 frames), cycled through; --frames / --tokens are ignored")
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='process-group backend for --gpus N > 1 (nccl = RCCL over xGMI; gloo only with --dry-run)')
     ap.add_argument('--dry-run', action='store_true', help='start the ranks, form the process group, exchange one all-gather and print the JSON line without touching a GPU (CPU test of the launch path)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-seconds', type=float, default=20.0)
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='also measure what the headline figure does not need: HIP-event times of the '
+                    'recurrence launches inside the timed region (roofline), three steps after it with the decoder, contraction and '
+                    'convolution calls timed (roofline_gemm, roofline_conv, stage_ms_per_step), and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--cpu-seconds', type=float, default=20.0, help='with --full: duration of the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed as DIR/<name>.npy (float32 / float64)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 class KernelTimer(object):
@@ -106,6 +117,32 @@ def cpu_baseline(cfg_model, D, V, seconds, B=16, T=1200, L=180):
     return {'value': B * T * n / dt, 'unit': 'frames/s', 'cores': cores, 'kind': 'port',
             'sample': 'oracle (plain PyTorch CPU restatement, fp32, fused ATen LSTM) fwd+bwd on B=%d x T=%d x L=%d, %d passes in %.1f s'
                       % (B, T, L, n, dt)}
+
+
+DUMP_MAX_ELEMENTS = 2 ** 21        # per array: 8 MB in float32; five of the arrays can be large, so a dump stays under 48 MB
+
+
+def dump_outputs(path, out, model):
+    """What a caller of the timed step receives from its last call (the one that starts from the seeded initial state): the
+    dict train_step returns (losses, squared gradient norm, CTC log-probabilities, attention logits and alignments, encoder
+    lengths) and the model it updated in place (parameters and their gradients, concatenated in parameters() order).  Floating arrays keep float64 or become float32, integer ones
+    become float64.  An array of more than DUMP_MAX_ELEMENTS elements is written as the elements at DUMP_MAX_ELEMENTS sorted
+    positions drawn with a fixed seed from its flattened form, so that two builds write the same sample of the same shape."""
+    import numpy as np
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    arrays['params'] = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    arrays['grads'] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                 for p in model.parameters()])
+    os.makedirs(path, exist_ok=True)
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+        a = t.cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+    log('outputs of the last timed step written to %s: %s' % (path, ', '.join(sorted(arrays))))
 
 
 def workload_string(config, args, Dfeat):
@@ -228,13 +265,22 @@ def main():
         if config['data']['audio']['delta_order'] >= 1 else None
     augment = Augment(seed=1234 + rank).cuda() if config['data']['audio'].get('augment', False) else None
 
-    # inside the timed region only the dominant kernel (the LSTM recurrence, 8 launches per step) carries HIP events; the
-    # other stages and the contractions are timed in a short pass AFTER it (an event pair per call costs host time and
+    # --full: inside the timed region only the dominant kernel (the LSTM recurrence, 8 launches per step) carries HIP events;
+    # the other stages and the contractions are timed in a short pass AFTER it (an event pair per call costs host time and
     # ~4 us of queue time: 100 pairs per step made the step 0.3-1.5 ms longer, depending on the host)
-    timer = KernelTimer(['asr_lstm_fwd', 'asr_lstm_bwd', 'asr_lstm16_fwd', 'asr_lstm16_bwd'] + (['asr_fbank'] if args.waveform else []))
-    timer.wrap(H)
+    timer = None
+    if args.full:
+        timer = KernelTimer(['asr_lstm_fwd', 'asr_lstm_bwd', 'asr_lstm16_fwd', 'asr_lstm16_bwd'] + (['asr_fbank'] if args.waveform else []))
+        timer.wrap(H)
 
     import contextlib
+
+    # the last timed step starts again from the seeded initial weights and optimizer state, so that what it computes is the
+    # same in every run with the same arguments: the split reductions add gradients with fp32 atomics, in an order that
+    # changes from run to run, and over many optimizer steps the bf16 rounding of the weights amplifies those last-bit
+    # differences far beyond rounding.  One copy of the state inside the timed region (~0.15 GB, tens of us per run).
+    opt = optimizer.opt
+    initial_state = [(t, t.clone()) for t in vars(opt).values() if torch.is_tensor(t) and t is not opt.flat_grad]
 
     use_work = H.overlap_enabled() and (world == 1 or H.overlap_dp_enabled())
     if use_work:
@@ -242,10 +288,13 @@ def main():
         # is non-blocking and does not serialise with it
         H.work_stream().wait_stream(torch.cuda.current_stream())
 
-    def step():
+    def step(restart=False):
         # with the CU-masked overlap the whole step (input transform included) runs on the non-default work stream
         ctx = torch.cuda.stream(H.work_stream()) if use_work else contextlib.nullcontext()
         with ctx:
+            if restart:
+                for t, init in initial_state:
+                    t.copy_(init)
             return step_()
 
     host_batch = None
@@ -279,18 +328,20 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    timer.enabled = True
+    if timer is not None:
+        timer.enabled = True
     step_no[0] = 0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out = step()
+    for i in range(args.steps):
+        out = step(restart=i == args.steps - 1)
     t_host = time.perf_counter() - t0           # host time to ENQUEUE the steps (diagnostic: how far the CPU runs ahead of the GPU)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
     per_rank_ms = [dt / args.steps * 1e3]
     if world > 1:
         # every rank's own wall time per step (load balance across ranks explains the first scaling run) and the maximum
@@ -302,6 +353,34 @@ def main():
     loss = float(out['total_loss'])
     H.raise_if_aborted()          # a persistent launch that gave up inside the timed region invalidates the run
     log('timed %d steps in %.3f s' % (args.steps, dt))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
+    # padded and valid input frames of the timed steps on THIS rank (buckets cycled in order), times the ranks
+    seen = [batches[i % len(batches)] for i in range(args.steps)]
+    frames = sum(int(bt[0].shape[0] * bt[0].shape[1]) for bt in seen) * world
+    valid = sum(int(bt[1].sum()) for bt in seen) * world
+    line = {
+        'metric': 'audio frames/sec (fwd+bwd) LibriSpeech-100 joint CTC-att',
+        'value': frames / dt, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': args.prec, 'data': 'synthetic',
+        'config': {'workload': workload_string(config, args, Dfeat),
+                   'global_batch': (B if args.shape == 'fixed' else [int(bt[0].shape[0]) for bt in batches]) if world == 1 else B * world,
+                   'frames_per_utt': T if args.shape == 'fixed' else [int(bt[0].shape[1]) for bt in batches], 'parallelism': 'dp%d' % world},
+        'valid_frames_per_s': valid / dt, 'loss': loss, 'per_rank_ms_per_step': per_rank_ms,
+        'per_rank_frames': [frames // world] * world, 'per_rank_max_T': [max(int(bt[0].shape[1]) for bt in batches)] * world, 'host_enqueue_ms_per_step': t_host / args.steps * 1e3,
+    }
+    if args.host_input:
+        line['input'] = 'pinned host memory, copied to the GPU inside every step (PCIe-inclusive; not the headline value)'
+    if args.full:
+        line.update(full_measurements(args, rank, world, config, Dfeat, V, B, timer, step))
+    if rank == 0:
+        print(json.dumps(line))
+
+
+def full_measurements(args, rank, world, config, Dfeat, V, B, timer, step):
+    """--full: the per-kernel figures (recurrence events of the timed region, three more steps with the other stages timed) and
+    the CPU baseline.  Every rank runs the extra steps; the returned fields matter on rank 0 only."""
     lstm_summ = timer.summary()
     post_steps = 3
     timer.names, timer.records, timer.enabled = {'asr_att_decoder_fwd', 'asr_att_decoder_bwd', 'asr_att_decoder_bwd_ex', 'asr_att_decoder_bwd_params', 'asr_gemm', 'asr_gemm16',
@@ -311,12 +390,8 @@ def main():
     torch.cuda.synchronize()
     timer.enabled = False
     post_summ = timer.summary()
-    # padded and valid input frames of the timed steps on THIS rank (buckets cycled in order), times the ranks
-    seen = [batches[i % len(batches)] for i in range(args.steps)]
-    frames = sum(int(bt[0].shape[0] * bt[0].shape[1]) for bt in seen) * world
-    valid = sum(int(bt[1].sum()) for bt in seen) * world
     if rank != 0:
-        return
+        return {}
 
     # ---- roofline of the dominant kernel: the persistent encoder-LSTM recurrence (one launch per layer and pass) ---
     summ = lstm_summ
@@ -400,23 +475,11 @@ def main():
     if not args.no_cpu_baseline and world == 1:
         log('cpu baseline (oracle) for ~%.0f s...' % args.cpu_seconds)
         cpu = cpu_baseline(config['model'], Dfeat, V, args.cpu_seconds, min(B, 16), args.frames, args.tokens)
-    line = {
-        'metric': 'audio frames/sec (fwd+bwd) LibriSpeech-100 joint CTC-att',
-        'value': frames / dt, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': args.prec, 'data': 'synthetic',
-        'config': {'workload': workload_string(config, args, Dfeat),
-                   'global_batch': (B if args.shape == 'fixed' else [int(bt[0].shape[0]) for bt in batches]) if world == 1 else B * world,
-                   'frames_per_utt': T if args.shape == 'fixed' else [int(bt[0].shape[1]) for bt in batches], 'parallelism': 'dp%d' % world},
-        'valid_frames_per_s': valid / dt, 'loss': loss, 'per_rank_ms_per_step': per_rank_ms,
-        'per_rank_frames': [frames // world] * world, 'per_rank_max_T': [max(int(bt[0].shape[1]) for bt in batches)] * world, 'host_enqueue_ms_per_step': t_host / args.steps * 1e3,
+    return {
         'stage_ms_per_step': dict([(k, v / args.steps) for k, v in tot.items()] +
                                   [(k, sum(ms for _, ms in v) / post_steps) for k, v in post_summ.items() if k not in ('asr_gemm', 'asr_gemm16', 'asr_conv3x3', 'asr_conv3x3_16', 'asr_conv3x3_16_wgrad')]),
         'roofline': roof, 'roofline_gemm': gemm, 'roofline_conv': conv, 'cpu_baseline': cpu,
     }
-    if args.host_input:
-        line['input'] = 'pinned host memory, copied to the GPU inside every step (PCIe-inclusive; not the headline value)'
-    print(json.dumps(line))
 
 
 if __name__ == '__main__':

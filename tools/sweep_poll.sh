@@ -2,7 +2,7 @@
 # Sweep of the polling delays of the persistent kernels on the bench step (ms per step + recurrence / decoder stage times).
 # usage: bash tools/sweep_poll.sh > gpurun_out/sweep_poll.txt
 run() {
-  env "$@" python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
