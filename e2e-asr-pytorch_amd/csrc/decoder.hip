@@ -662,6 +662,8 @@ __global__ __launch_bounds__(640) void att_bwd_energy_kernel(DecB p, int t, int 
         g_wp.store(d.Kn * d.A, tid, nthr, st_wp);
         g_wp.rest(d.Kn * d.A, tid, nthr, ld_wp, st_wp);
         for (int i = tid; i < d.Kn * (AP - d.A); i += nthr) { const int k = i / (AP - d.A); s_wpT[k * AP + d.A + (i - k * (AP - d.A))] = 0.f; }
+        // pad columns Kn..KP-1 of the conv tile: the KNMAX-wide sweep multiplies them by zero weights, and 0 * (stale LDS) can be NaN
+        for (int i = tid; i < TE * (KP - d.Kn); i += nthr) { const int ti = i / (KP - d.Kn); s_cv[ti * KP + d.Kn + (i - ti * (KP - d.Kn))] = 0.f; }
     }
     __syncthreads();
     // ---- stage 1: dattn of the tile (16 lanes per frame, float4 over E), block-wide dot, de

@@ -314,7 +314,7 @@ def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, 
     NH, adim = att.num_head, att.dim
     train = model.training
     dev = enc.device
-    enc_len = enc_len.to(dev).contiguous()
+    enc_len = enc_len.to(dev, torch.int64).contiguous()            # asr_masked_softmax_fwd reads int64_t lengths
     # ---- memory of the attention (computed once, reference :340-355)
     key = LinearActFn.apply(anchor, enc, att.proj_k.weight, att.proj_k.bias, H.ACT_TANH, prec)            # (B,T,NH*adim)
     if att.v_proj:

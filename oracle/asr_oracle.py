@@ -451,7 +451,7 @@ def att_decoder_variants(enc, enc_len, P, cfg, decode_step, teacher=None, masks=
             value = value.repeat(nh, 1, 1)          # head-major rows against batch-major keys: as the reference has it (:354)
     prev_att = None
     if cfg.att_mode == 'loc':
-        prev_att = torch.where(ar >= enc_len[:, None], torch.zeros(()), (1.0 / enc_len.float())[:, None].expand(B, Tp))
+        prev_att = torch.where(ar >= enc_len[:, None], torch.zeros(()), (1.0 / enc_len.to(enc.dtype))[:, None].expand(B, Tp))
         prev_att = prev_att[:, None, :].expand(B, nh, Tp)
     E = P['pre_embed.weight']
     last = E[torch.zeros(B, dtype=torch.long)]
@@ -511,7 +511,7 @@ def att_decoder(enc, enc_len, P, cfg, decode_step, teacher=None, state=None, ret
     ar = torch.arange(Tp)[None, :]
     mask = ar >= enc_len[:, None]
     key = attention_keys(enc, P)
-    prev_att = torch.where(mask, torch.zeros(()), (1.0 / enc_len.float())[:, None].expand(B, Tp))
+    prev_att = torch.where(mask, torch.zeros(()), (1.0 / enc_len.to(enc.dtype))[:, None].expand(B, Tp))
     E = P['pre_embed.weight']
     last = E[torch.zeros(B, dtype=torch.long)]
     logits_seq, att_seq = [], []

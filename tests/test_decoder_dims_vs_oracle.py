@@ -1,0 +1,483 @@
+"""The attention decoder at every decoder size its plans accept, against a float64 restatement of the same operation.
+
+The three implementations of the decoder loop - per-step kernels (csrc/decoder.hip), the LDS-resident persistent loop
+(csrc/decoder_persist.hip) and the streamed-tile persistent loop (csrc/decoder_stream.hip) - accept a wide range of
+(B, T', E, A, Dd, Kn, Ks) through their plan predicates, while the model tests only build config/librispeech_asr.yaml.
+Here `AttDecoderFn` runs on a synthetic encoder output at each point of a table of sizes, forced onto every plan the point
+accepts (asr_att_decoder_set_persistent 3: persistent, LDS-resident preferred; 3|4|8: persistent, streamed preferred;
+0: per-step kernels), and its logits, attention rows, decoder / attention / embedding gradients and encoder-output gradient
+are compared with oracle.asr_oracle.att_decoder run in float64 on the CPU (autograd for the backward).
+
+bf16 contraction mode runs on every plan; the weights and the encoder output are rounded to bf16 before either side sees
+them, so what remains is the kernels' own arithmetic.  fp32 mode (per-step kernels only: the persistent plans are bf16
+only) runs with unrounded inputs against a tight bound.  The bf16 bounds were measured once at the bench dims (B=16,
+T'=300, E=640, A=300, Dd=300, Kn=10, Ks=100, where the bench-shape and config-5 oracle tests pass) and apply unchanged to
+every other point.
+
+Each case asserts the plan it took: the plan queries say which persistent plan the preference selects, and the launch
+epoch of the work area (status word 1008, bumped by every persistent launch) says that the launch really happened - a
+persistent launch that cannot be made co-resident falls back to the per-step kernels without an error.
+
+The plan-table tests at the end are host-only (the predicates are host code) and run without a GPU.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import asr_oracle as O
+
+V = 31
+D_IN = 8                     # input features of the (unused) encoder: keeps its weights small
+BENCH = dict(B=16, Tp=300, E=640, A=300, Dd=300, Kn=10, Ks=100, NL=1, temp=0.5, L=4)
+EPOCH_BYTE = 4 * 1008        # launch epoch inside a persistent work area's status block (csrc/decoder_cluster.h, EPOCH_WORD)
+
+# Metrics: 'logits' / 'denc' / 'grad.<param>' relative Frobenius error (a gradient's norm floored at 1e-3 of the largest
+# gradient norm); 'proj.<param>' the systematic part of a gradient's error - its component along the reference, relative to
+# it (|<g - r, r>| / |r|^2: a whole tensor off by a factor shows here at full size while bf16 rounding noise averages out);
+# 'att' max-abs on the attention rows; 'gbias' max |d gen_energy.bias| / largest gradient norm (analytically zero).
+#
+# bf16 contraction mode, every plan.  BF16_BENCH is the largest error measured at the bench dims over ten input / weight
+# seeds (seed 0 is the one the matrix runs) and the three plans; the bound of every point is BF16_MARGIN times it, per
+# tensor, because the seed-to-seed spread differs between tensors (proj_q's small gradient spreads most).  Two documented
+# exceptions, each tied to the conditioning of the operation rather than to a kernel:
+#   * 'att' scales with 0.5 / temperature below the bench temperature: an energy error moves the softmax by error / temperature;
+#   * encoder outputs scaled by 30 or more (SATURATED) saturate the key and gate nonlinearities.  The fp32 per-step kernels'
+#     errors grow 16-32x there (denc 2.1e-5 vs 6.7e-7, grad up to 3.0e-5 vs 1.4e-6, six seeds); bf16 needs up to 5.2x the
+#     bench bound, so those two points get SATURATED_FACTOR = 8 and no other point does.
+BF16_BENCH = {
+    'logits': 1.27e-3, 'att': 3.62e-4, 'denc': 3.06e-3, 'gbias': 1.94e-4,
+    'grad.pre_embed.weight': 2.62e-3, 'grad.decoder.char_trans.weight': 3.52e-3, 'grad.decoder.char_trans.bias': 1.05e-7,
+    'grad.decoder.layers.weight_ih': 3.44e-3, 'grad.decoder.layers.weight_hh': 3.38e-3,
+    'grad.decoder.layers.bias_ih': 2.64e-3, 'grad.decoder.layers.bias_hh': 2.64e-3,
+    'grad.attention.proj_q.weight': 1.05e-2, 'grad.attention.proj_q.bias': 1.30e-2,
+    'grad.attention.proj_k.weight': 3.06e-3, 'grad.attention.proj_k.bias': 5.70e-3,
+    'grad.attention.att_layer.loc_conv.weight': 6.25e-3, 'grad.attention.att_layer.loc_proj.weight': 5.77e-3,
+    'grad.attention.att_layer.gen_energy.weight': 2.95e-3,
+    'proj.pre_embed.weight': 2.01e-4, 'proj.decoder.char_trans.weight': 8.12e-4, 'proj.decoder.char_trans.bias': 3.65e-8,
+    'proj.decoder.layers.weight_ih': 1.54e-3, 'proj.decoder.layers.weight_hh': 9.20e-4,
+    'proj.decoder.layers.bias_ih': 5.43e-4, 'proj.decoder.layers.bias_hh': 5.43e-4,
+    'proj.attention.proj_q.weight': 1.92e-3, 'proj.attention.proj_q.bias': 1.87e-3,
+    'proj.attention.proj_k.weight': 3.95e-4, 'proj.attention.proj_k.bias': 7.58e-4,
+    'proj.attention.att_layer.loc_conv.weight': 1.65e-3, 'proj.attention.att_layer.loc_proj.weight': 2.20e-3,
+    'proj.attention.att_layer.gen_energy.weight': 5.34e-4,
+}
+BF16_MARGIN = 2.5
+BF16_FLOOR = 1e-5            # char_trans.bias: a column sum of dlogits, exact up to fp32 rounding
+SATURATED, SATURATED_FACTOR = 30.0, 8.0
+# fp32 mode, per-step kernels.  Bench dims (ten seeds): logits 2.5e-7, att 2.7e-7, denc 6.7e-7, grad 1.4e-6, proj 2.3e-7,
+# gbias 2e-8; the largest anywhere in the matrix is 3.3e-5 (grad, T'=1, where proj_k's gradient is pure rounding).
+F32_TOL = {'logits': 1e-4, 'att': 1e-5, 'denc': 1e-4, 'grad': 1e-4, 'proj': 1e-4, 'gbias': 1e-6}
+
+
+def _bound(c, prec, key):
+    if prec == 'fp32':
+        return F32_TOL[key.split('.')[0]]
+    ref = BF16_BENCH[key.rsplit('_l', 1)[0] if key.startswith(('grad.decoder.layers', 'proj.decoder.layers')) else key]
+    b = max(BF16_MARGIN * ref, BF16_FLOOR)
+    if key == 'att' and c['temp'] < BENCH['temp']:
+        b *= BENCH['temp'] / c['temp']
+    if c['scale'] >= SATURATED:
+        b *= SATURATED_FACTOR
+    return b
+
+
+def _hipabi():
+    try:
+        from src import hipabi as H
+    except RuntimeError as e:                     # src.hipabi.HipLibraryMissing: the library is not built
+        if type(e).__name__ != 'HipLibraryMissing':
+            raise
+        pytest.skip(str(e))
+    return H
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# the dims table
+# --------------------------------------------------------------------------------------------------------------------
+def _case(cid, rows=None, scale=1.0, lens='mixed', int32=False, f32=True, **kw):
+    c = dict(BENCH)
+    c.update(kw)
+    c.update(id=cid, rows=rows, scale=scale, lens=lens, int32=int32, f32=f32)
+    return c
+
+
+SMALL = dict(B=8, Tp=200, E=256, Dd=64, Kn=4, Ks=10)       # the backward's floor of A
+MID = dict(B=8, E=256, A=128, Dd=128, Kn=5, Ks=20)
+
+CASES = [
+    _case('bench'),
+    # widths
+    _case('mid_A128', **MID),
+    _case('A256_E512_Ks50', B=16, Tp=500, E=512, A=256, Dd=256, Ks=50),
+    _case('A64', A=64, **SMALL),
+    _case('A66', A=66, **SMALL),
+    _case('A70', A=70, **SMALL),
+    _case('A320', A=320, Dd=320),
+    _case('A322', A=322, Dd=320),
+    _case('A301_odd', A=301),
+    _case('A384', A=384),
+    _case('A386', A=386),
+    _case('E648', E=648),
+    _case('E1024', B=8, E=1024),
+    _case('E302_no_half_copies', E=302),
+    _case('E34_no_half_copies', B=8, Tp=120, E=34, A=64, Dd=64, Kn=4, Ks=10),
+    _case('Dd512', B=8, E=512, A=256, Dd=512),
+    _case('Dd640', B=8, Dd=640),
+    # location filter
+    _case('Kn1', Kn=1),
+    _case('Kn5', Kn=5),
+    _case('Kn11', Kn=11),
+    _case('Kn16', Kn=16),
+    _case('Ks0', Ks=0),
+    _case('Ks1', Ks=1),
+    _case('Ks200', Ks=200),
+    _case('Ks512_Kn4', Kn=4, Ks=512),          # at Kn=10 the per-step kernels refuse this filter (test_wide_filter_refused)
+    _case('Ks_wider_than_Tp', B=8, Tp=60, Ks=100),
+    # softmax temperature
+    _case('temp1', temp=1.0),
+    _case('temp025', temp=0.25),
+    # decoder depth (per-step kernels only)
+    _case('NL2', NL=2),
+    _case('NL4', NL=4, Dd=160),
+    # batch and length edges
+    _case('B1', B=1),
+    _case('B8', B=8),
+    _case('B9', B=9),
+    _case('B64', B=64, rows=(40, 48)),
+    _case('enc_len1', lens='one'),
+    _case('Tp1', B=4, Tp=1),
+    _case('Tp1920_B8', B=8, Tp=1920, L=2, f32=False),
+    _case('Tp1921_B8', B=8, Tp=1921, L=2, f32=False),
+    # recurrence length
+    _case('L1', L=1),
+    _case('L72_mid', L=72, **MID),
+    # magnitude of the encoder output (the context partial sums travel as fp16 halves)
+    _case('scale1e-3', scale=1e-3),
+    _case('scale30', scale=30.0),
+    _case('mid_scale1e-3', scale=1e-3, **MID),
+    _case('mid_scale30', scale=30.0, **MID),
+    # int32 lengths must give the int64 results
+    _case('int32_lengths', int32=True, f32=False),
+]
+# T' at the LDS-resident limits (found with the plan query at run time) and one frame past them
+for _B in (8, 16):
+    for _kind in ('fwd', 'bwd'):
+        for _past in (0, 1):
+            CASES.append(_case('resident_%s_limit_B%d%s' % (_kind, _B, '+1' if _past else ''), B=_B, Tp=('limit', _kind, _past), L=2, f32=False))
+
+
+def _dims(H, c, Tp=None):
+    d = H.DecDims()
+    d.B, d.Tp, d.E, d.A = c['B'], Tp if Tp is not None else c['Tp'], c['E'], c['A']
+    d.Q, d.Dd, d.NL, d.V = c['Dd'] * c['NL'], c['Dd'], c['NL'], V
+    d.Kn, d.Ks, d.L = c['Kn'], c['Ks'], c['L']
+    d.temperature = float(c['temp'])
+    return d
+
+
+def _plans(H, d, flags):
+    """(forward, backward) plan that a launch under `flags` takes: 0 per-step, 1 LDS-resident, 2 streamed."""
+    old = H.lib().asr_att_decoder_set_persistent(flags)
+    try:
+        f = int(H.lib().asr_att_decoder_fwd_plan(ctypes.byref(d)))
+        b = int(H.lib().asr_att_decoder_bwd_plan(ctypes.byref(d)))
+    finally:
+        H.lib().asr_att_decoder_set_persistent(old)
+    return (f if flags & 1 else 0, b if flags & 2 else 0)
+
+
+def _resident_limit(H, c, kind):
+    """Largest T' that takes the LDS-resident plan of `kind` at the case's other dims."""
+    q = H.lib().asr_att_decoder_fwd_plan if kind == 'fwd' else H.lib().asr_att_decoder_bwd_plan
+    old = H.lib().asr_att_decoder_set_persistent(3)
+    try:
+        ok = [t for t in range(1, 4097) if int(q(ctypes.byref(_dims(H, c, t)))) == 1]
+    finally:
+        H.lib().asr_att_decoder_set_persistent(old)
+    assert ok and ok == list(range(ok[0], ok[-1] + 1)), 'the resident %s plan does not accept one interval of T\'' % kind
+    return ok[-1]
+
+
+def _resolve(H, c):
+    c = dict(c)
+    if isinstance(c['Tp'], tuple):
+        _, kind, past = c['Tp']
+        c['Tp'] = _resident_limit(H, c, kind) + past
+    return c
+
+
+def _runs(H, c):
+    """(precision, flags, (fwd plan, bwd plan)) for every distinct plan pair the case accepts."""
+    d = _dims(H, c)
+    out, seen = [], set()
+    for flags in (3, 3 | 4 | 8, 0):
+        p = _plans(H, d, flags)
+        if p not in seen:
+            seen.add(p)
+            out.append(('bf16', flags, p))
+    if c['f32']:
+        out.append(('fp32', 0, (0, 0)))
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# one comparison
+# --------------------------------------------------------------------------------------------------------------------
+def _model_cfg(c):
+    return {'ctc_weight': 0.0,
+            'encoder': {'vgg': 0, 'vgg_freq': -1, 'vgg_low_filt': -1, 'module': 'LSTM', 'bidirection': False, 'dim': [c['E']], 'dropout': [0.0], 'layer_norm': [False],
+                        'proj': [False], 'sample_rate': [1], 'sample_style': 'drop'},
+            'attention': {'mode': 'loc', 'dim': c['A'], 'num_head': 1, 'v_proj': False, 'temperature': c['temp'],
+                          'loc_kernel_size': c['Ks'], 'loc_kernel_num': c['Kn']},
+            'decoder': {'module': 'LSTM', 'dim': c['Dd'], 'layer': c['NL'], 'dropout': 0.0}}
+
+
+def _inputs(c, seed):
+    B, Tp, L = c['B'], c['Tp'], c['L']
+    g = torch.Generator().manual_seed(seed)
+    enc = torch.randn(B, Tp, c['E'], generator=g, dtype=torch.float64) * c['scale']
+    enc_len = torch.randint(max(Tp // 3, 1), Tp + 1, (B,), generator=g)
+    enc_len[0] = Tp
+    if c['lens'] == 'one' and B > 1:
+        enc_len[1] = 1
+    teacher = torch.randint(1, V, (B, L), generator=g)
+    dlog = torch.randn(B, L, V, generator=g, dtype=torch.float64) * 0.1
+    r0, r1 = c['rows'] or (0, B)
+    dlog[:r0] = 0
+    dlog[r1:] = 0
+    return enc, enc_len, teacher, dlog
+
+
+def _oracle(c, sd, enc, enc_len, teacher, dlog):
+    """float64 forward + autograd backward on the rows that carry a gradient."""
+    r0, r1 = c['rows'] or (0, c['B'])
+    cfg = O.ModelCfg(_model_cfg(c), D_IN, V)
+    P = {k: v.double().clone().requires_grad_(True) for k, v in sd.items()}
+    e = enc[r0:r1].clone().requires_grad_(True)
+    logits, att = O.att_decoder(e, enc_len[r0:r1], P, cfg, c['L'], teacher=teacher[r0:r1])
+    (logits * dlog[r0:r1]).sum().backward()
+    grads = {k: p.grad for k, p in P.items() if p.grad is not None}
+    return logits.detach(), att.detach(), grads, e.grad
+
+
+def _device(H, F, model, c, prec, flags, enc, enc_len, teacher, dlog):
+    """One forward + backward of AttDecoderFn under `flags`; returns the results and whether each pass ran persistent."""
+    B, Tp, L = c['B'], c['Tp'], c['L']
+    d = F._dec_dims(model, B, Tp, L)
+    dev = torch.device('cuda', torch.cuda.current_device())         # the work areas are keyed by 'cuda:N'
+
+    bwd_area = any(_plans(H, d, f)[1] for f in (3, 3 | 4 | 8))        # else the offset below lies in the per-step kernels' buffers
+
+    def epoch(kind):
+        if kind == 'bwd' and not bwd_area:
+            return 0
+        k = (kind, tuple(getattr(d, f) for f, _ in d._fields_), str(dev))
+        ws = F._DEC_WS.get(k)
+        if ws is None:
+            return 0
+        off = EPOCH_BYTE + (int(H.lib().asr_att_decoder_bwd_status_offset(ctypes.byref(d))) if kind == 'bwd' else 0)
+        return int(ws[off:off + 4].view(torch.int32).item())
+
+    old = H.lib().asr_att_decoder_set_persistent(flags)
+    try:
+        e0 = (epoch('fwd'), epoch('bwd'))
+        model.zero_grad()
+        x = enc.to(dev, torch.float32).requires_grad_(True)
+        lens = enc_len.to(dev, torch.int32 if c['int32'] else torch.int64)
+        logits, att, _ = F.AttDecoderFn.apply(model._anchor, x, lens, teacher.to(dev), L, model, H.BF16 if prec == 'bf16' else H.F32)
+        (logits * dlog.to(dev, torch.float32)).sum().backward()
+        H.raise_if_aborted()
+        e1 = (epoch('fwd'), epoch('bwd'))
+    finally:
+        H.lib().asr_att_decoder_set_persistent(old)
+    names = [n for n, _ in model.named_parameters() if n.startswith(('decoder', 'attention', 'pre_embed'))]
+    grads = {n: p.grad.detach().double().cpu() for n, p in model.named_parameters() if n in names}
+    ran = (e1[0] - e0[0], e1[1] - e0[1])
+    return logits.detach().double().cpu(), att.detach().double().cpu(), grads, x.grad.double().cpu(), ran
+
+
+def _errors(c, got, want):
+    """Relative Frobenius errors per tensor, max-abs on the attention rows, gen_energy.bias against the gradient scale."""
+    r0, r1 = c['rows'] or (0, c['B'])
+    logits, att, grads, denc = got
+    rl, ra, rg, rd = want
+    rel = lambda a, b: float((a - b).norm() / (b.norm() + 1e-30))
+    err = {'logits': rel(logits[r0:r1], rl), 'att': float((att[r0:r1] - ra).abs().max()), 'denc': rel(denc[r0:r1], rd)}
+    # rows without a gradient stay without one
+    rest = torch.cat([denc[:r0].flatten(), denc[r1:].flatten()])
+    err['denc_outside_rows'] = float(rest.abs().max()) if rest.numel() else 0.0
+    gmax = max(float(g.norm()) for g in rg.values())
+    for n, g in grads.items():
+        assert n in rg, n
+        if n.endswith('gen_energy.bias'):
+            # analytically zero (softmax is shift invariant): both sides are rounding noise
+            err['gbias'] = max(float(g.abs().max()), float(rg[n].abs().max())) / gmax
+        else:
+            den = max(float(rg[n].norm()), 1e-3 * gmax)
+            err['grad.' + n] = float((g - rg[n]).norm() / den)
+            err['proj.' + n] = abs(float(((g - rg[n]) * rg[n]).sum())) / den ** 2
+    return err
+
+
+def _check(c, prec, err):
+    bad = []
+    for k, v in err.items():
+        t = 0.0 if k == 'denc_outside_rows' else _bound(c, prec, k)
+        if not (v <= t):
+            bad.append('%-48s %.3e > %.2e' % (k, v, t))
+    return bad
+
+
+def measure(c, seed=0):
+    """Every run of one case: [(precision, flags, plans, launches seen, errors)].  Asserts the plan taken."""
+    H = _hipabi()
+    from src import functions as F
+    from src.asr import ASR
+    c = _resolve(H, c)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    try:
+        return c, _measure_runs(H, F, ASR, c, seed)
+    finally:
+        torch.set_num_threads(threads)
+
+
+def _measure_runs(H, F, ASR, c, seed):
+    mc = _model_cfg(c)
+    sd = O.seeded_state_dict(O.param_shapes(O.ModelCfg(mc, D_IN, V)), 1000 + seed)
+    enc, enc_len, teacher, dlog = _inputs(c, 17 + seed)
+    refs, out = {}, []
+    for prec, flags, plans in _runs(H, c):
+        if prec not in refs:
+            sdp = {k: v.bfloat16().float() for k, v in sd.items()} if prec == 'bf16' else sd
+            encp = enc.float().bfloat16().double() if prec == 'bf16' else enc.float().double()
+            model = ASR(D_IN, V, c['B'], prec=prec, **mc)
+            model.load_state_dict(sdp)
+            model = model.cuda().train()
+            refs[prec] = (model, encp, _oracle(c, sdp, encp, enc_len, teacher, dlog))
+        model, encp, want = refs[prec]
+        d = F._dec_dims(model, c['B'], c['Tp'], c['L'])
+        assert _plans(H, d, flags) == plans
+        *got, ran = _device(H, F, model, c, prec, flags, encp, enc_len, teacher, dlog)
+        # a persistent plan launched exactly once per pass; the per-step kernels launched none
+        assert ran == (int(plans[0] > 0), int(plans[1] > 0)), '%s %s flags %d: plans %s, persistent launches %s' % (c['id'], prec, flags, plans, ran)
+        out.append((prec, flags, plans, _errors(c, got, want)))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', CASES, ids=[c['id'] for c in CASES])
+def test_decoder_vs_float64_oracle(case):
+    c, runs = measure(case)
+    report = []
+    for prec, flags, plans, err in runs:
+        bad = _check(c, prec, err)
+        report += ['%s flags %d plans %s: %s' % (prec, flags, plans, b) for b in bad]
+    assert not report, 'dims %s\n' % ({k: c[k] for k in ('B', 'Tp', 'E', 'A', 'Dd', 'Kn', 'Ks', 'NL', 'temp', 'L', 'scale')},) + '\n'.join(report)
+
+
+@pytest.mark.gpu
+def test_wide_filter_refused():
+    """Kn=10 x Ks=512 at the bench dims: the streamed forward plan accepts it, but the per-step energy kernel's tile does not fit
+    the LDS and the backward's filter bank is too large, so the decoder refuses the shape with an error up front."""
+    H = _hipabi()
+    from src import functions as F
+    from src.asr import ASR
+    c = dict(BENCH, Ks=512)
+    model = ASR(D_IN, V, c['B'], prec='bf16', **_model_cfg(c)).cuda()
+    enc = torch.zeros(c['B'], c['Tp'], c['E'], device='cuda')
+    lens = torch.full((c['B'],), c['Tp'], dtype=torch.int64, device='cuda')
+    teacher = torch.ones(c['B'], c['L'], dtype=torch.int64, device='cuda')
+    with pytest.raises(RuntimeError, match='LDS'):
+        F.AttDecoderFn.apply(model._anchor, enc, lens, teacher, c['L'], model, H.BF16)
+    torch.cuda.synchronize()
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# host-only: the plan predicates' acceptance boundaries and the coverage of the matrix above
+# --------------------------------------------------------------------------------------------------------------------
+def _q(H, **kw):
+    c = dict(BENCH)
+    c.update(kw)
+    d = _dims(H, c)
+    return [_plans(H, d, 3), _plans(H, d, 3 | 4 | 8)]
+
+
+# (dims, [(fwd, bwd) LDS-resident preferred, (fwd, bwd) streamed preferred]); 0 per-step kernels, 1 LDS-resident, 2 streamed
+PLAN_TABLE = [
+    ({}, [(1, 1), (2, 2)]),
+    (dict(B=8, E=256, A=128, Dd=128, Kn=5, Ks=20), [(1, 1), (2, 2)]),
+    (dict(B=16, Tp=500, E=512, A=256, Dd=256, Ks=50), [(1, 1), (2, 2)]),
+    # A: backward limit 320 (even only), forward limit 384; the backward's floor: none at 64, streamed only at 66, both at 70
+    (dict(A=320, Dd=320), [(1, 1), (2, 2)]),
+    (dict(A=322, Dd=320), [(1, 0), (2, 0)]),
+    (dict(A=301), [(1, 0), (2, 0)]),
+    (dict(A=384), [(1, 0), (2, 0)]),
+    (dict(A=386), [(0, 0), (0, 0)]),
+    (dict(A=64, **SMALL), [(1, 0), (2, 0)]),
+    (dict(A=66, **SMALL), [(1, 2), (2, 2)]),
+    (dict(A=70, **SMALL), [(1, 1), (2, 2)]),
+    # E: backward limit 640, forward multiples of 8
+    (dict(E=648), [(1, 0), (2, 0)]),
+    (dict(B=8, E=1024), [(1, 0), (2, 0)]),
+    (dict(E=302), [(0, 0), (0, 0)]),
+    # Dd: forward limit 640
+    (dict(B=8, Dd=640), [(1, 0), (2, 0)]),
+    (dict(B=8, Dd=641), [(0, 0), (0, 0)]),
+    # Kn: persistent plans up to 10
+    (dict(Kn=1), [(1, 1), (2, 2)]),
+    (dict(Kn=5), [(1, 1), (2, 2)]),
+    (dict(Kn=10), [(1, 1), (2, 2)]),
+    (dict(Kn=11), [(0, 0), (0, 0)]),
+    (dict(Kn=16), [(0, 0), (0, 0)]),
+    # Ks
+    (dict(Ks=0), [(1, 1), (2, 2)]),
+    (dict(Ks=1), [(1, 1), (2, 2)]),
+    (dict(Ks=200), [(1, 1), (2, 2)]),
+    (dict(Ks=512), [(2, 0), (2, 0)]),
+    (dict(Kn=4, Ks=512), [(2, 1), (2, 2)]),
+    # batch and length
+    (dict(B=1), [(1, 1), (2, 2)]),
+    (dict(B=4, Tp=1), [(2, 1), (2, 2)]),
+    (dict(B=64), [(2, 2), (2, 2)]),
+    (dict(B=8, Tp=1920), [(2, 2), (2, 2)]),
+    (dict(B=8, Tp=1921), [(2, 0), (2, 0)]),
+    (dict(B=8, Tp=2000), [(2, 0), (2, 0)]),
+    # more than one decoder layer: per-step kernels
+    (dict(NL=2), [(0, 0), (0, 0)]),
+]
+
+
+@pytest.mark.parametrize('kw,want', PLAN_TABLE, ids=[','.join('%s=%s' % i for i in kw.items()) or 'bench' for kw, _ in PLAN_TABLE])
+def test_plan_table(kw, want):
+    H = _hipabi()
+    assert _q(H, **kw) == want
+
+
+def test_resident_T_limits():
+    """The LDS-resident plans' T' limits at the bench dims (the GPU matrix finds them with the same query)."""
+    H = _hipabi()
+    got = {(B, k): _resident_limit(H, dict(BENCH, B=B), k) for B in (8, 16) for k in ('fwd', 'bwd')}
+    assert got == {(8, 'fwd'): 1200, (8, 'bwd'): 756, (16, 'fwd'): 640, (16, 'bwd'): 600}, got
+    for (B, k), t in got.items():
+        i = 0 if k == 'fwd' else 1
+        assert _q(H, B=B, Tp=t)[0][i] == 1 and _q(H, B=B, Tp=t + 1)[0][i] == 2
+
+
+def test_matrix_covers_every_plan():
+    """Forward plans 1 and 2 and backward plans 1 and 2 each run at >= 4 points of the GPU matrix that differ from the
+    bench point in A, E, Dd, Kn or Ks (every case asserts that it took the plan the query reports)."""
+    H = _hipabi()
+    cover = {}
+    for c in CASES:
+        c = _resolve(H, c)
+        if all(c[k] == BENCH[k] for k in ('A', 'E', 'Dd', 'Kn', 'Ks')):
+            continue
+        for prec, flags, (f, b) in _runs(H, c):
+            cover.setdefault(('fwd', f), set()).add(c['id'])
+            cover.setdefault(('bwd', b), set()).add(c['id'])
+    for key in (('fwd', 1), ('fwd', 2), ('bwd', 1), ('bwd', 2), ('fwd', 0), ('bwd', 0)):
+        assert len(cover.get(key, ())) >= 4, (key, sorted(cover.get(key, ())))
