@@ -3,7 +3,9 @@ threshold rule, joint CTC / RNN-LM scoring, average-score pruning — batched ov
 GPU.  `forward` keeps the whole search on the device: per output position one attention+decoder step, one CTC
 prefix-score launch, one LM step and ONE bookkeeping kernel (asr_beam_step: fusion, top-k, <eos> rule, pruning, finals)
 for all U x beam rows; nothing is copied to the host until the search has ended.  `forward_host` is the first
-implementation (score table on the host each step), kept as a cross-check."""
+implementation (score table on the host each step), kept as a cross-check for the shipped decoder.  Models the decode
+kernels do not cover (GRU, dot / multi-head attention, v_proj, deep LSTM) take the step of src/decode_variants.py; both
+searches share the bookkeeping of _BeamBook."""
 import ctypes
 import math
 
@@ -63,9 +65,10 @@ class BeamDecoder(nn.Module):
         assert emb_decoder is None, 'embedding-fusion decoding is outside the HIP path'
         self.beam_size, self.min_len_ratio, self.max_len_ratio, self.asr = beam_size, min_len_ratio, max_len_ratio, asr
         assert self.asr.enable_att
-        if not (self.asr.decoder.fast and self.asr.attention.fast):
-            raise NotImplementedError('beam search runs on the decode kernels of the shipped decoder (LSTM, location-aware attention, '
-                                      'one head); the model variants of src/variants.py train and validate greedily only')
+        # the decode kernels of the shipped decoder (asr_att_decoder_step) cover an LSTM of <= MAX_DEC_LAYERS layers with
+        # location-aware single-head attention and no value projection, whatever its dropout (inactive in eval); every other
+        # model runs the variant search of src/decode_variants.py
+        self.fast = self.asr.decoder.layers.module == 'LSTM' and self.asr.decoder.layer <= H.MAX_DEC_LAYERS and self.asr.attention.fast
         self.apply_ctc = ctc_weight > 0
         if self.apply_ctc:
             assert self.asr.ctc_weight > 0, 'ASR was not trained with CTC decoder'
@@ -122,102 +125,31 @@ class BeamDecoder(nn.Module):
     def forward(self, audio_feature, feature_len):
         """audio_feature (U,T,D) zero-padded, feature_len (U).  U == 1: the reference's return value (list of <= beam
         Hypothesis, best first); U > 1: a list of such lists.  No device-to-host copy inside the search loop."""
-        asr, dev, st = self.asr, audio_feature.device, H.stream_ptr()
-        prec, V, beam = asr.prec, asr.vocab_size, self.beam_size
         U = audio_feature.shape[0]
         flens = [int(x) for x in feature_len.reshape(-1).tolist()]
         max_lens = [int(math.ceil(f * self.max_len_ratio)) for f in flens]
         min_lens = [int(math.ceil(f * self.min_len_ratio)) for f in flens]
         Lmax = max(max(max_lens), 1)
         enc, enc_len, tlen, ctc_lp = self._encode(audio_feature, feature_len)
-        Tp, E = enc.shape[1], enc.shape[2]
-        R = U * beam
-        i32 = lambda *s_: torch.zeros(s_, dtype=torch.int32, device=dev)
-        f32 = lambda *s_: torch.zeros(s_, dtype=torch.float32, device=dev)
-        d = F_hip._dec_dims(asr, R, Tp, Lmax + 1)
-        sd = F_hip._dec_state(d, dev, save_conv=False)
-        sd['tokens'].zero_()
-        w = H.dec_weights_struct(F_hip._dec_tensors(asr, False), d.NL)
-        s = H.dec_state_struct(sd)
-        enc_rep = enc.unsqueeze(1).expand(U, beam, Tp, E).reshape(R, Tp, E).contiguous()
-        len_rep = enc_len.unsqueeze(1).expand(U, beam).reshape(R).contiguous()
-        H.call('asr_att_decoder_keys', ctypes.byref(d), ctypes.byref(w), H.ptr(enc_rep), H.ptr(sd['key']), prec, st)
-        C = self.ctc_beam_size if self.apply_ctc else 0
-        ctc_r = ctc_rn = cand = psi = None
-        if self.apply_ctc:
-            ctc_r, ctc_rn = f32(R, Tp, 2), f32(R, C, Tp, 2)
-            cand, psi = i32(R, C), f32(R, C)
-            H.call('asr_ctc_prefix_init_batched', H.ptr(ctc_lp), H.ptr(tlen), H.ptr(ctc_r), R, beam, Tp, V, st)
-        lm_state = None
-        if self.apply_lm:
-            self.lm.prec = prec
-            lm_state = self.lm.init_state(R, dev)
-        # hypothesis state, double buffered; row u*beam is the empty hypothesis of utterance u
-        state = [{'alive': i32(R), 'sum': f32(R), 'ctcp': f32(R), 'len': i32(R), 'seq': i32(R, Lmax), 'sc': f32(R, Lmax)} for _ in range(2)]
-        state[0]['alive'][::beam] = 1
-        last_tok, parent, ctc_index = i32(R), torch.zeros(R, dtype=torch.int64, device=dev), torch.zeros(R, dtype=torch.int64, device=dev)
-        min_len_d = torch.tensor(min_lens, dtype=torch.int32, device=dev)
-        max_len_d = torch.tensor(max_lens, dtype=torch.int32, device=dev)
-        done = i32(U)
-        fin_n, fin_len, fin_avg = i32(U), i32(U, beam), f32(U, beam)
-        fin_seq, fin_sc = i32(U, beam, Lmax + 1), f32(U, beam, Lmax + 1)
-        att_lp = f32(R, V)
-        tmp = {k: torch.empty_like(sd[k][:, 0]) for k in ('hs', 'cs', 'att')}
+        if self.fast:
+            dec = _FastStep(self.asr, enc, enc_len, self.beam_size, Lmax)
+        else:
+            from src.decode_variants import VariantStep
+            dec = VariantStep(self.asr, enc, enc_len, self.beam_size, Lmax)
+        book = _BeamBook(self, U, Lmax, min_lens, max_lens, ctc_lp, tlen, dec.tokens)
         for t in range(Lmax):
-            a, b = state[t & 1], state[(t + 1) & 1]
-            H.call('asr_att_decoder_step', ctypes.byref(d), ctypes.byref(w), H.ptr(enc_rep), H.ptr(len_rep), ctypes.byref(s), t, prec, st)
-            logits = sd['logits'][:, t].contiguous()
-            H.call('asr_log_softmax', H.ptr(logits), H.ptr(att_lp), R, V, st)
-            if self.apply_ctc:
-                H.call('asr_beam_candidates', H.ptr(att_lp), H.ptr(cand), R, V, C, st)
-                H.call('asr_ctc_prefix_score_batched', H.ptr(ctc_lp), H.ptr(tlen), H.ptr(ctc_r), H.ptr(cand), H.ptr(a['len']), H.ptr(last_tok),
-                       H.ptr(psi), H.ptr(ctc_rn), R, C, Tp, V, beam, st)
-            lm_lp = lm_new = None
-            if self.apply_lm:
-                lm_lp, lm_new = self.lm.step(sd['tokens'][:, t].contiguous(), lm_state)
-            args = H.BeamStep()
-            for name, ten in (('att_logp', att_lp), ('lm_logp', lm_lp), ('psi', psi), ('candidates', cand), ('alive_in', a['alive']),
-                              ('sum_in', a['sum']), ('ctcp_in', a['ctcp']), ('len_in', a['len']), ('seq_in', a['seq']), ('score_in', a['sc']),
-                              ('alive_out', b['alive']), ('sum_out', b['sum']), ('ctcp_out', b['ctcp']), ('len_out', b['len']),
-                              ('seq_out', b['seq']), ('score_out', b['sc']), ('last_token', last_tok), ('parent', parent),
-                              ('ctc_index', ctc_index), ('tokens', sd['tokens']), ('min_len', min_len_d), ('max_len', max_len_d),
-                              ('done', done), ('fin_n', fin_n), ('fin_len', fin_len), ('fin_avg', fin_avg), ('fin_seq', fin_seq),
-                              ('fin_score', fin_sc)):
-                setattr(args, name, ten.data_ptr() if ten is not None else None)
-            args.tokens_ld = sd['tokens'].shape[1]
-            args.U, args.beam, args.V, args.C, args.Lmax, args.t = U, beam, V, C, Lmax, t
-            args.ctc_weight = float(self.ctc_w) if self.apply_ctc else 0.0
-            args.lm_weight = float(self.lm_w) if self.apply_lm else 0.0
-            args.eos_threshold = 1.5
-            H.call('asr_beam_step', ctypes.byref(args), st)
-            # state of the survivors: new row i <- row parent[i] (device gathers; no host round trip)
-            for name in ('hs', 'cs', 'att'):
-                src = sd[name][:, t]
-                width = src[0].numel()
-                H.call('asr_gather_rows', H.ptr(src), H.ptr(parent), H.ptr(tmp[name]), R, width, src.stride(0), width, R, st)
-                src.copy_(tmp[name])
-            if self.apply_ctc:
-                H.call('asr_gather_rows', H.ptr(ctc_rn), H.ptr(ctc_index), H.ptr(ctc_r), R, Tp * 2, Tp * 2, Tp * 2, R * C, st)
-            if self.apply_lm:
-                hn, cn = torch.empty_like(lm_new[0]), torch.empty_like(lm_new[1])
-                for l in range(self.lm.n_layers):
-                    H.call('asr_gather_rows', H.ptr(lm_new[0][l]), H.ptr(parent), H.ptr(hn[l]), R, self.lm.dim, self.lm.dim, self.lm.dim, R, st)
-                    H.call('asr_gather_rows', H.ptr(lm_new[1][l]), H.ptr(parent), H.ptr(cn[l]), R, self.lm.dim, self.lm.dim, self.lm.dim, R, st)
-                lm_state = (hn, cn)
-            if (t & 15) == 15 and bool(done.all()):          # every 16 positions: stop early when every search has ended
+            parent = book.step(t, dec.step(t))
+            dec.reorder(t, parent)                          # state of the survivors: new row i <- row parent[i]
+            if (t & 15) == 15 and book.all_done():          # every 16 positions: stop early when every search has ended
                 break
-        n_c, len_c, seq_c, sc_c = fin_n.cpu(), fin_len.cpu(), fin_seq.cpu(), fin_sc.cpu()
-        out = []
-        for u in range(U):
-            hyps = []
-            for i in range(int(n_c[u])):
-                l = int(len_c[u, i])
-                hyps.append(Hypothesis(i, seq_c[u, i, :l].tolist(), sc_c[u, i, :l].tolist()))
-            out.append(hyps)
-        return out[0] if U == 1 else out
+        return book.readout()
 
     @torch.no_grad()
     def forward_host(self, audio_feature, feature_len):
+        """First implementation (score table on the host every step), shipped decoder only; kept as a cross-check."""
+        if not self.fast:
+            raise NotImplementedError('forward_host covers the shipped decoder only (LSTM, location-aware attention, one head); '
+                                      'decode this model with forward')
         assert audio_feature.shape[0] == 1, 'Batchsize == 1 is required for beam search'
         asr, dev, st = self.asr, audio_feature.device, H.stream_ptr()
         prec = asr.prec
@@ -301,3 +233,129 @@ class BeamDecoder(nn.Module):
         finals += hyps
         finals.sort(key=lambda o: o.avgScore(), reverse=True)
         return finals[:self.beam_size]
+
+
+class _FastStep(object):
+    """Decoder state and step of the shipped decoder on the decode kernels (asr_att_decoder_keys / _step)."""
+
+    def __init__(self, asr, enc, enc_len, beam, Lmax):
+        U, Tp, E = enc.shape
+        R = U * beam
+        self.asr, self.R = asr, R
+        self.d = F_hip._dec_dims(asr, R, Tp, Lmax + 1)
+        self.sd = F_hip._dec_state(self.d, enc.device, save_conv=False)
+        self.sd['tokens'].zero_()
+        self.tokens = self.sd['tokens']
+        self.w = H.dec_weights_struct(F_hip._dec_tensors(asr, False), self.d.NL)
+        self.s = H.dec_state_struct(self.sd)
+        self.enc_rep = enc.unsqueeze(1).expand(U, beam, Tp, E).reshape(R, Tp, E).contiguous()
+        self.len_rep = enc_len.unsqueeze(1).expand(U, beam).reshape(R).contiguous()
+        H.call('asr_att_decoder_keys', ctypes.byref(self.d), ctypes.byref(self.w), H.ptr(self.enc_rep), H.ptr(self.sd['key']), asr.prec,
+               H.stream_ptr())
+        self.tmp = {k: torch.empty_like(self.sd[k][:, 0]) for k in ('hs', 'cs', 'att')}
+
+    def step(self, t):
+        H.call('asr_att_decoder_step', ctypes.byref(self.d), ctypes.byref(self.w), H.ptr(self.enc_rep), H.ptr(self.len_rep),
+               ctypes.byref(self.s), t, self.asr.prec, H.stream_ptr())
+        return self.sd['logits'][:, t].contiguous()
+
+    def reorder(self, t, parent):
+        R, st = self.R, H.stream_ptr()
+        for name in ('hs', 'cs', 'att'):
+            src = self.sd[name][:, t]
+            width = src[0].numel()
+            H.call('asr_gather_rows', H.ptr(src), H.ptr(parent), H.ptr(self.tmp[name]), R, width, src.stride(0), width, R, st)
+            src.copy_(self.tmp[name])
+
+
+class _BeamBook(object):
+    """The bookkeeping of one output position that both searches share (reference src/decode.py:117-177): attention
+    log-probs, CTC candidates and prefix scores, the LM step, asr_beam_step (fusion, top-k, <eos> rule, pruning, finals)
+    and the re-ordering of the CTC / LM states; the finals are read out once the search has ended.  `tokens` (R, Lmax+1)
+    int64 is the decoder's token table: asr_beam_step writes column t+1."""
+
+    def __init__(self, bd, U, Lmax, min_lens, max_lens, ctc_lp, tlen, tokens):
+        dev = tokens.device
+        beam, V = bd.beam_size, bd.asr.vocab_size
+        R = U * beam
+        i32 = lambda *s_: torch.zeros(s_, dtype=torch.int32, device=dev)
+        f32 = lambda *s_: torch.zeros(s_, dtype=torch.float32, device=dev)
+        self.bd, self.U, self.beam, self.V, self.R, self.Lmax, self.tokens = bd, U, beam, V, R, Lmax, tokens
+        self.Tp = ctc_lp.shape[1] if ctc_lp is not None else 0
+        self.ctc_lp, self.tlen = ctc_lp, tlen
+        self.C = bd.ctc_beam_size if bd.apply_ctc else 0
+        self.ctc_r = self.ctc_rn = self.cand = self.psi = None
+        st = H.stream_ptr()
+        if bd.apply_ctc:
+            C, Tp = self.C, self.Tp
+            self.ctc_r, self.ctc_rn = f32(R, Tp, 2), f32(R, C, Tp, 2)
+            self.cand, self.psi = i32(R, C), f32(R, C)
+            H.call('asr_ctc_prefix_init_batched', H.ptr(ctc_lp), H.ptr(tlen), H.ptr(self.ctc_r), R, beam, Tp, V, st)
+        self.lm_state = None
+        if bd.apply_lm:
+            bd.lm.prec = bd.asr.prec
+            self.lm_state = bd.lm.init_state(R, dev)
+        # hypothesis state, double buffered; row u*beam is the empty hypothesis of utterance u
+        self.state = [{'alive': i32(R), 'sum': f32(R), 'ctcp': f32(R), 'len': i32(R), 'seq': i32(R, Lmax), 'sc': f32(R, Lmax)} for _ in range(2)]
+        self.state[0]['alive'][::beam] = 1
+        self.last_tok, self.parent = i32(R), torch.zeros(R, dtype=torch.int64, device=dev)
+        self.ctc_index = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.min_len_d = torch.tensor(min_lens, dtype=torch.int32, device=dev)
+        self.max_len_d = torch.tensor(max_lens, dtype=torch.int32, device=dev)
+        self.done = i32(U)
+        self.fin_n, self.fin_len, self.fin_avg = i32(U), i32(U, beam), f32(U, beam)
+        self.fin_seq, self.fin_sc = i32(U, beam, Lmax + 1), f32(U, beam, Lmax + 1)
+        self.att_lp = f32(R, V)
+
+    def step(self, t, logits):
+        """logits (R,V) of output position t -> parent (R) int64: the source row of every surviving row."""
+        bd, R, V, C, Tp, st = self.bd, self.R, self.V, self.C, self.Tp, H.stream_ptr()
+        a, b = self.state[t & 1], self.state[(t + 1) & 1]
+        att_lp = self.att_lp
+        H.call('asr_log_softmax', H.ptr(logits), H.ptr(att_lp), R, V, st)
+        if bd.apply_ctc:
+            H.call('asr_beam_candidates', H.ptr(att_lp), H.ptr(self.cand), R, V, C, st)
+            H.call('asr_ctc_prefix_score_batched', H.ptr(self.ctc_lp), H.ptr(self.tlen), H.ptr(self.ctc_r), H.ptr(self.cand), H.ptr(a['len']),
+                   H.ptr(self.last_tok), H.ptr(self.psi), H.ptr(self.ctc_rn), R, C, Tp, V, self.beam, st)
+        lm_lp = lm_new = None
+        if bd.apply_lm:
+            lm_lp, lm_new = bd.lm.step(self.tokens[:, t].contiguous(), self.lm_state)
+        args = H.BeamStep()
+        for name, ten in (('att_logp', att_lp), ('lm_logp', lm_lp), ('psi', self.psi), ('candidates', self.cand), ('alive_in', a['alive']),
+                          ('sum_in', a['sum']), ('ctcp_in', a['ctcp']), ('len_in', a['len']), ('seq_in', a['seq']), ('score_in', a['sc']),
+                          ('alive_out', b['alive']), ('sum_out', b['sum']), ('ctcp_out', b['ctcp']), ('len_out', b['len']),
+                          ('seq_out', b['seq']), ('score_out', b['sc']), ('last_token', self.last_tok), ('parent', self.parent),
+                          ('ctc_index', self.ctc_index), ('tokens', self.tokens), ('min_len', self.min_len_d), ('max_len', self.max_len_d),
+                          ('done', self.done), ('fin_n', self.fin_n), ('fin_len', self.fin_len), ('fin_avg', self.fin_avg),
+                          ('fin_seq', self.fin_seq), ('fin_score', self.fin_sc)):
+            setattr(args, name, ten.data_ptr() if ten is not None else None)
+        args.tokens_ld = self.tokens.shape[1]
+        args.U, args.beam, args.V, args.C, args.Lmax, args.t = self.U, self.beam, V, C, self.Lmax, t
+        args.ctc_weight = float(bd.ctc_w) if bd.apply_ctc else 0.0
+        args.lm_weight = float(bd.lm_w) if bd.apply_lm else 0.0
+        args.eos_threshold = 1.5
+        H.call('asr_beam_step', ctypes.byref(args), st)
+        if bd.apply_ctc:
+            H.call('asr_gather_rows', H.ptr(self.ctc_rn), H.ptr(self.ctc_index), H.ptr(self.ctc_r), R, Tp * 2, Tp * 2, Tp * 2, R * C, st)
+        if bd.apply_lm:
+            lm, dim = bd.lm, bd.lm.dim
+            hn, cn = torch.empty_like(lm_new[0]), torch.empty_like(lm_new[1])
+            for l in range(lm.n_layers):
+                H.call('asr_gather_rows', H.ptr(lm_new[0][l]), H.ptr(self.parent), H.ptr(hn[l]), R, dim, dim, dim, R, st)
+                H.call('asr_gather_rows', H.ptr(lm_new[1][l]), H.ptr(self.parent), H.ptr(cn[l]), R, dim, dim, dim, R, st)
+            self.lm_state = (hn, cn)
+        return self.parent
+
+    def all_done(self):
+        return bool(self.done.all())
+
+    def readout(self):
+        n_c, len_c, seq_c, sc_c = self.fin_n.cpu(), self.fin_len.cpu(), self.fin_seq.cpu(), self.fin_sc.cpu()
+        out = []
+        for u in range(self.U):
+            hyps = []
+            for i in range(int(n_c[u])):
+                l = int(len_c[u, i])
+                hyps.append(Hypothesis(i, seq_c[u, i, :l].tolist(), sc_c[u, i, :l].tolist()))
+            out.append(hyps)
+        return out[0] if self.U == 1 else out

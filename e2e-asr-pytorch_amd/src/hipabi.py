@@ -47,6 +47,16 @@ class BeamStep(ctypes.Structure):
                 + [(n, _f) for n in ('ctc_weight', 'lm_weight', 'eos_threshold')])
 
 
+ATT_DOT, ATT_LOC = 0, 1
+BEAM_ATTEND_MAX_ROWS, BEAM_ATTEND_MAX_T = 16, 8192
+
+
+class BeamAttend(ctypes.Structure):
+    _fields_ = ([(n, _vp) for n in ('key', 'value', 'q', 'loc', 'wg', 'bg', 'enc_len', 'attn')] + [('attn_ld', _l), ('ctx', _vp)]
+                + [(n, _l) for n in ('ctx_ld', 'ld_k', 'ld_v', 'ld_l')]
+                + [(n, _i) for n in ('U', 'rows_per_utt', 'NH', 'NHv', 'Tp', 'A', 'Dv', 'mode', 'kv_bf16')] + [('temperature', _f)])
+
+
 _P = ctypes.POINTER
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
@@ -122,6 +132,7 @@ SIGNATURES = {
     'asr_beam_candidates': [_vp, _vp, _i, _i, _i, _vp],
     'asr_sample_tokens': [_vp, _l, _vp, _l, _i, _i, _u64, _vp],
     'asr_beam_step': [ctypes.POINTER(BeamStep), _vp],
+    'asr_beam_attend': [ctypes.POINTER(BeamAttend), _vp],
     'asr_ctc_prefix_init_batched': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'asr_ctc_prefix_score_batched': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'asr_gemm16': [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -157,6 +168,7 @@ _RESTYPES = {
     'asr_att_decoder_bwd_persistent_tiles': (ctypes.c_int, [_P(DecDims)]),
     'asr_att_decoder_fwd_plan': (ctypes.c_int, [_P(DecDims)]),
     'asr_att_decoder_bwd_plan': (ctypes.c_int, [_P(DecDims)]),
+    'asr_beam_attend_resident_max_t': (ctypes.c_int, [_i]),
 }
 
 

@@ -513,6 +513,39 @@ int asr_ctc_prefix_score_batched(const float* logp, const int* tlen, const float
                                  const int* prefix_len, const int* last_token, float* psi, float* r_out,
                                  int N, int C, int Tmax, int V, int rows_per_utt, asr_stream_t stream);
 
+/* Beam-search attention of the model variants (csrc/decode_variants.hip; src/decode_variants.py): one output position of
+ * BeamDecoder.forward's attention (src/decode.py:107-110 -> src/asr.py:331-364, ScaleDotAttention / LocationAwareAttention
+ * src/module.py:1121-1189) for U utterances x rows_per_utt hypothesis rows (row r belongs to utterance u = r / rows_per_utt),
+ * forward only.  Keys and values are held once per utterance, not per row.  Per row r and head n:
+ *   dot: e[t] = q[r,n,:] . key[u,n,t,:]
+ *   loc: e[t] = wg . tanh(key[u,n,t,:] + q[r,n,:] + loc[r,t,:]) + bg[0]     (loc = tanh(loc_proj(loc_conv(prev_att))), shared by heads)
+ *   attn[r, n*Tp + t] = softmax_t(e / temperature) over t < enc_len[u], exactly 0 for t >= enc_len[u] (row stride attn_ld);
+ *   ctx[r*ctx_ld + n*Dv + c] = sum_t attn[r,n,t] value[u, NHv == 1 ? 0 : n, t, c].
+ * key (U,NH,Tp,ld_k) and value (U,NHv,Tp,ld_v) are fp32 or, kv_bf16 = 1, bf16; q (R,NH,A), loc (R,Tp,ld_l), wg (A), bg (1),
+ * attn and ctx are fp32.  Contiguous row strides that are a multiple of 16 bytes get 16-byte loads.  rows_per_utt <=
+ * ASR_BEAM_ATTEND_MAX_ROWS and Tp <= ASR_BEAM_ATTEND_MAX_T, else ASR_E_UNSUPPORTED.  The energies stay in LDS while
+ * rows_per_utt * Tp <= asr_beam_attend_resident_max_t(1) and are staged in the attn rows above that.  No reference
+ * counterpart as one call: the reference runs its attention once per hypothesis. */
+#define ASR_ATT_DOT 0
+#define ASR_ATT_LOC 1
+#define ASR_BEAM_ATTEND_MAX_ROWS 16
+#define ASR_BEAM_ATTEND_MAX_T 8192
+typedef struct {
+    const void* key; const void* value;     /* (U,NH,Tp,ld_k), (U,NHv,Tp,ld_v): fp32 or bf16 (kv_bf16) */
+    const float* q;                         /* (R,NH,A) */
+    const float* loc;                       /* (R,Tp,ld_l) or NULL (dot) */
+    const float* wg; const float* bg;       /* (A), (1) or NULL (dot) */
+    const int64_t* enc_len;                 /* (U) */
+    float* attn; long attn_ld;              /* (R, attn_ld >= NH*Tp) */
+    float* ctx; long ctx_ld;                /* (R, ctx_ld >= NH*Dv) */
+    long ld_k, ld_v, ld_l;
+    int U, rows_per_utt, NH, NHv, Tp, A, Dv, mode, kv_bf16;
+    float temperature;
+} asr_beam_attend_t;
+int asr_beam_attend(const asr_beam_attend_t* args, asr_stream_t stream);
+/* largest Tp whose energies stay in LDS for `rows_per_utt` rows */
+int asr_beam_attend_resident_max_t(int rows_per_utt);
+
 /* Test support: keeps `workgroups` compute units busy (one 64-thread workgroup each holding `lds_bytes` of LDS) for
  * `seconds` (<= 20) on `stream`; tests/test_persist_abort.py uses it to starve a persistent launch of co-residency. */
 int asr_debug_occupy(int workgroups, int lds_bytes, double seconds, asr_stream_t stream);
