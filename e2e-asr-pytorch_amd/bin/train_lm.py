@@ -1,6 +1,7 @@
 """RNN language-model training Solver (reference bin/train_lm.py:10-123): `fetch_data` (prepend <sos> = 0, lengths), `load_data`,
 `set_model`, `exec`, `validate`.  Every tensor op of the step runs in libasr_hip.so: embedding gather / gradient, dropout,
-the LSTM stack through the encoder's recurrence kernels, the output projection, cross entropy, clip + Adam."""
+the LSTM stack through the encoder's recurrence kernels or the GRU stack through gru_rec.hip, the output projection, cross entropy,
+clip + Adam."""
 import torch
 
 from src import hipabi as H

@@ -203,7 +203,7 @@ class BeamDecoder(nn.Module):
                     cur[i] = (1 - self.ctc_w) * cur[i] + self.ctc_w * hack
                     cur[i, 0] = LOG_ZERO
             if self.apply_lm:
-                lm_lp, lm_new = self.lm.step(toks.to(dev), (lm_state[0][:, :n].contiguous(), lm_state[1][:, :n].contiguous()))
+                lm_lp, lm_new = self.lm.step(toks.to(dev), self.lm.state_rows(lm_state, n))
                 cur += self.lm_w * lm_lp.cpu()
             children = []
             for i, h in enumerate(hyps):
@@ -228,8 +228,7 @@ class BeamDecoder(nn.Module):
                 ci = torch.tensor([h.ctc_idx for h in hyps], dtype=torch.int64, device=dev)
                 ctc_r[:m] = r_new[par, ci]
             if self.apply_lm:
-                lm_state[0][:, :m] = lm_new[0][:, par]
-                lm_state[1][:, :m] = lm_new[1][:, par]
+                lm_state = self.lm.gather_state(lm_new, par)
         finals += hyps
         finals.sort(key=lambda o: o.avgScore(), reverse=True)
         return finals[:self.beam_size]
@@ -338,12 +337,7 @@ class _BeamBook(object):
         if bd.apply_ctc:
             H.call('asr_gather_rows', H.ptr(self.ctc_rn), H.ptr(self.ctc_index), H.ptr(self.ctc_r), R, Tp * 2, Tp * 2, Tp * 2, R * C, st)
         if bd.apply_lm:
-            lm, dim = bd.lm, bd.lm.dim
-            hn, cn = torch.empty_like(lm_new[0]), torch.empty_like(lm_new[1])
-            for l in range(lm.n_layers):
-                H.call('asr_gather_rows', H.ptr(lm_new[0][l]), H.ptr(self.parent), H.ptr(hn[l]), R, dim, dim, dim, R, st)
-                H.call('asr_gather_rows', H.ptr(lm_new[1][l]), H.ptr(self.parent), H.ptr(cn[l]), R, dim, dim, dim, R, st)
-            self.lm_state = (hn, cn)
+            self.lm_state = bd.lm.gather_state(lm_new, self.parent)
         return self.parent
 
     def all_done(self):

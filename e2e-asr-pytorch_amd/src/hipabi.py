@@ -121,6 +121,8 @@ SIGNATURES = {
     'asr_gru_cell_bwd': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     'asr_gru_fwd': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     'asr_gru_bwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    'asr_gru_rec_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    'asr_gru_rec_bwd': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_sumsq': [_vp, _l, _vp, _vp],
     'asr_scale': [_vp, _l, _f, _vp],
     'asr_scale_dev': [_vp, _vp, _l, _vp, _vp],
@@ -155,6 +157,7 @@ _RESTYPES = {
     'asr_device_arch': (ctypes.c_char_p, []),
     'asr_version': (ctypes.c_int, []),
     'asr_lstm_workspace_bytes': (_sz, [_i, _i, _i]),
+    'asr_gru_rec_workspace_bytes': (_sz, [_i, _i]),
     'asr_specaug_workspace_bytes': (_sz, [_i]),
     'asr_lstm_set_persistent': (ctypes.c_int, [_i]),
     'asr_lstm_plan': (ctypes.c_int, [_i, _i, _i, _i, _i]),

@@ -451,6 +451,25 @@ int asr_gru_bwd(const float* dy, const float* y, const float* saved, const float
                 float* dgi, float* dgh, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Single-direction nn.GRU recurrence of the RNN language model (module 'GRU', reference src/lm.py:18; gate order r,z,n),
+ * one launch per time step with MFMA in `prec` (bf16 operands / fp32 accumulate, or fp32).  Any 1 <= H <= 2048; a larger H
+ * returns ASR_E_UNSUPPORTED.
+ *   asr_gru_rec_fwd : gi (B,T,3H) = x W_ih^T + b_ih (asr_gemm); whh (3H,H) = weight_hh as stored; bhh (3H); h0 (B,H) the
+ *                     initial state or NULL for zeros (must not alias y).  Writes y (B,T,H) and, unless NULL,
+ *                     saved (B,T,4H) = r | z | n | gh_n (gh_n = (h_{t-1} W_hh^T + b_hh)_n, the layout of asr_gru_cell_fwd).
+ *                     T = 1 with h0 = the previous state and saved = NULL is one decode step.
+ *   asr_gru_rec_bwd : dy (B,T,H), y / saved / h0 as given to and written by the forward; whh (3H,H).  Writes dgi, dgh
+ *                     (B,T,3H) (gradients wrt gi and gh = h_{t-1} W_hh^T + b_hh) and, unless NULL, dh0 (B,H).  The caller
+ *                     forms dW_ih, db_ih, dx, dW_hh (asr_gemm with seqT / bshift) and db_hh from them.  workspace: 16-byte
+ *                     aligned, asr_gru_rec_workspace_bytes(B, H) bytes (transposed W_hh and the carried gradient).
+ */
+size_t asr_gru_rec_workspace_bytes(int B, int H);
+int asr_gru_rec_fwd(const float* gi, const float* whh, const float* bhh, const float* h0, int B, int T, int H, int prec,
+                    float* y, float* saved, asr_stream_t stream);
+int asr_gru_rec_bwd(const float* dy, const float* y, const float* saved, const float* h0, const float* whh, int B, int T, int H,
+                    int prec, float* dgi, float* dgh, float* dh0, void* workspace, size_t workspace_bytes, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Beam-search inference (BeamDecoder.forward src/decode.py:65-183), batched over live hypotheses.
  *   asr_att_decoder_keys : key = tanh(proj_k(enc)) once per utterance (src/asr.py:345).
  *   asr_att_decoder_step : ONE decode step t for all dims->B rows of `state` (each row = one hypothesis at step t):

@@ -2,8 +2,9 @@
 RNN-LM of config/librispeech_lm.yaml (4 x LSTM-1024, tied, random weights) with weight 0.3, utterances of T frames decoded
 U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Prints one JSON line.
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
-       [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU]
-The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one."""
+       [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
+The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one; --lm-module GRU
+fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'e2e-asr-pytorch_amd')
@@ -19,6 +20,7 @@ ap.add_argument('--max-len-ratio', type=float, default=0.05); ap.add_argument('-
 ap.add_argument('--beam', type=int, default=8); ap.add_argument('--host', action='store_true'); ap.add_argument('--prec', default='bf16')
 ap.add_argument('--model-yaml', default=os.path.join(PKG, 'config', 'librispeech_asr.yaml'))
 ap.add_argument('--attention-mode'); ap.add_argument('--num-head', type=int); ap.add_argument('--decoder-module')
+ap.add_argument('--lm-module', choices=('LSTM', 'GRU'), default='LSTM')
 a = ap.parse_args()
 torch.manual_seed(0)
 mc = yaml.safe_load(open(a.model_yaml))['model']
@@ -27,6 +29,7 @@ if a.num_head: mc['attention']['num_head'] = a.num_head
 if a.decoder_module: mc['decoder']['module'] = a.decoder_module
 model = ASR(160, 31, 1, prec=a.prec, **mc).cuda().eval()
 lmc = yaml.safe_load(open(os.path.join(PKG, 'config', 'librispeech_lm.yaml')))['model']
+lmc['module'] = a.lm_module
 lm = RNNLM(31, **lmc).cuda().eval()
 dec = BeamDecoder(model, None, beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio, ctc_weight=0.3)
 dec.set_lm(lm, 0.3)
@@ -48,7 +51,7 @@ H.raise_if_aborted()
 n_hyp = len(out[0]) if (U > 1 or a.host) else len(out)
 print(json.dumps({'metric': 'beam-search decode, config 4', 'utterances_per_s': U / dt, 'ms_per_utterance': dt * 1e3 / U,
                   'decode_positions_per_s': U * steps / dt, 'batch_utterances': U, 'frames': T, 'max_positions': steps, 'beam': a.beam,
-                  'ctc_weight': 0.3, 'lm': '4x1024 tied (33.6 M)', 'lm_weight': 0.3, 'path': 'host score table' if a.host else 'device beam step',
+                  'ctc_weight': 0.3, 'lm': '4x1024 tied, %s' % a.lm_module, 'lm_weight': 0.3, 'path': 'host score table' if a.host else 'device beam step',
                   'hyps_first_utt': n_hyp, 'prec': a.prec, 'decoder_path': 'fast' if dec.fast else 'variant',
                   'attention': '%s x%d' % (mc['attention']['mode'], mc['attention']['num_head']), 'decoder': mc['decoder']['module'],
                   'reference_cpu_note': 'BASELINE.md: ~1.0 s per T=400 utterance, reference on 8 CPU cores'}))
