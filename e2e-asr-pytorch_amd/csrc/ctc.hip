@@ -45,7 +45,8 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
     return m + __logf(1.f + __expf(md - m) + __expf(mn - m));
 }
 
-constexpr int CTC_FCH = 8;        // frames per workgroup of the gradient kernel
+constexpr int CTC_FCH = 8;        // frames per workgroup of the gradient kernel (halved until the class sums fit in LDS)
+constexpr size_t CTC_GRAD_LDS = 60 * 1024;   // dynamic LDS budget of the gradient kernel, the sweep's (64 KiB is what a launch gets at most)
 
 __global__ __launch_bounds__(1024) void ctc_sweep_kernel(CtcP p, int CF) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -121,11 +122,12 @@ __global__ __launch_bounds__(1024) void ctc_sweep_kernel(CtcP p, int CF) {
     }
 }
 
-// gradient of CTC_FCH frames of one utterance: one thread per state, class sums through LDS (labels by atomics with the
+// gradient of FCH frames of one utterance: one thread per state, class sums through LDS (labels by atomics with the
 // multiplicity of the label in the target as contention, blank by a wave reduction)
+template <int FCH>
 __global__ __launch_bounds__(1024) void ctc_grad_kernel(CtcP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int b = blockIdx.y, t0 = blockIdx.x * CTC_FCH;
+    const int b = blockIdx.y, t0 = blockIdx.x * FCH;
     const int tid = threadIdx.x, NTH = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = NTH >> 6;
     const int V = p.V, T = p.T;
     int tl = (int)p.tgt_len[b];
@@ -134,10 +136,10 @@ __global__ __launch_bounds__(1024) void ctc_grad_kernel(CtcP p) {
     int Tin = (int)p.in_len[b];
     Tin = max(0, min(Tin, T));
     float* acc = reinterpret_cast<float*>(smem);          // [FCH][V]
-    float* blk = acc + CTC_FCH * V;                       // [FCH][nwave] blank partial sums
+    float* blk = acc + FCH * V;                       // [FCH][nwave] blank partial sums
     const float* lp = p.lp + (long)b * T * V;
     float* grad = p.grad + (long)b * T * V;
-    for (int i = tid; i < CTC_FCH * V; i += NTH) acc[i] = 0.f;
+    for (int i = tid; i < FCH * V; i += NTH) acc[i] = 0.f;
     const int s = tid;
     const bool sok = s < S;
     const int e = (sok && (s & 1)) ? (int)p.tgt[(long)b * p.L + (s >> 1)] : 0;
@@ -154,9 +156,9 @@ __global__ __launch_bounds__(1024) void ctc_grad_kernel(CtcP p) {
         }
         *p.loss = sum;
     }
-    float occ[CTC_FCH];
+    float occ[FCH];
 #pragma unroll
-    for (int f = 0; f < CTC_FCH; ++f) {
+    for (int f = 0; f < FCH; ++f) {
         const int t = t0 + f;
         occ[f] = 0.f;
         if (sok && t < Tin) {
@@ -167,19 +169,22 @@ __global__ __launch_bounds__(1024) void ctc_grad_kernel(CtcP p) {
     }
     __syncthreads();
 #pragma unroll
-    for (int f = 0; f < CTC_FCH; ++f) {
+    for (int f = 0; f < FCH; ++f) {
         if (sok && (s & 1) && t0 + f < Tin) atomicAdd(&acc[f * V + e], occ[f]);
         const float bsum = wave_sum((sok && !(s & 1)) ? occ[f] : 0.f);
         if (lane == 0) blk[f * nwave + wave] = bsum;
     }
     __syncthreads();
-    for (int i = tid; i < CTC_FCH * V; i += NTH) {
+    for (int i = tid; i < FCH * V; i += NTH) {
         const int f = i / V, v = i - f * V, t = t0 + f;
         if (t >= T) continue;
         float g = 0.f;
         if (t < Tin) {
             float a = acc[i];
             if (v == 0) for (int w = 0; w < nwave; ++w) a += blk[f * nwave + w];
+            // a class without a lattice state has posterior exp(-inf + nll): NaN for an infeasible alignment like every
+            // other class of the row (torch), not the plain softmax term
+            if (!(nll < INFINITY)) a = NAN;
             g = scale * (expf(lp[(long)t * V + v]) - a);
         }
         grad[(long)t * V + v] = g;
@@ -206,13 +211,26 @@ extern "C" int asr_ctc_loss(const float* logp, const int64_t* targets, const int
     // frames of log-probs staged per chunk: as many as fit beside the lattice buffers in 60 KB
     const size_t fixed = (size_t)(Smax + 2) * 4 + 2 * (size_t)(Smax + 6) * 4 + 16;
     int CF = (int)((60 * 1024 - fixed) / ((size_t)V * 4));
-    ASR_REQUIRE(CF >= 1, ASR_E_UNSUPPORTED, "asr_ctc_loss: 2L+1=%d states and V=%d classes exceed the LDS budget", Smax, V);
+    ASR_REQUIRE(CF >= 1, ASR_E_UNSUPPORTED, "asr_ctc_loss: V=%d classes exceed the LDS budget: at most V=%d with 2L+1=%d states "
+                "(one frame of log-probs beside the lattice buffers in 60 KB)", V, (int)((60 * 1024 - fixed) / 4), Smax);
     if (CF > T) CF = T;
     const size_t lds_s = fixed + (size_t)CF * V * 4;
-    const size_t lds_g = (size_t)CTC_FCH * (V + nthr / 64) * 4;
+    // gradient kernel: CTC_FCH frames of class sums per workgroup, fewer for a vocabulary whose sums would pass the launch limit
+    // (V > ~1900; one frame always fits: it is smaller than the sweep's one staged frame + lattice buffers)
+    const size_t lds_g1 = (size_t)(V + nthr / 64) * 4;
+    ASR_REQUIRE(lds_g1 <= CTC_GRAD_LDS, ASR_E_UNSUPPORTED, "asr_ctc_loss: V=%d classes exceed the %zu bytes of LDS of the gradient kernel",
+                V, CTC_GRAD_LDS);
+    int fch = CTC_FCH;
+    while ((size_t)fch * lds_g1 > CTC_GRAD_LDS) fch >>= 1;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ctc_sweep_kernel, dim3(B, 2), dim3(nthr), lds_s, st, p, CF);
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3(cdiv(T, CTC_FCH), B), dim3(nthr), lds_g, st, p);
+    const dim3 gg(cdiv(T, fch), B);
+    switch (fch) {
+        case 8: hipLaunchKernelGGL(ctc_grad_kernel<8>, gg, dim3(nthr), 8 * lds_g1, st, p); break;
+        case 4: hipLaunchKernelGGL(ctc_grad_kernel<4>, gg, dim3(nthr), 4 * lds_g1, st, p); break;
+        case 2: hipLaunchKernelGGL(ctc_grad_kernel<2>, gg, dim3(nthr), 2 * lds_g1, st, p); break;
+        default: hipLaunchKernelGGL(ctc_grad_kernel<1>, gg, dim3(nthr), lds_g1, st, p); break;
+    }
     ASR_LAUNCH_CHECK("asr_ctc_loss");
     return ASR_OK;
 }

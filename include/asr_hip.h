@@ -183,7 +183,8 @@ int asr_layernorm_bwd(const float* dy, const float* x, const float* w, const flo
  *   (exp(logp) - posterior), exactly 0 for t >= input_len; +inf / NaN for infeasible alignments.
  * workspace: asr_ctc_loss_workspace_bytes(B,T,L) (alpha lattice).
  * Limit: 2*L+1 <= 1024 lattice states (L = padded target width <= 511 tokens), one state per thread of a workgroup;
- * longer targets return ASR_E_UNSUPPORTED.
+ * longer targets return ASR_E_UNSUPPORTED; so does a vocabulary of which one frame of log-probs does not fit beside the lattice
+ * buffers in 60 KB of LDS (V <= 15342 - 3 * (2L+1): about 15 300 classes for short targets, 12 273 at L = 511).
  */
 size_t asr_ctc_loss_workspace_bytes(int B, int T, int L);
 int asr_ctc_loss(const float* logp, const int64_t* targets, const int64_t* input_len, const int64_t* target_len,

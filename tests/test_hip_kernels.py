@@ -211,6 +211,11 @@ def test_clip_and_adadelta_step():
     Hh.call('asr_adadelta_step', Hh.ptr(pd), Hh.ptr(gd), Hh.ptr(sq), Hh.ptr(ad), n, 1.0, 0.9, 1e-8, 0.0, 5.0, Hh.ptr(nsq), 1.0,
             None, Hh.stream_ptr())
     assert torch.equal(before, pd)
+    # so is an infinite one
+    nsq.fill_(float('inf'))
+    Hh.call('asr_adadelta_step', Hh.ptr(pd), Hh.ptr(gd), Hh.ptr(sq), Hh.ptr(ad), n, 1.0, 0.9, 1e-8, 0.0, 5.0, Hh.ptr(nsq), 1.0,
+            None, Hh.stream_ptr())
+    assert torch.equal(before, pd)
     # a set status word (a persistent launch of the step gave up, asr_status_collect): the update is refused as well
     Hh.call('asr_sumsq', Hh.ptr(gd), n, Hh.ptr(nsq), Hh.stream_ptr())
     status = torch.zeros(1, dtype=torch.int32, device='cuda')
