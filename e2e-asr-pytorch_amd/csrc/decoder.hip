@@ -11,6 +11,7 @@
 // Step kernels are bandwidth/latency bound: key (B,T',A) and enc (B,T',E) are re-read every step and
 // stay resident in the 256 MB Infinity Cache between steps; one launch covers the whole batch.
 #include "common.h"
+#include "decoder_internal.h"
 #include <stdlib.h>
 
 namespace {
@@ -1120,11 +1121,6 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
     if (grp == 0 && k < Dd) demb[(long)v * Dd + k] += red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
 }
 
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t dec_bwd_persist_work_bytes_fw(const asr_dec_dims_t& d);
-int dec_bwd_persist_tiles_fw(const asr_dec_dims_t& d);
-int dec_bwd_persist_tiles_max_fw(const asr_dec_dims_t& d);
 struct BwdLayout {
     size_t dhs, dxin, dq, dkey, datt_next, dcf, wq_t, slots, wslots, dkeypre, wcat[ASR_MAX_DEC_LAYERS], pwork, pwork_bytes, total;
     int ntp, ntp_max;       // tiles per utterance of the persistent backward under the current plan preference (0: no plan) / the larger of its two plans
@@ -1137,7 +1133,7 @@ struct BwdLayout {
 BwdLayout bwd_layout(const asr_dec_dims_t& d) {
     BwdLayout o;
     size_t off = 0;
-    auto take = [&](size_t nfloat) { size_t r = off; off += align_up(nfloat * sizeof(float)); return r; };
+    auto take = [&](size_t nfloat) { size_t r = off; off += align_up256(nfloat * sizeof(float)); return r; };
     const int XW = d.Dd + d.E;
     const int taps = 2 * d.Ks + 1;
     // energy backward: NG frame groups x ceil(A/64) waves (<= 640 threads); the smallest tile that keeps the batch in
@@ -1179,10 +1175,11 @@ BwdLayout bwd_layout(const asr_dec_dims_t& d) {
     o.dhs = take((size_t)d.B * d.L * d.NL * d.Dd);
     o.dq = take((size_t)d.B * d.L * d.A);
     o.dkey = take((size_t)d.B * d.Tp * d.A);
-    o.ntp = dec_bwd_persist_tiles_fw(d);
-    o.ntp_max = dec_bwd_persist_tiles_max_fw(d);
+    const DecPlanInfo pi = dec_bwd_plan_info(d);
+    o.ntp = pi.tiles;
+    o.ntp_max = pi.tiles_max;
     o.slots = take((size_t)d.B * (o.nte > o.ntp_max ? o.nte : o.ntp_max) * o.slot);
-    o.pwork_bytes = dec_bwd_persist_work_bytes_fw(d);
+    o.pwork_bytes = pi.work_bytes;
     o.pwork = take(o.pwork_bytes / sizeof(float) + 64);
     o.dxin = take((size_t)d.B * d.L * XW);
     o.dkeypre = take((size_t)d.B * d.Tp * d.A);
@@ -1244,28 +1241,11 @@ void launch_energy(const DecP& p, int t, const EnergyPlan& pl, hipStream_t st) {
 
 }  // namespace
 
-// decoder_persist.hip
-size_t dec_fwd_persist_work_bytes(const asr_dec_dims_t& d);
-int dec_fwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const float* enc,
-                       const int64_t* enc_len, void* work, size_t work_bytes, hipStream_t st);
-
-size_t dec_bwd_persist_work_bytes(const asr_dec_dims_t& d);
-int dec_bwd_persist_tiles(const asr_dec_dims_t& d);
-int dec_bwd_persist_tiles_max(const asr_dec_dims_t& d);
-int dec_bwd_plan_kind(const asr_dec_dims_t& d);
-namespace { size_t dec_bwd_persist_work_bytes_fw(const asr_dec_dims_t& d) { return dec_bwd_persist_work_bytes(d); }
-            int dec_bwd_persist_tiles_fw(const asr_dec_dims_t& d) { return dec_bwd_persist_tiles(d); }
-            int dec_bwd_persist_tiles_max_fw(const asr_dec_dims_t& d) { return dec_bwd_persist_tiles_max(d); } }
-int dec_bwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const int64_t* enc_len,
-                       const float* dhs, float* dxin, float* dq, float* dkey, float* slots, int slot, const float* wcatT, const float* wqT,
-                       void* work, size_t work_bytes, float** dgates_out, hipStream_t st);
-
-int dec_fwd_plan_kind(const asr_dec_dims_t& d);
 extern "C" size_t asr_att_decoder_fwd_work_bytes(const asr_dec_dims_t* dims) {
-    return dims ? dec_fwd_persist_work_bytes(*dims) : 0;
+    return dims ? dec_fwd_plan_info(*dims).work_bytes : 0;
 }
-extern "C" int asr_att_decoder_fwd_plan(const asr_dec_dims_t* dims) { return dims ? dec_fwd_plan_kind(*dims) : 0; }
-extern "C" int asr_att_decoder_bwd_plan(const asr_dec_dims_t* dims) { return dims ? dec_bwd_plan_kind(*dims) : 0; }
+extern "C" int asr_att_decoder_fwd_plan(const asr_dec_dims_t* dims) { return dims ? dec_fwd_plan_info(*dims).kind : 0; }
+extern "C" int asr_att_decoder_bwd_plan(const asr_dec_dims_t* dims) { return dims ? dec_bwd_plan_info(*dims).kind : 0; }
 
 extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights,
                                    const float* enc, const int64_t* enc_len, const int64_t* teacher, int teacher_ld,
@@ -1377,7 +1357,8 @@ extern "C" int asr_att_decoder_step(const asr_dec_dims_t* dims, const asr_dec_we
     return ASR_OK;
 }
 
-// offset of the persistent backward's status block inside the workspace (diagnostics: tools/diag_dec.py)
+// offset of the persistent backward's status block inside the workspace: it opens the launch's work area (decoder_plan.h::bwd_work;
+// diagnostics: tools/diag_dec.py)
 extern "C" size_t asr_att_decoder_bwd_status_offset(const asr_dec_dims_t* dims) {
     if (!dims) return 0;
     return bwd_layout(*dims).pwork;
@@ -1407,9 +1388,6 @@ static int wgrad_slices(int out_rows, int out_cols, int depth) {
 extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
                                           const float* enc, const int64_t* enc_len, const asr_dec_state_t* state, const float* dlogits,
                                           void* workspace, size_t workspace_bytes, int looped, int prec, asr_stream_t stream);
-// pointer to the gate gradients the persistent backward leaves in its work area (decoder_persist.hip)
-float* dec_bwd_persist_dgates(const asr_dec_dims_t& d, void* work);
-
 extern "C" int asr_att_decoder_bwd_ex(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
                                       const float* enc, const int64_t* enc_len, const asr_dec_state_t* state,
                                       const float* dlogits, float* denc,
@@ -1573,7 +1551,7 @@ extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_
     p.slots = (float*)(ws + lay.slots); p.nte = lay.nte; p.slot = lay.slot;
     float* wslots = (float*)(ws + lay.wslots);
     float* dkeypre = (float*)(ws + lay.dkeypre);
-    const float* pdg = looped ? dec_bwd_persist_dgates(d, ws + lay.pwork) : nullptr;
+    const float* pdg = looped ? dec_bwd_dgates(d, ws + lay.pwork) : nullptr;
     const int nslots_used = d.B * (looped ? lay.ntp : lay.nte);
     // output layer: dW_c += dlogits^T h_top ; db_c += colsum(dlogits)
     rc = asr_gemm(dlogits, state->hs + (size_t)(d.NL - 1) * d.Dd, grads->Wc, nullptr, d.V, d.Dd, BL, d.V, SW, d.Dd, 0, 0,

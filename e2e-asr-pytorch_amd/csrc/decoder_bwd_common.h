@@ -80,6 +80,43 @@ __host__ __device__ inline BCarve bwd_carve(int TE, int KP, int A, int E, int Kn
     return c;
 }
 
+// LDS carve of dec_bwd_stream (decoder_stream.hip), shared by kernel and host plan
+struct SBCarve { int AP, DW, PADL, WT, parts, dl, wp16, dg16, cvx, cvT, shorts; int wc, crec, qst, nrec, dcp, de, out, hq, pt, dcx, dq, floats; };
+__host__ __device__ inline SBCarve sbwd_carve(int TEB, int A, int E, int Kn, int Ks, int NT, int UPW, int CPW, int CG2, int QG2, int NG2) {
+    SBCarve c;
+    const int nct = 64 * ((A + 63) / 64);
+    int ap8 = 8 * ((A + 63) / 64); if ((ap8 & 1) == 0) ++ap8;
+    c.AP = 8 * ap8;
+    c.PADL = Ks + 8 + ((4 - ((2 * Ks) & 3)) & 3);       // PADL + Ks is a multiple of 4
+    c.DW = (c.PADL + TEB + Ks + 8 + 3) & ~3;            // zero-padded dconv window of the tile: frames tau0 - PADL ..
+    if (((c.DW >> 2) & 1) == 0) c.DW += 4;
+    c.WT = (2 * Ks + 1 + 3) & ~3;
+    const int nitem = Kn * (TEB >> 4);                   // (kernel, 16-frame group) items of the transposed convolution
+    c.parts = nct / nitem; if (c.parts > 4) c.parts = 4; if (c.parts < 1) c.parts = 1;
+    int o = 0;
+    c.dl = o; o += 16 * SW_MT * c.AP;
+    c.wp16 = o; o += 16 * c.AP;
+    c.dg16 = o; o += 64 * KCHB * 4;
+    c.cvx = o; o += 16 * SW_MT * CVX_LD;
+    c.cvT = o; o += 16 * CVT_LD;
+    c.shorts = (o + 7) & ~7;
+    o = 0;
+    c.wc = o; o += Kn * c.WT;
+    c.crec = o; o += NT * CG2 * 2;
+    c.qst = o; o += NT * QG2 * 2;
+    c.nrec = o; o += NT * NG2 * 2 + 8;
+    c.dcp = o; o += Kn * c.DW;
+    c.de = o; o += 16 * SW_MT * ((TEB + 16 * SW_MT - 1) / (16 * SW_MT)) + 8;
+    const int nout = CPW + UPW;
+    c.out = o; o += (nout > RPWB * 8 ? ((nout + 3) & ~3) : RPWB * 8);
+    c.hq = o; o += (UPW > 64 ? ((UPW + 3) & ~3) : 64);
+    c.pt = o; o += c.parts * Kn * TEB;
+    c.dcx = o; o += (E + 3) & ~3;
+    c.dq = o; o += (A + 3) & ~3;
+    c.floats = o;
+    return c;
+}
+
 __device__ __forceinline__ void cbar(unsigned* cnt, unsigned& gen, int nw) {
     gen += nw;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "handoff.h"
+#include "decoder_internal.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -73,7 +74,6 @@ __device__ __forceinline__ void dp_jitter(unsigned k, unsigned step, unsigned ep
 #define DP_DUMP
 #endif
 constexpr int RB = 5;                   // gate rows per batch of the cell contraction
-inline size_t align_up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ float bf2f_(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
 __device__ __forceinline__ float tanh_f(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
@@ -124,7 +124,7 @@ struct PD {
     int HG2, QG2, SG2;              // granules per producer record (even)
     int KC, KCP;                    // E + Dd, padded to a multiple of 8
     int allow_local;
-    unsigned epoch;                 // launch counter (tag bits)
+    unsigned epoch;                 // unused (the epoch lives in the status block, EPOCH_WORD); kept: it is part of the kernel argument block
 };
 
 // ---- location convolution on the matrix cores -----------------------------------------------------------------------------------
@@ -145,6 +145,35 @@ __host__ __device__ inline ConvGeo conv_geo(int TEB, int Ks) {
     return g;
 }
 __host__ __device__ inline int conv_img_shorts(const ConvGeo& g) { return 8 * g.IMG_LD + 32 * g.WKP; }     // {hi, lo} x 4 copies | {hi, lo} x 16 rows
+
+// LDS carve of dec_fwd_stream (decoder_stream.hip; floats behind the bf16 conv tile), shared by kernel and host plan
+struct FCarve { int cvx_shorts, img, shorts, WT, ATP, NG, x2, q, wg, attp, wc, epart, e, w, g, cpart, stage, stage_floats, floats; };
+__host__ __device__ inline FCarve fwd_carve(int TEB, int NT, int A, int E, int Kn, int Ks, int KCP, int UPW, int SG2) {
+    FCarve c;
+    c.cvx_shorts = TEB * FCVX_LD;
+    c.img = (c.cvx_shorts + 7) & ~7;                          // bf16 images of the convolution (conv_geo)
+    c.shorts = (c.img + conv_img_shorts(conv_geo(TEB, Ks)) + 7) & ~7;
+    c.WT = (2 * Ks + 1 + 3) & ~3;
+    c.ATP = (NT * TEB + 2 * Ks + 8 + 3) & ~3;
+    const int nch = E >> 3;
+    c.NG = (64 * NCW) / nch; if (c.NG > 8) c.NG = 8;          // frame groups of the partial-context pass
+    int o = 0;
+    c.x2 = o; o += 2 * KCP;
+    c.q = o; o += (A + 3) & ~3;
+    c.wg = o; o += (A + 3) & ~3;
+    c.attp = o; o += c.ATP;
+    c.wc = o;                                             // (the fp32 filter rows of dec_fwd_persist live in the bf16 filter image here)
+    c.epart = o; o += NCW * TEB;
+    c.e = o; o += TEB;
+    c.w = o; o += TEB;
+    c.g = o; o += (4 * UPW + 3) & ~3;
+    c.cpart = o; o += c.NG * E;
+    c.stage = o;
+    c.stage_floats = NT * 2 * SG2; if (c.stage_floats < Kn * TEB) c.stage_floats = Kn * TEB;      // doubles as the conv's partial sums
+    o += c.stage_floats;
+    c.floats = o;
+    return c;
+}
 
 // filter image: rows n < Kn hold W_conv[n][0 .. taps) split hi | lo, everything else zero (once per launch)
 __device__ inline void conv_build_wimg(const float* __restrict__ Wconv, int Kn, int taps, const ConvGeo& g, unsigned short* wimg, int tid, int nthr) {

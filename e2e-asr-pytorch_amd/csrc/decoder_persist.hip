@@ -18,10 +18,7 @@
 // Waves 0-7 compute and store, waves 8-11 only poll (their vector-memory queue holds nothing else).  The compute waves
 // synchronise among themselves through an LDS counter where the polling waves are busy; s_barrier is used where
 // the polled data is handed over.
-#include "common.h"
-#include "handoff.h"
-#include <stdlib.h>
-#include <algorithm>
+#include "decoder_plan.h"
 
 static int g_persist_fwd = -1, g_persist_bwd = -1;   // -1: from env ASR_DEC_PERSIST / ASR_DEC_PERSIST_BWD (default on)
 static int g_stream_fwd = -1, g_stream_bwd = -1;     // 1: take the streamed-tile plan (decoder_stream.hip) even where the LDS-resident one exists; -1: env ASR_DEC_STREAM
@@ -32,19 +29,50 @@ extern "C" int asr_att_decoder_set_persistent(int flags) {
     g_persist_fwd = flags & 1; g_persist_bwd = (flags >> 1) & 1; g_stream_fwd = (flags >> 2) & 1; g_stream_bwd = (flags >> 3) & 1;
     return old;
 }
-static void stream_env() {
-    if (g_stream_fwd < 0) { const char* e = getenv("ASR_DEC_STREAM"); g_stream_fwd = (e && e[0] == '1') ? 1 : 0; }
-    if (g_stream_bwd < 0) { const char* e = getenv("ASR_DEC_STREAM"); g_stream_bwd = (e && e[0] == '1') ? 1 : 0; }
+// what asr_att_decoder_set_persistent has not set comes from the environment, on first use
+static void read_switches() {
+    if (g_persist_fwd < 0) g_persist_fwd = env_switch("ASR_DEC_PERSIST", 1);
+    if (g_persist_bwd < 0) g_persist_bwd = env_switch("ASR_DEC_PERSIST_BWD", 1);
+    if (g_stream_fwd < 0) g_stream_fwd = env_switch("ASR_DEC_STREAM", 0);
+    if (g_stream_bwd < 0) g_stream_bwd = env_switch("ASR_DEC_STREAM", 0);
 }
-// decoder_stream.hip
-size_t dec_fwd_stream_work_bytes(const asr_dec_dims_t& d);
-int dec_fwd_streamed(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const float* enc,
-                     const int64_t* enc_len, void* work, size_t work_bytes, hipStream_t st);
+static FwdPlan fwd_plan(const asr_dec_dims_t& d) { read_switches(); return chosen_plan(persist_plan(d), stream_plan_f(d), g_stream_fwd); }
+static BwdPlan bwd_plan(const asr_dec_dims_t& d) { read_switches(); return chosen_plan(persist_plan_b(d), stream_plan_b(d), g_stream_bwd); }
 
-#include "decoder_cluster.h"
-#include "decoder_bwd_common.h"
+DecPlanInfo dec_fwd_plan_info(const asr_dec_dims_t& d) {
+    read_switches();
+    const FwdPlan r = persist_plan(d), s = stream_plan_f(d);
+    return {chosen_plan(r, s, g_stream_fwd).kind, 0, 0, std::max(r.total, s.total)};
+}
+DecPlanInfo dec_bwd_plan_info(const asr_dec_dims_t& d) {
+    read_switches();
+    const BwdPlan r = persist_plan_b(d), s = stream_plan_b(d), pl = chosen_plan(r, s, g_stream_bwd);
+    return {pl.kind, pl.NT, std::max(r.NT, s.NT), std::max(r.total, s.total)};
+}
+float* dec_bwd_dgates(const asr_dec_dims_t& d, void* work) { return bwd_work(d, bwd_plan(d), work).dgates; }
 
 namespace {
+
+// Dynamic LDS of dec_fwd_persist in bytes, for persist_plan.  The kernel keeps its hand-written carve: taking the offsets or the
+// lengths from one shared function, as the other three cluster kernels do, changed its scalar-register spill counts.  Every
+// term sizes the pointer named beside it, in the order of the kernel's "LDS carve" block - change the two together.
+size_t dec_fwd_persist_lds(int TE, int NT, int A, int E, int Ks, int KCP, int UPW, int SG2) {
+    const int EPL = 16 * cdiv(TE, 16);                          // the kernel's EPL = 16 * MT
+    const ConvGeo cg = conv_geo(EPL, Ks);
+    const size_t shorts = (size_t)((TE * A + 7) & ~7)           // s_key
+                        + ((TE * E + 7) & ~7)                   // s_enc
+                        + EPL * FCVX_LD                         // s_cvx
+                        + 8 * cg.IMG_LD                         // s_ximg
+                        + 32 * cg.WKP;                          // s_wimg
+    const size_t floats = (size_t)2 * KCP                       // s_x2
+                        + ((A + 3) & ~3)                        // s_q
+                        + ((A + 3) & ~3)                        // s_wg
+                        + ((NT * TE + 2 * Ks + 8 + 3) & ~3)     // s_attp (ATP)
+                        + NCW * EPL                             // s_epart
+                        + ((4 * UPW + 3) & ~3)                  // s_g
+                        + (size_t)NT * 2 * SG2;                 // s_stage
+    return 2 * shorts + 4 * floats;
+}
 
 template <int KNMAX, int TPW>
 __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
@@ -553,98 +581,53 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
     DP_DUMP
 }
 
-struct PersistPlan { bool ok; int tpw, NT, TE, UPW, QPW, CPW, HG2, QG2, SG2, KC, KCP; size_t lds, status_bytes, xbuf_bytes, wcat_bytes, emb_bytes, total; };
-
-PersistPlan persist_plan(const asr_dec_dims_t& d) {
-    PersistPlan pl{};
-    pl.ok = false;
-    if (d.NL != 1 || d.B > 64 || d.A > 16 * FSW_NU * NCW || d.Kn > 10 || (d.E & 7) != 0 || d.Dd > 20 * 32 || d.Tp < 1) return pl;
+FwdPlan persist_plan(const asr_dec_dims_t& d) {
+    if (d.NL != 1 || d.B > 64 || d.A > 16 * FSW_NU * NCW || d.Kn > 10 || (d.E & 7) != 0 || d.Dd > 20 * 32 || d.Tp < 1) return FwdPlan{};
     const int cpx = cdiv(d.B, 8);                       // clusters per XCD
     const int cand[] = {2, 4, 5, 8};
-    int tpw = 0;
-    for (int i = 0; i < 4; ++i) {
+    FwdPlan pl{};
+    for (int i = 0; i < 4 && !pl.tpw; ++i) {
         const int nt = cdiv(d.Tp, 8 * cand[i]);
-        if (nt <= 30 && cpx * nt <= 32) { tpw = cand[i]; break; }
+        if (nt <= 30 && cpx * nt <= 32) pl.tpw = cand[i];
     }
-    if (!tpw) return pl;
-    pl.tpw = tpw; pl.TE = 8 * tpw; pl.NT = cdiv(d.Tp, pl.TE);
-    pl.UPW = cdiv(d.Dd, pl.NT); pl.QPW = cdiv(d.A, pl.NT); pl.CPW = cdiv(d.E, pl.NT);
-    if (pl.UPW > 64 || cdiv(4 * pl.UPW, NCW) > 60) return pl;
-    auto even = [](int x) { return (x + 1) & ~1; };
-    pl.HG2 = even((pl.UPW + 1) / 2); pl.QG2 = even((pl.QPW + 1) / 2); pl.SG2 = even((pl.TE + 2) / 2 + d.E / 4);      // record: e pairs, (m, s), context as halves
-    pl.KC = d.E + d.Dd; pl.KCP = (pl.KC + 7) & ~7;
-    const int taps = 2 * d.Ks + 1;
-    size_t fl = 0;
-    const int epl = 16 * cdiv(pl.TE, 16);
-    fl += 2 * pl.KCP + 2 * ((d.A + 3) & ~3) + ((pl.NT * pl.TE + 2 * d.Ks + 8 + 3) & ~3) +
-          (size_t)NCW * epl + ((4 * pl.UPW + 3) & ~3) + (size_t)pl.NT * 2 * pl.SG2;
-    pl.lds = 2 * (size_t)(((pl.TE * d.A + 7) & ~7) + ((pl.TE * d.E + 7) & ~7) + epl * FCVX_LD + conv_img_shorts(conv_geo(epl, d.Ks))) + 4 * fl;
+    if (!pl.tpw) return FwdPlan{};
+    pl.kind = 1; pl.TE = 8 * pl.tpw; pl.NT = cdiv(d.Tp, pl.TE);
+    fwd_sizes(d, pl);
+    if (pl.UPW > 64 || cdiv(4 * pl.UPW, NCW) > 60) return FwdPlan{};
+    pl.lds = dec_fwd_persist_lds(pl.TE, pl.NT, d.A, d.E, d.Ks, pl.KCP, pl.UPW, pl.SG2);
     if (getenv("ASR_DEC_PLAN_DEBUG")) fprintf(stderr, "[asr] resident fwd plan B=%d T'=%d: NT=%d TE=%d UPW=%d LDS=%zu\n", d.B, d.Tp, pl.NT, pl.TE, pl.UPW, pl.lds);
-    if (pl.lds > 156 * 1024) return pl;
-    pl.status_bytes = 4096;
-    pl.xbuf_bytes = align_up256(2 * (size_t)d.B * pl.NT * (pl.HG2 + pl.QG2 + pl.SG2) * sizeof(u64));
-    pl.wcat_bytes = align_up256((size_t)4 * d.Dd * pl.KCP * 2);
-    pl.emb_bytes = align_up256((size_t)d.B * d.L * 4 * d.Dd * sizeof(float));
-    pl.total = pl.status_bytes + pl.xbuf_bytes + pl.wcat_bytes + pl.emb_bytes;
-    pl.ok = true;
-    return pl;
+    return pl.lds > 156 * 1024 ? FwdPlan{} : pl;
 }
 
 }  // namespace
 
-// 0: per-step kernels, 1: LDS-resident tiles (this file), 2: streamed tiles (decoder_stream.hip)
-int dec_fwd_plan_kind(const asr_dec_dims_t& d) {
-    stream_env();
-    const PersistPlan pl = persist_plan(d);
-    if (pl.ok && !g_stream_fwd) return 1;
-    return dec_fwd_stream_work_bytes(d) ? 2 : (pl.ok ? 1 : 0);
-}
-size_t dec_fwd_persist_work_bytes(const asr_dec_dims_t& d) {
-    const PersistPlan pl = persist_plan(d);                 // sized for whichever plan may be taken (the preference can be switched)
-    return std::max(pl.ok ? pl.total : (size_t)0, dec_fwd_stream_work_bytes(d));
-}
-
-// Returns ASR_OK when the whole loop was launched, 1 when the configuration has no persistent plan, negative on error.
 int dec_fwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const float* enc,
                        const int64_t* enc_len, void* work, size_t work_bytes, hipStream_t st) {
-    if (g_persist_fwd < 0) { const char* e = getenv("ASR_DEC_PERSIST"); g_persist_fwd = (e && e[0] == '0') ? 0 : 1; }
+    read_switches();
     if (!g_persist_fwd) return 1;
-    if (dec_fwd_plan_kind(d) == 2) return dec_fwd_streamed(d, w, s, enc, enc_len, work, work_bytes, st);
-    const PersistPlan pl = persist_plan(d);
-    if (!pl.ok || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv) return 1;
-    char* base = (char*)work;
-    unsigned* status = (unsigned*)base;
-    u64* xbuf = (u64*)(base + pl.status_bytes);
-    unsigned short* wcat16 = (unsigned short*)(base + pl.status_bytes + pl.xbuf_bytes);
-    float* embproj = (float*)(base + pl.status_bytes + pl.xbuf_bytes + pl.wcat_bytes);
-    clear_work(work, pl.xbuf_bytes, st);
-    hipLaunchKernelGGL(build_wcat16_kernel, dim3(512), dim3(256), 0, st, w.Wih[0], w.Whh[0], wcat16, 4 * d.Dd, d.Dd, d.E, pl.KCP);
+    const FwdPlan pl = fwd_plan(d);
+    if (pl.kind == 2) return dec_fwd_streamed(d, w, s, enc, enc_len, work, work_bytes, st);
+    if (!pl.kind || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv) return 1;
+    const FwdWork wk = fwd_work(d, pl, work);
+    clear_work(work, wk.xbuf_bytes, st);
+    hipLaunchKernelGGL(build_wcat16_kernel, dim3(512), dim3(256), 0, st, w.Wih[0], w.Whh[0], wk.wcat16, 4 * d.Dd, d.Dd, d.E, pl.KCP);
     const int XW = d.Dd + d.E;
-    int rc = asr_gemm(s.xin, w.Wih[0], embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0,
+    int rc = asr_gemm(s.xin, w.Wih[0], wk.embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0,
                       0, 0, ASR_BF16, (asr_stream_t)st);
     if (rc != ASR_OK) return rc;
-    static int allow = -1;
-    if (allow < 0) { const char* e = getenv("ASR_LSTM_XCD_LOCAL"); allow = (e && e[0] == '0') ? 0 : 1; }
-    PD p{d, w, s, enc, enc_len, wcat16, embproj, xbuf, status, pl.NT, pl.TE, pl.UPW, pl.QPW, pl.CPW, pl.HG2, pl.QG2, pl.SG2, pl.KC, pl.KCP, allow};
-    const int cpx = cdiv(d.B, 8);
-    const dim3 grid(8 * cpx * pl.NT), block(64 * (NCW + NPW));
-#define DPF_LAUNCH(KN_, TPW_)                                                                                                   \
-    {                                                                                                                           \
-        static unsigned char attr_[32];                                                                                         \
-        if (first_on_device(attr_)) hipFuncSetAttribute((const void*)dec_fwd_persist<KN_, TPW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048); \
-        if (!grid_resident(dec_fwd_persist<KN_, TPW_>, (int)grid.x, (int)block.x, pl.lds)) return 1;                              \
-        hipLaunchKernelGGL((dec_fwd_persist<KN_, TPW_>), grid, block, pl.lds, st, p);                                             \
-        hipLaunchKernelGGL(bump_epoch_kernel, dim3(1), dim3(1), 0, st, status);                                                   \
-    }
+    const PD p{d, w, s, enc, enc_len, wk.wcat16, wk.embproj, wk.xbuf, wk.status, pl.NT, pl.TE, pl.UPW, pl.QPW, pl.CPW, pl.HG2, pl.QG2, pl.SG2, pl.KC,
+               pl.KCP, xcd_local_allowed()};
+    const ClusterLaunch go{"asr_att_decoder_fwd(persistent)", 160 * 1024 - 2048, cluster_grid(d, pl.NT), dim3(64 * (NCW + NPW)), pl.lds, st};
     if (d.Kn <= 4) {
-        if (pl.tpw == 2) DPF_LAUNCH(4, 2) else if (pl.tpw == 4) DPF_LAUNCH(4, 4) else if (pl.tpw == 5) DPF_LAUNCH(4, 5) else DPF_LAUNCH(4, 8)
-    } else {
-        if (pl.tpw == 2) DPF_LAUNCH(10, 2) else if (pl.tpw == 4) DPF_LAUNCH(10, 4) else if (pl.tpw == 5) DPF_LAUNCH(10, 5) else return 1;
+        if (pl.tpw == 2) return go.run<dec_fwd_persist<4, 2>>(p);
+        if (pl.tpw == 4) return go.run<dec_fwd_persist<4, 4>>(p);
+        if (pl.tpw == 5) return go.run<dec_fwd_persist<4, 5>>(p);
+        return go.run<dec_fwd_persist<4, 8>>(p);
     }
-#undef DPF_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("asr_att_decoder_fwd(persistent): launch failed: %s", hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
+    if (pl.tpw == 2) return go.run<dec_fwd_persist<10, 2>>(p);
+    if (pl.tpw == 4) return go.run<dec_fwd_persist<10, 4>>(p);
+    if (pl.tpw == 5) return go.run<dec_fwd_persist<10, 5>>(p);
+    return 1;
 }
 
 // =================================================================================================
@@ -1102,129 +1085,23 @@ __global__ __launch_bounds__(512) void dec_bwd_persist(PB p) {
     if (dbg != 0.f) atomicAdd(p.slots + ((long)b * NT + j) * p.slot + A * (1 + Kn), dbg);     // slots are zero on entry
 }
 
-struct PersistPlanB { bool ok; int TE, NT, UPW, CPW, R4, CG2, QG2, VG2, NG2; size_t lds, status_bytes, xbuf_bytes, w16_bytes, dg_bytes, total; };
-
-PersistPlanB persist_plan_b(const asr_dec_dims_t& d) {
-    PersistPlanB pl{};
-    pl.ok = false;
-    if (d.NL != 1 || d.B > 64 || d.A > 320 || d.A < 16 || d.Kn > 10 || (d.E & 7) != 0 || (d.A & 1) != 0 || d.Dd > 64 * KCHB || d.L < 1) return pl;
-    const int cpx = cdiv(d.B, 8);
-    const int ncw = cdiv(d.A, 64), nct = 64 * ncw;
-    if (d.Dd > nct || d.E > 2 * nct || d.E > 640 || d.Tp > 4 * nct) return pl;
-    pl.R4 = (4 * d.Dd + 7) & ~7;
-    auto even = [](int x) { return (x + 1) & ~1; };
-    // frames per tile: the smallest multiple of 4 (most tiles, fewest weight rows and sweep frames per workgroup) whose tiles
-    // fit the XCD (32 CUs per XCD, ceil(B/8) clusters each), the register-resident weight rows and the LDS
-    // Second pass (short encoder outputs, e.g. T' = 150 behind a VGG front-end): more workgroups than the frames need.  The
-    // weight rows of the cell and the context columns are spread over ALL tiles of an utterance, so a short utterance can run
-    // out of register rows before it runs out of frames; tiles past T' hold rows only (every frame access of the kernel is
-    // clamped to the utterance and every frame store guarded by T', as for the tiles past a short utterance of a ragged batch).
-    bool found = false;
-    for (int pass = 0; pass < 2 && !found; ++pass)
-    for (int TE = 8; TE <= 40 && !found; TE += 4) {
-        const int nt_frames = cdiv(d.Tp, TE);
-        const int nt_hi = pass == 0 ? nt_frames : std::min(30, 32 / cpx);
-        for (int nt = nt_frames + pass; nt <= nt_hi && !found; ++nt) {
-            if (nt > 30 || cpx * nt > 32 || 8 * TE > nct || d.Kn * TE > 2 * nct) continue;
-            pl.TE = TE; pl.NT = nt;
-            pl.UPW = cdiv(d.Dd, nt); pl.CPW = cdiv(d.E, nt);
-            if (pl.UPW > 64 || pl.UPW + pl.CPW > RCB * ncw + RPB * NPB || (TE + pl.UPW + 1) / 2 + 1 > nct) continue;
-            pl.CG2 = even((pl.CPW + pl.UPW + 1) / 2); pl.QG2 = even(d.A / 2); pl.VG2 = even((TE * d.Kn + 1) / 2); pl.NG2 = even((TE + pl.UPW + 1) / 2);
-            if (pl.NT * pl.QG2 * 2 < NPB * 64 * 11) continue;       // s_qst doubles as the stage of the polling waves' partial accumulators
-            const BCarve cv = bwd_carve(TE, 12, d.A, d.E, d.Kn, d.Ks, pl.NT, pl.UPW, pl.CG2, pl.QG2, pl.NG2);
-            pl.lds = 2 * (size_t)cv.shorts + 4 * (size_t)cv.floats;
-            if (getenv("ASR_DEC_PLAN_DEBUG")) fprintf(stderr, "[asr] resident bwd plan B=%d T'=%d: NT=%d TE=%d LDS=%zu\n", d.B, d.Tp, pl.NT, pl.TE, pl.lds);
-            if (pl.lds > 160 * 1024 - 4096) continue;
-            found = true;
-        }
-    }
-    if (!found) return pl;
-    pl.status_bytes = 4096;
-    pl.xbuf_bytes = align_up256(2 * (size_t)d.B * pl.NT * (pl.CG2 + pl.QG2 + pl.VG2 + pl.NG2) * sizeof(u64));
-    pl.w16_bytes = align_up256((size_t)(d.Dd + d.E + d.Dd) * pl.R4 * 2);
-    pl.dg_bytes = align_up256((size_t)d.B * d.L * 4 * d.Dd * sizeof(float));
-    pl.total = pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes + pl.dg_bytes;
-    pl.ok = true;
-    return pl;
-}
-
-
 }  // namespace
 
-// decoder_stream.hip
-size_t dec_bwd_stream_work_bytes(const asr_dec_dims_t& d);
-int dec_bwd_stream_tiles(const asr_dec_dims_t& d);
-float* dec_bwd_stream_dgates(const asr_dec_dims_t& d, void* work);
-int dec_bwd_streamed(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const int64_t* enc_len,
-                     const float* dhs, float* dxin, float* dq, float* dkey, float* slots, int slot, const float* wcatT, const float* wqT,
-                     void* work, size_t work_bytes, float** dgates_out, hipStream_t st);
-
-// 0: per-step kernels, 1: tiles resident on chip (this file), 2: streamed tiles (decoder_stream.hip)
-int dec_bwd_plan_kind(const asr_dec_dims_t& d) {
-    stream_env();
-    const PersistPlanB pl = persist_plan_b(d);
-    if (pl.ok && !g_stream_bwd) return 1;
-    return dec_bwd_stream_work_bytes(d) ? 2 : (pl.ok ? 1 : 0);
-}
-float* dec_bwd_persist_dgates(const asr_dec_dims_t& d, void* work) {
-    if (dec_bwd_plan_kind(d) == 2) return dec_bwd_stream_dgates(d, work);
-    const PersistPlanB pl = persist_plan_b(d);
-    return (float*)((char*)work + pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes);
-}
-// the work area is sized for whichever plan may be taken for the shape (the preference can be switched between calls)
-size_t dec_bwd_persist_work_bytes(const asr_dec_dims_t& d) {
-    const PersistPlanB pl = persist_plan_b(d);
-    return std::max(pl.ok ? pl.total : (size_t)0, dec_bwd_stream_work_bytes(d));
-}
-int dec_bwd_persist_tiles(const asr_dec_dims_t& d) {
-    const int kind = dec_bwd_plan_kind(d);
-    if (kind == 2) return dec_bwd_stream_tiles(d);
-    return kind == 1 ? persist_plan_b(d).NT : 0;
-}
-// slots are sized for the larger tile count of the two plans
-int dec_bwd_persist_tiles_max(const asr_dec_dims_t& d) {
-    const PersistPlanB pl = persist_plan_b(d);
-    return std::max(pl.ok ? pl.NT : 0, dec_bwd_stream_tiles(d));
-}
-
-// Returns ASR_OK when the whole backward loop was launched, 1 when there is no persistent plan, negative on error.
-// dhs: (B,L,Dd) gradient wrt h from the output layer; wcatT: ((Dd+E+Dd) x 4Dd) fp32 transposed [W_ih | W_hh]; wqT: (Dd x A).
-// *dgates_out: (B*L, 4Dd) gate pre-activation gradients inside `work`.
 int dec_bwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const int64_t* enc_len,
                        const float* dhs, float* dxin, float* dq, float* dkey, float* slots, int slot, const float* wcatT, const float* wqT,
                        void* work, size_t work_bytes, float** dgates_out, hipStream_t st) {
-    if (g_persist_bwd < 0) { const char* e = getenv("ASR_DEC_PERSIST_BWD"); g_persist_bwd = (e && e[0] == '0') ? 0 : 1; }
+    read_switches();
     if (!g_persist_bwd) return 1;
-    if (dec_bwd_plan_kind(d) == 2) return dec_bwd_streamed(d, w, s, enc_len, dhs, dxin, dq, dkey, slots, slot, wcatT, wqT, work, work_bytes, dgates_out, st);
-    const PersistPlanB pl = persist_plan_b(d);
-    if (!pl.ok || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv || !s.enc16) return 1;
-    char* base = (char*)work;
-    unsigned* status = (unsigned*)base;
-    u64* xbuf = (u64*)(base + pl.status_bytes);
-    unsigned short* w16 = (unsigned short*)(base + pl.status_bytes + pl.xbuf_bytes);
-    float* dgates = (float*)(base + pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes);
-    *dgates_out = dgates;
-    clear_work(work, pl.xbuf_bytes, st);
-    hipLaunchKernelGGL(cast_rows_bf16_kernel, dim3(512), dim3(256), 0, st, wcatT, w16, d.Dd + d.E + d.Dd, 4 * d.Dd, pl.R4);
-    static int allow = -1, delay = -1;
-    if (allow < 0) { const char* e = getenv("ASR_LSTM_XCD_LOCAL"); allow = (e && e[0] == '0') ? 0 : 1; }
-    if (delay < 0) { const char* e = getenv("ASR_DEC_BWD_POLL_DELAY"); delay = e ? atoi(e) : 0; }
-    PB p{d, w, s, (const unsigned short*)s.enc16, enc_len, dhs, dxin, dq, dkey, slots, dgates, w16, wqT, xbuf, status,
-         slot, pl.NT, pl.TE, pl.UPW, pl.CPW, pl.R4, pl.CG2, pl.QG2, pl.VG2, pl.NG2, allow, delay};
-    const int cpx = cdiv(d.B, 8), ncw = cdiv(d.A, 64);
-    const dim3 grid(8 * cpx * pl.NT), block(64 * (ncw + NPB));
-#define DPB_LAUNCH(KN_, TE_)                                                                                                    \
-    {                                                                                                                           \
-        static unsigned char attr_[32];                                                                                         \
-        if (first_on_device(attr_)) hipFuncSetAttribute((const void*)dec_bwd_persist<KN_, TE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); \
-        if (!grid_resident(dec_bwd_persist<KN_, TE_>, (int)grid.x, (int)block.x, pl.lds)) return 1;                               \
-        hipLaunchKernelGGL((dec_bwd_persist<KN_, TE_>), grid, block, pl.lds, st, p);                                              \
-        hipLaunchKernelGGL(bump_epoch_kernel, dim3(1), dim3(1), 0, st, status);                                                   \
-    }
-    if (d.Kn <= 4) { if (pl.TE == 40) DPB_LAUNCH(4, 40) else DPB_LAUNCH(4, 0) }
-    else { if (pl.TE == 40) DPB_LAUNCH(10, 40) else DPB_LAUNCH(10, 0) }
-#undef DPB_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("asr_att_decoder_bwd(persistent): launch failed: %s", hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
+    const BwdPlan pl = bwd_plan(d);
+    if (pl.kind == 2) return dec_bwd_streamed(d, w, s, enc_len, dhs, dxin, dq, dkey, slots, slot, wcatT, wqT, work, work_bytes, dgates_out, st);
+    if (!pl.kind || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv || !s.enc16) return 1;
+    const BwdWork wk = bwd_work(d, pl, work);
+    *dgates_out = wk.dgates;
+    clear_work(work, wk.xbuf_bytes, st);
+    hipLaunchKernelGGL(cast_rows_bf16_kernel, dim3(512), dim3(256), 0, st, wcatT, wk.w16, d.Dd + d.E + d.Dd, 4 * d.Dd, pl.R4);
+    const PB p{d, w, s, (const unsigned short*)s.enc16, enc_len, dhs, dxin, dq, dkey, slots, wk.dgates, wk.w16, wqT, wk.xbuf, wk.status,
+               slot, pl.NT, pl.TE, pl.UPW, pl.CPW, pl.R4, pl.CG2, pl.QG2, pl.VG2, pl.NG2, xcd_local_allowed(), dec_bwd_poll_delay()};
+    const ClusterLaunch go{"asr_att_decoder_bwd(persistent)", 160 * 1024 - 4096, cluster_grid(d, pl.NT), dim3(64 * (cdiv(d.A, 64) + NPB)), pl.lds, st};
+    if (d.Kn <= 4) return pl.TE == 40 ? go.run<dec_bwd_persist<4, 40>>(p) : go.run<dec_bwd_persist<4, 0>>(p);
+    return pl.TE == 40 ? go.run<dec_bwd_persist<10, 40>>(p) : go.run<dec_bwd_persist<10, 0>>(p);
 }

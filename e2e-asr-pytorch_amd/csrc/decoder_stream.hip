@@ -35,35 +35,6 @@ struct PSF {
     int allow_local;
 };
 
-// LDS carve (floats behind the bf16 conv tile), shared by kernel and host plan
-struct FCarve { int cvx_shorts, img, shorts, WT, ATP, NG, x2, q, wg, attp, wc, epart, e, w, g, cpart, stage, stage_floats, floats; };
-__host__ __device__ inline FCarve fwd_carve(int TEB, int NT, int A, int E, int Kn, int Ks, int KCP, int UPW, int SG2) {
-    FCarve c;
-    c.cvx_shorts = TEB * FCVX_LD;
-    c.img = (c.cvx_shorts + 7) & ~7;                          // bf16 images of the convolution (conv_geo)
-    c.shorts = (c.img + conv_img_shorts(conv_geo(TEB, Ks)) + 7) & ~7;
-    c.WT = (2 * Ks + 1 + 3) & ~3;
-    c.ATP = (NT * TEB + 2 * Ks + 8 + 3) & ~3;
-    const int nch = E >> 3;
-    c.NG = (64 * NCW) / nch; if (c.NG > 8) c.NG = 8;          // frame groups of the partial-context pass
-    int o = 0;
-    c.x2 = o; o += 2 * KCP;
-    c.q = o; o += (A + 3) & ~3;
-    c.wg = o; o += (A + 3) & ~3;
-    c.attp = o; o += c.ATP;
-    c.wc = o;                                             // (the fp32 filter rows of dec_fwd_persist live in the bf16 filter image here)
-    c.epart = o; o += NCW * TEB;
-    c.e = o; o += TEB;
-    c.w = o; o += TEB;
-    c.g = o; o += (4 * UPW + 3) & ~3;
-    c.cpart = o; o += c.NG * E;
-    c.stage = o;
-    c.stage_floats = NT * 2 * SG2; if (c.stage_floats < Kn * TEB) c.stage_floats = Kn * TEB;      // doubles as the conv's partial sums
-    o += c.stage_floats;
-    c.floats = o;
-    return c;
-}
-
 template <int KNMAX>
 __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_stream(PSF p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -597,79 +568,7 @@ __global__ void build_key16p_kernel(const float* __restrict__ key, unsigned shor
     }
 }
 
-struct StreamPlanF { bool ok; int NT, TEB, UPW, QPW, CPW, HG2, QG2, SG2, KC, KCP; size_t lds, status_bytes, xbuf_bytes, wcat_bytes, emb_bytes, key_bytes, total; };
-
-StreamPlanF stream_plan_f(const asr_dec_dims_t& d) {
-    StreamPlanF pl{};
-    pl.ok = false;
-    if (d.NL != 1 || d.B > 64 || d.B < 1 || d.A > 16 * FSW_NU * NCW || d.Kn > 10 || (d.E & 7) != 0 || d.E > 8 * 64 * NCW || d.Dd > 20 * 32 || d.Tp < 1) return pl;
-    const int cpx = cdiv(d.B, 8);
-    pl.NT = std::min(30, 32 / cpx);
-    pl.TEB = 16 * cdiv(d.Tp, 16 * pl.NT);
-    pl.UPW = cdiv(d.Dd, pl.NT); pl.QPW = cdiv(d.A, pl.NT); pl.CPW = cdiv(d.E, pl.NT);
-    if (pl.UPW > 120 || cdiv(4 * pl.UPW, NCW) > 60) return pl;
-    auto even = [](int x) { return (x + 1) & ~1; };
-    pl.HG2 = even((pl.UPW + 1) / 2); pl.QG2 = even((pl.QPW + 1) / 2); pl.SG2 = even((pl.TEB + 2) / 2 + d.E / 4);      // record: e pairs, (m, s), context as halves
-    pl.KC = d.E + d.Dd; pl.KCP = (pl.KC + 7) & ~7;
-    const FCarve c = fwd_carve(pl.TEB, pl.NT, d.A, d.E, d.Kn, d.Ks, pl.KCP, pl.UPW, pl.SG2);
-    if (c.NG < 1) return pl;
-    pl.lds = 2 * (size_t)c.shorts + 4 * (size_t)c.floats;
-    if (getenv("ASR_DEC_PLAN_DEBUG")) fprintf(stderr, "[asr] streamed fwd plan B=%d T'=%d: NT=%d TEB=%d UPW=%d LDS=%zu\n", d.B, d.Tp, pl.NT, pl.TEB, pl.UPW, pl.lds);
-    if (pl.lds > 156 * 1024) return pl;
-    pl.status_bytes = 4096;
-    pl.xbuf_bytes = align_up256(2 * (size_t)d.B * pl.NT * (pl.HG2 + pl.QG2 + pl.SG2) * sizeof(u64));
-    pl.wcat_bytes = align_up256((size_t)4 * d.Dd * pl.KCP * 2);
-    pl.emb_bytes = align_up256((size_t)d.B * d.L * 4 * d.Dd * sizeof(float));
-    pl.key_bytes = align_up256((size_t)d.B * pl.NT * ((pl.TEB + 31) / 32) * 4 * d.A * 16);      // pair image (odd tile counts are padded)
-    pl.total = pl.status_bytes + pl.xbuf_bytes + pl.wcat_bytes + pl.emb_bytes + pl.key_bytes;
-    pl.ok = true;
-    return pl;
-}
-
 }  // namespace
-
-size_t dec_fwd_stream_work_bytes(const asr_dec_dims_t& d) {
-    const StreamPlanF pl = stream_plan_f(d);
-    return pl.ok ? pl.total : 0;
-}
-
-// Returns ASR_OK when the whole loop was launched, 1 when the configuration has no streamed plan, negative on error.
-int dec_fwd_streamed(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const float* enc,
-                     const int64_t* enc_len, void* work, size_t work_bytes, hipStream_t st) {
-    const StreamPlanF pl = stream_plan_f(d);
-    if (!pl.ok || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv || !s.enc16) return 1;
-    char* base = (char*)work;
-    unsigned* status = (unsigned*)base;
-    u64* xbuf = (u64*)(base + pl.status_bytes);
-    unsigned short* wcat16 = (unsigned short*)(base + pl.status_bytes + pl.xbuf_bytes);
-    float* embproj = (float*)(base + pl.status_bytes + pl.xbuf_bytes + pl.wcat_bytes);
-    unsigned short* key16t = (unsigned short*)(base + pl.status_bytes + pl.xbuf_bytes + pl.wcat_bytes + pl.emb_bytes);
-    clear_work(work, pl.xbuf_bytes, st);
-    hipLaunchKernelGGL(build_wcat16_kernel, dim3(512), dim3(256), 0, st, w.Wih[0], w.Whh[0], wcat16, 4 * d.Dd, d.Dd, d.E, pl.KCP);
-    hipLaunchKernelGGL(build_key16p_kernel, dim3(1024), dim3(256), 0, st, s.key, key16t, d.B, d.Tp, d.A, pl.NT, pl.TEB);
-    const int XW = d.Dd + d.E;
-    int rc = asr_gemm(s.xin, w.Wih[0], embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0,
-                      0, 0, ASR_BF16, (asr_stream_t)st);
-    if (rc != ASR_OK) return rc;
-    static int allow = -1;
-    if (allow < 0) { const char* e = getenv("ASR_LSTM_XCD_LOCAL"); allow = (e && e[0] == '0') ? 0 : 1; }
-    PSF p{d, w, s, enc, enc_len, wcat16, embproj, key16t, xbuf, status, pl.NT, pl.TEB, pl.UPW, pl.QPW, pl.CPW, pl.HG2, pl.QG2, pl.SG2, pl.KC, pl.KCP, allow};
-    const int cpx = cdiv(d.B, 8);
-    const dim3 grid(8 * cpx * pl.NT), block(64 * (NCW + NPW));
-#define DSF_LAUNCH(KN_)                                                                                                         \
-    {                                                                                                                           \
-        static unsigned char attr_[32];                                                                                         \
-        if (first_on_device(attr_)) hipFuncSetAttribute((const void*)dec_fwd_stream<KN_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048); \
-        if (!grid_resident(dec_fwd_stream<KN_>, (int)grid.x, (int)block.x, pl.lds)) return 1;                                   \
-        hipLaunchKernelGGL((dec_fwd_stream<KN_>), grid, block, pl.lds, st, p);                                                  \
-        hipLaunchKernelGGL(bump_epoch_kernel, dim3(1), dim3(1), 0, st, status);                                                 \
-    }
-    if (d.Kn <= 4) DSF_LAUNCH(4) else DSF_LAUNCH(10)
-#undef DSF_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("asr_att_decoder_fwd(streamed): launch failed: %s", hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
-}
 
 // =================================================================================================
 // Backward of the teacher-forced decoder loop with streamed tiles: ONE persistent launch, the cluster / record scheme of
@@ -686,7 +585,7 @@ int dec_fwd_streamed(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const 
 // A step costs two workgroup barriers per 48-frame group on top of dec_bwd_persist's; groups past the utterance's length are
 // skipped (their dconv is published as zeros).
 // =================================================================================================
-#include "decoder_bwd_common.h"
+#include "decoder_plan.h"
 
 namespace {
 
@@ -712,42 +611,6 @@ struct PSB {
     int allow_local;
     int poll_delay;
 };
-
-struct SBCarve { int AP, DW, PADL, WT, parts, dl, wp16, dg16, cvx, cvT, shorts; int wc, crec, qst, nrec, dcp, de, out, hq, pt, dcx, dq, floats; };
-__host__ __device__ inline SBCarve sbwd_carve(int TEB, int A, int E, int Kn, int Ks, int NT, int UPW, int CPW, int CG2, int QG2, int NG2) {
-    SBCarve c;
-    const int nct = 64 * ((A + 63) / 64);
-    int ap8 = 8 * ((A + 63) / 64); if ((ap8 & 1) == 0) ++ap8;
-    c.AP = 8 * ap8;
-    c.PADL = Ks + 8 + ((4 - ((2 * Ks) & 3)) & 3);       // PADL + Ks is a multiple of 4
-    c.DW = (c.PADL + TEB + Ks + 8 + 3) & ~3;            // zero-padded dconv window of the tile: frames tau0 - PADL ..
-    if (((c.DW >> 2) & 1) == 0) c.DW += 4;
-    c.WT = (2 * Ks + 1 + 3) & ~3;
-    const int nitem = Kn * (TEB >> 4);                   // (kernel, 16-frame group) items of the transposed convolution
-    c.parts = nct / nitem; if (c.parts > 4) c.parts = 4; if (c.parts < 1) c.parts = 1;
-    int o = 0;
-    c.dl = o; o += 16 * SW_MT * c.AP;
-    c.wp16 = o; o += 16 * c.AP;
-    c.dg16 = o; o += 64 * KCHB * 4;
-    c.cvx = o; o += 16 * SW_MT * CVX_LD;
-    c.cvT = o; o += 16 * CVT_LD;
-    c.shorts = (o + 7) & ~7;
-    o = 0;
-    c.wc = o; o += Kn * c.WT;
-    c.crec = o; o += NT * CG2 * 2;
-    c.qst = o; o += NT * QG2 * 2;
-    c.nrec = o; o += NT * NG2 * 2 + 8;
-    c.dcp = o; o += Kn * c.DW;
-    c.de = o; o += 16 * SW_MT * ((TEB + 16 * SW_MT - 1) / (16 * SW_MT)) + 8;
-    const int nout = CPW + UPW;
-    c.out = o; o += (nout > RPWB * 8 ? ((nout + 3) & ~3) : RPWB * 8);
-    c.hq = o; o += (UPW > 64 ? ((UPW + 3) & ~3) : 64);
-    c.pt = o; o += c.parts * Kn * TEB;
-    c.dcx = o; o += (E + 3) & ~3;
-    c.dq = o; o += (A + 3) & ~3;
-    c.floats = o;
-    return c;
-}
 
 // one 48-frame group of the energy-backward sweep (decoder_bwd_common.h::sweep_step with the key fragment in registers): the dkey
 // contribution of a (unit, 16-frame tile) is added to the value read ahead (`old`) and stored at once, and the tile's key
@@ -1441,89 +1304,51 @@ __global__ void dkey_untranspose_kernel(const float* __restrict__ dkT, float* __
     }
 }
 
-struct StreamPlanB { bool ok; int TEB, NT, UPW, CPW, R4, CG2, QG2, VG2, NG2; size_t lds, status_bytes, xbuf_bytes, w16_bytes, dg_bytes, key_bytes, dkt_bytes, total; };
-
-StreamPlanB stream_plan_b(const asr_dec_dims_t& d) {
-    StreamPlanB pl{};
-    pl.ok = false;
-    if (d.NL != 1 || d.B > 64 || d.B < 1 || d.A > 320 || d.A < 16 || d.Kn > 10 || (d.E & 7) != 0 || (d.A & 1) != 0 || d.Dd > 64 * KCHB || d.L < 1 || d.Tp < 1) return pl;
-    const int cpx = cdiv(d.B, 8);
-    const int ncw = cdiv(d.A, 64), nct = 64 * ncw;
-    if (d.Dd > nct || d.E > 2 * nct || d.E > 640 || d.Tp > 6 * nct || d.Kn * 16 * SW_MT > 2 * nct) return pl;
-    if (cdiv(d.A, 16) > SW_NU * ncw + SW_NUP * NPB) return pl;           // sweep units over all waves
-    pl.R4 = (4 * d.Dd + 7) & ~7;
-    pl.NT = std::min(30, 32 / cpx);
-    pl.TEB = 16 * cdiv(d.Tp, 16 * pl.NT);
-    pl.UPW = cdiv(d.Dd, pl.NT); pl.CPW = cdiv(d.E, pl.NT);
-    auto even = [](int x) { return (x + 1) & ~1; };
-    pl.CG2 = even((pl.CPW + pl.UPW + 1) / 2); pl.QG2 = even(d.A / 2); pl.VG2 = even((pl.TEB * d.Kn + 1) / 2); pl.NG2 = even((pl.TEB + pl.UPW + 1) / 2);
-    const SBCarve cv = sbwd_carve(pl.TEB, d.A, d.E, d.Kn, d.Ks, pl.NT, pl.UPW, pl.CPW, pl.CG2, pl.QG2, pl.NG2);
-    pl.lds = 2 * (size_t)cv.shorts + 4 * (size_t)cv.floats;
-    if (getenv("ASR_DEC_PLAN_DEBUG")) fprintf(stderr, "[asr] streamed bwd plan B=%d T'=%d: NT=%d TEB=%d UPW=%d LDS=%zu\n", d.B, d.Tp, pl.NT, pl.TEB, pl.UPW, pl.lds);
-    if (pl.lds > 160 * 1024 - 4096) return pl;
-    pl.status_bytes = 4096;
-    pl.xbuf_bytes = align_up256(2 * (size_t)d.B * pl.NT * (pl.CG2 + pl.QG2 + pl.VG2 + pl.NG2) * sizeof(u64));
-    pl.w16_bytes = align_up256((size_t)(d.Dd + d.E + d.Dd) * pl.R4 * 2);
-    pl.dg_bytes = align_up256((size_t)d.B * d.L * 4 * d.Dd * sizeof(float));
-    pl.key_bytes = align_up256((size_t)d.B * pl.NT * pl.TEB * d.A * 2);
-    pl.dkt_bytes = align_up256((size_t)d.B * pl.NT * pl.TEB * d.A * 4);
-    pl.total = pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes + pl.dg_bytes + pl.key_bytes + pl.dkt_bytes;
-    pl.ok = true;
-    return pl;
-}
-
 }  // namespace
 
-size_t dec_bwd_stream_work_bytes(const asr_dec_dims_t& d) { const StreamPlanB pl = stream_plan_b(d); return pl.ok ? pl.total : 0; }
-int dec_bwd_stream_tiles(const asr_dec_dims_t& d) { const StreamPlanB pl = stream_plan_b(d); return pl.ok ? pl.NT : 0; }
-float* dec_bwd_stream_dgates(const asr_dec_dims_t& d, void* work) {
-    const StreamPlanB pl = stream_plan_b(d);
-    return (float*)((char*)work + pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes);
+// Both launchers: the contract of dec_fwd_persistent / dec_bwd_persistent (decoder_internal.h), which hand the shapes of a streamed plan on
+int dec_fwd_streamed(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const float* enc,
+                     const int64_t* enc_len, void* work, size_t work_bytes, hipStream_t st) {
+    const FwdPlan pl = stream_plan_f(d);
+    if (!pl.kind || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv || !s.enc16) return 1;
+    const FwdWork wk = fwd_work(d, pl, work);
+    clear_work(work, wk.xbuf_bytes, st);
+    hipLaunchKernelGGL(build_wcat16_kernel, dim3(512), dim3(256), 0, st, w.Wih[0], w.Whh[0], wk.wcat16, 4 * d.Dd, d.Dd, d.E, pl.KCP);
+    hipLaunchKernelGGL(build_key16p_kernel, dim3(1024), dim3(256), 0, st, s.key, wk.key16t, d.B, d.Tp, d.A, pl.NT, pl.TE);
+    const int XW = d.Dd + d.E;
+    int rc = asr_gemm(s.xin, w.Wih[0], wk.embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0,
+                      0, 0, ASR_BF16, (asr_stream_t)st);
+    if (rc != ASR_OK) return rc;
+    const PSF p{d, w, s, enc, enc_len, wk.wcat16, wk.embproj, wk.key16t, wk.xbuf, wk.status, pl.NT, pl.TE, pl.UPW, pl.QPW, pl.CPW, pl.HG2, pl.QG2,
+                pl.SG2, pl.KC, pl.KCP, xcd_local_allowed()};
+    const ClusterLaunch go{"asr_att_decoder_fwd(streamed)", 160 * 1024 - 2048, cluster_grid(d, pl.NT), dim3(64 * (NCW + NPW)), pl.lds, st};
+    return d.Kn <= 4 ? go.run<dec_fwd_stream<4>>(p) : go.run<dec_fwd_stream<10>>(p);
 }
 
-// Same contract as dec_bwd_persistent (decoder_persist.hip).
 int dec_bwd_streamed(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const int64_t* enc_len,
                      const float* dhs, float* dxin, float* dq, float* dkey, float* slots, int slot, const float* wcatT, const float* wqT,
                      void* work, size_t work_bytes, float** dgates_out, hipStream_t st) {
-    const StreamPlanB pl = stream_plan_b(d);
-    if (!pl.ok || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv || !s.enc16) return 1;
-    char* base = (char*)work;
-    unsigned* status = (unsigned*)base;
-    u64* xbuf = (u64*)(base + pl.status_bytes);
-    unsigned short* w16 = (unsigned short*)(base + pl.status_bytes + pl.xbuf_bytes);
-    float* dgates = (float*)(base + pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes);
-    unsigned short* key16t = (unsigned short*)(base + pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes + pl.dg_bytes);
-    float* dkT = (float*)(base + pl.status_bytes + pl.xbuf_bytes + pl.w16_bytes + pl.dg_bytes + pl.key_bytes);
-    *dgates_out = dgates;
-    clear_work(work, pl.xbuf_bytes, st);
-    hipMemsetAsync(dkT, 0, pl.dkt_bytes, st);
-    hipLaunchKernelGGL(cast_rows_bf16_kernel, dim3(512), dim3(256), 0, st, wcatT, w16, d.Dd + d.E + d.Dd, 4 * d.Dd, pl.R4);
-    hipLaunchKernelGGL(build_key16t_kernel, dim3(1024), dim3(256), 0, st, s.key, key16t, d.B, d.Tp, d.A, pl.NT * pl.TEB / 4);
-    static int allow = -1, delay = -1;
-    if (allow < 0) { const char* e = getenv("ASR_LSTM_XCD_LOCAL"); allow = (e && e[0] == '0') ? 0 : 1; }
-    if (delay < 0) { const char* e = getenv("ASR_DEC_BWD_POLL_DELAY"); delay = e ? atoi(e) : 0; }
-    PSB p{d, w, s, (const unsigned short*)s.enc16, enc_len, dhs, dxin, dq, dkT, slots, dgates, w16, wqT, key16t, xbuf, status,
-          slot, pl.NT, pl.TEB, pl.UPW, pl.CPW, pl.R4, pl.CG2, pl.QG2, pl.VG2, pl.NG2, allow, delay};
-    const int cpx = cdiv(d.B, 8), ncw = cdiv(d.A, 64);
-    const dim3 grid(8 * cpx * pl.NT), block(64 * (ncw + NPB));
-#define DSB_LAUNCH(KN_, RC_, RP_)                                                                                               \
-    {                                                                                                                           \
-        static unsigned char attr_[32];                                                                                         \
-        if (first_on_device(attr_)) hipFuncSetAttribute((const void*)dec_bwd_stream<KN_, RC_, RP_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); \
-        if (!grid_resident(dec_bwd_stream<KN_, RC_, RP_>, (int)grid.x, (int)block.x, pl.lds)) return 1;                         \
-        hipLaunchKernelGGL((dec_bwd_stream<KN_, RC_, RP_>), grid, block, pl.lds, st, p);                                        \
-        hipLaunchKernelGGL(bump_epoch_kernel, dim3(1), dim3(1), 0, st, status);                                                 \
-    }
-    const int nrows = pl.CPW + pl.UPW;
+    const BwdPlan pl = stream_plan_b(d);
+    if (!pl.kind || !work || work_bytes < pl.total || ((uintptr_t)work & 255) != 0 || !s.conv || !s.enc16) return 1;
+    const BwdWork wk = bwd_work(d, pl, work);
+    *dgates_out = wk.dgates;
+    clear_work(work, wk.xbuf_bytes, st);
+    hipMemsetAsync(wk.dkT, 0, wk.dkt_bytes, st);
+    hipLaunchKernelGGL(cast_rows_bf16_kernel, dim3(512), dim3(256), 0, st, wcatT, wk.w16, d.Dd + d.E + d.Dd, 4 * d.Dd, pl.R4);
+    hipLaunchKernelGGL(build_key16t_kernel, dim3(1024), dim3(256), 0, st, s.key, wk.key16t, d.B, d.Tp, d.A, pl.NT * pl.TE / 4);
+    const PSB p{d, w, s, (const unsigned short*)s.enc16, enc_len, dhs, dxin, dq, wk.dkT, slots, wk.dgates, wk.w16, wqT, wk.key16t, wk.xbuf, wk.status,
+                slot, pl.NT, pl.TE, pl.UPW, pl.CPW, pl.R4, pl.CG2, pl.QG2, pl.VG2, pl.NG2, xcd_local_allowed(), dec_bwd_poll_delay()};
+    const int ncw = cdiv(d.A, 64);
+    const ClusterLaunch go{"asr_att_decoder_bwd(streamed)", 160 * 1024 - 4096, cluster_grid(d, pl.NT), dim3(64 * (ncw + NPB)), pl.lds, st};
     // measured (tools/diag_dec_stream.py, us per step): B=8 x T'=1225 half-resident 29.8 / all rows streamed 30.1 / the full resident
     // set of dec_bwd_persist (8 + 9 rows per wave, 110 spilled registers here) 34.5; B=16 x T'=1225 streamed 35.2 / full set 37.8
-    int res = (nrows <= 4 * ncw + 5 * NPB) ? 1 : 0;
-    if (const char* e = getenv("ASR_DEC_STREAM_RES")) { if (atoi(e) == 0) res = 0; }        // experiments: stream every row
-    if (d.Kn <= 4) { if (res == 1) DSB_LAUNCH(4, 4, 5) else DSB_LAUNCH(4, 0, 0) }
-    else { if (res == 1) DSB_LAUNCH(10, 4, 5) else DSB_LAUNCH(10, 0, 0) }
-#undef DSB_LAUNCH
-    hipLaunchKernelGGL(dkey_untranspose_kernel, dim3(2048), dim3(256), 0, st, dkT, dkey, d.B, d.Tp, d.A, (long)pl.NT * pl.TEB / 4);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("asr_att_decoder_bwd(streamed): launch failed: %s", hipGetErrorString(e)); return ASR_E_LAUNCH; }
+    bool res = pl.CPW + pl.UPW <= 4 * ncw + 5 * NPB;
+    if (const char* e = getenv("ASR_DEC_STREAM_RES")) { if (atoi(e) == 0) res = false; }        // experiments: stream every row
+    int rc;
+    if (d.Kn <= 4) rc = res ? go.run<dec_bwd_stream<4, 4, 5>>(p) : go.run<dec_bwd_stream<4, 0, 0>>(p);
+    else rc = res ? go.run<dec_bwd_stream<10, 4, 5>>(p) : go.run<dec_bwd_stream<10, 0, 0>>(p);
+    if (rc != ASR_OK) return rc;
+    hipLaunchKernelGGL(dkey_untranspose_kernel, dim3(2048), dim3(256), 0, st, wk.dkT, dkey, d.B, d.Tp, d.A, (long)pl.NT * pl.TE / 4);
+    ASR_LAUNCH_CHECK(go.who);
     return ASR_OK;
 }

@@ -1,13 +1,26 @@
-// Inter-workgroup hand-off primitives of the persistent kernels (lstm_persist2.hip, decoder_persist.hip):
-// data-tagged 8-byte granules, 16-byte polling sweeps, XCD placement consensus.  See cdna_hip_programming.md G16 form R2
-// and DESIGN.md 4.2.  Everything here is `static` per translation unit.
+// Inter-workgroup hand-off primitives of the persistent kernels (lstm_persist2.hip, lstm_persist3.hip, decoder_persist.hip,
+// decoder_stream.hip; core.hip scrubs their work areas): data-tagged 8-byte granules, 16-byte polling sweeps, XCD placement
+// consensus.  See cdna_hip_programming.md G16 form R2 and DESIGN.md 4.2.  Everything here is `static` per translation unit.
 #pragma once
 #include "common.h"
+#include <stdlib.h>
 
 namespace {
 
 typedef unsigned long long u64;
 constexpr int SPIN_LIMIT2 = 1 << 22;
+
+// An environment switch, read on first use: one that is on by default is turned off by a leading '0', one that is off by
+// default is turned on by a leading '1'.
+inline int env_switch(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return (e && e[0] == (dflt ? '0' : '1')) ? !dflt : dflt;
+}
+// ASR_LSTM_XCD_LOCAL=0 forces write-through hand-offs even where a cluster is verified to share an XCD (xcd_consensus)
+inline int xcd_local_allowed() {
+    static const int on = env_switch("ASR_LSTM_XCD_LOCAL", 1);
+    return on;
+}
 
 __device__ __forceinline__ u64 ld_gran(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_gran(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

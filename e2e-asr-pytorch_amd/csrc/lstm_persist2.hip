@@ -453,11 +453,6 @@ int launch_p2(KernelT kernel, const P2& p, size_t lds, hipStream_t st, const cha
     return ASR_OK;
 }
 
-int allow_local() {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("ASR_LSTM_XCD_LOCAL"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on;
-}
 int poll_delay(bool bwd) {
     static int df = -1, db = -1;
     if (df < 0) {
@@ -492,7 +487,7 @@ int lstm_fwd_persistent2(float* gates, const float* whh, const float* bias2, flo
     const size_t need = 256 + 2 * (size_t)ND * fwd_region(B, H) * sizeof(u64);
     if (ws_bytes < need) return 1;
     hipMemsetAsync(ws, 0, need, st);
-    P2 p{gates, whh, bias2, y, c, (u64*)((char*)ws + 256), (unsigned*)ws, B, T, H, ND, H / 16, allow_local(), poll_delay(false), next_epoch()};
+    P2 p{gates, whh, bias2, y, c, (u64*)((char*)ws + 256), (unsigned*)ws, B, T, H, ND, H / 16, xcd_local_allowed(), poll_delay(false), next_epoch()};
     const int nks = (H + 31) / 32;
     FWD2_CASE(1) FWD2_CASE(2) FWD2_CASE(4) FWD2_CASE(6) FWD2_CASE(8) FWD2_CASE(10) FWD2_CASE(12) FWD2_CASE(16)
     return 1;
@@ -506,7 +501,7 @@ int lstm_bwd_persistent2(float* gates, const float* whh, const float* dy, const 
     if (ws_bytes < need) return 1;
     hipMemsetAsync(ws, 0, need, st);
     P2 p{gates, whh, nullptr, const_cast<float*>(dy), const_cast<float*>(c), (u64*)((char*)ws + 256), (unsigned*)ws,
-         B, T, H, ND, (int)P, allow_local(), poll_delay(true), next_epoch()};
+         B, T, H, ND, (int)P, xcd_local_allowed(), poll_delay(true), next_epoch()};
     const int nto = ((int)P + 3) / 4;
     BWD2_CASE(1) BWD2_CASE(2) BWD2_CASE(3) BWD2_CASE(4) BWD2_CASE(5) BWD2_CASE(6) BWD2_CASE(8)
     return 1;

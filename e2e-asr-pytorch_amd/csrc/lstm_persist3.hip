@@ -681,10 +681,6 @@ __global__ __launch_bounds__(512) void lstm_bwd_p4(P3 p) {
     DIAG3_DUMP(0, 64)
 }
 
-int allow_local3() {
-    static const int on = [] { const char* e = getenv("ASR_LSTM_XCD_LOCAL"); return (e && e[0] == '0') ? 0 : 1; }();
-    return on;
-}
 // which backward kernel: 3 = reduce-scatter of partial dh (lstm_bwd_p3, default), 4 = all-gather of the gate gradients
 // (lstm_bwd_p4, ASR_LSTM3_BWD=4).  Measured on MI355X, B=16 x T=1200 x H=320: 1.36 vs 1.77 us per step (B=64: 1.65 vs 4.4) -
 // the all-gather form publishes 1/5 of the bytes and has no P-way sum, but every workgroup polls 4x the bytes (the whole group's
@@ -765,7 +761,7 @@ int lstm_fwd_persistent3(unsigned short* gates, const float* whh, unsigned short
     unsigned* hdr = (unsigned*)((char*)ws + (size_t)(epoch & 1u) * HDR_BYTES);
     unsigned* hdr_next = (unsigned*)((char*)ws + (size_t)((epoch + 1u) & 1u) * HDR_BYTES);
     u64* region = (u64*)((char*)ws + HDR_SLOTS * HDR_BYTES + (size_t)((epoch >> 2) % FWD_REGIONS) * fwd3_region_bytes(H));
-    P3 p{gates, whh, y, c, region, hdr, hdr_next, B, T, H, ND, H / 16, NS, BS, allow_local3(), poll_delay3(false), epoch, nullptr, 0u};
+    P3 p{gates, whh, y, c, region, hdr, hdr_next, B, T, H, ND, H / 16, NS, BS, xcd_local_allowed(), poll_delay3(false), epoch, nullptr, 0u};
     const int nks = (H + 31) / 32;
     FWD3_CASE(1) FWD3_CASE(2) FWD3_CASE(4) FWD3_CASE(6) FWD3_CASE(8) FWD3_CASE(10) FWD3_CASE(12) FWD3_CASE(16)
     return 1;
@@ -787,7 +783,7 @@ int lstm_bwd_persistent3(unsigned short* gates, const float* whh, const unsigned
     const size_t rbytes = bwd3_region_bytes(H, BS);
     if (rbytes >= (1ull << 31)) return 1;
     P3 p{gates, whh, const_cast<unsigned short*>(dy), const_cast<float*>(c), region, hdr, hdr_next, B, T, H, ND, H / 16, NS, BS,
-         allow_local3(), poll_delay3(true), epoch, (unsigned char*)region + rbytes - bwd3_dump_bytes(H), (unsigned)rbytes};
+         xcd_local_allowed(), poll_delay3(true), epoch, (unsigned char*)region + rbytes - bwd3_dump_bytes(H), (unsigned)rbytes};
     const int nto = (p.P + 3) / 4;
     BWD3_CASE(1) BWD3_CASE(2) BWD3_CASE(3) BWD3_CASE(4) BWD3_CASE(5) BWD3_CASE(6) BWD3_CASE(8)
     return 1;
