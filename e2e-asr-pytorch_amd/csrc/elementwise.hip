@@ -128,8 +128,10 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(const float* __restric
     float s = 0.f;
     for (int v = lane; v < V; v += 64) s += expf(xr[v] - m);
     s = wave_sum(s);
-    const float lse = m + logf(s);
-    for (int v = lane; v < V; v += 64) out[row * V + v] = xr[v] - lse;
+    // (x - m) - log(sum), not x - (m + log(sum)): the latter rounds at ulp(|m|), which a common offset of the logits makes
+    // arbitrarily coarse against the result (tests/test_hip_glue_kernels_vs_float64.py, the 'x1+100' cases)
+    const float ls = logf(s);
+    for (int v = lane; v < V; v += 64) out[row * V + v] = (xr[v] - m) - ls;
 }
 
 __global__ __launch_bounds__(256) void logsoftmax_relu_bwd_kernel(const float* __restrict__ g, const float* __restrict__ lp,
@@ -167,28 +169,42 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
 }
 
-// dx for LayerNorm(+optional ReLU); dw/db accumulated with atomics into (n) buffers.
+// dx for LayerNorm(+optional ReLU); dw/db accumulated with atomics into (n) buffers.  The four rows of a workgroup are summed in
+// LDS first and added with ONE atomic per column: a quarter of the atomics, and a quarter of the fp32 roundings in the chain
+// that builds dw[i] / db[i] (one atomic per row measured 2.5x torch's float32 error, tests/test_hip_glue_kernels_vs_float64.py).
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ w, const float* __restrict__ b,
                                                             const float* __restrict__ stats, float* __restrict__ dx,
                                                             float* __restrict__ dw, float* __restrict__ db,
                                                             long R, int n, int relu) {
-    const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= R) return;
-    const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+    __shared__ float s_dw[4][64], s_db[4][64];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long row = blockIdx.x * 4L + wv;
+    const bool live = row < R;                                  // a wave past the last row only takes part in the barriers
+    const float mean = live ? stats[2 * row] : 0.f, rstd = live ? stats[2 * row + 1] : 0.f;
     const float* xr = x + row * n;
     const float* gr = dy + row * n;
     float s1 = 0.f, s2 = 0.f;
-    for (int i = lane; i < n; i += 64) {
-        const float xh = (xr[i] - mean) * rstd;
-        float g = gr[i];
-        if (relu && (xh * w[i] + b[i]) <= 0.f) g = 0.f;
-        const float gw = g * w[i];
-        s1 += gw; s2 += gw * xh;
-        atomicAdd(dw + i, g * xh);
-        atomicAdd(db + i, g);
+    for (int i0 = 0; i0 < n; i0 += 64) {                        // the same trip count for every wave of the workgroup
+        const int i = i0 + lane;
+        float pw = 0.f, pb = 0.f;
+        if (live && i < n) {
+            const float xh = (xr[i] - mean) * rstd;
+            float g = gr[i];
+            if (relu && (xh * w[i] + b[i]) <= 0.f) g = 0.f;
+            const float gw = g * w[i];
+            s1 += gw; s2 += gw * xh;
+            pw = g * xh; pb = g;
+        }
+        s_dw[wv][lane] = pw; s_db[wv][lane] = pb;
+        __syncthreads();
+        if (i < n) {
+            if (wv == 0) atomicAdd(dw + i, (s_dw[0][lane] + s_dw[1][lane]) + (s_dw[2][lane] + s_dw[3][lane]));
+            if (wv == 1) atomicAdd(db + i, (s_db[0][lane] + s_db[1][lane]) + (s_db[2][lane] + s_db[3][lane]));
+        }
+        __syncthreads();
     }
+    if (!live) return;
     s1 = wave_sum(s1) / n; s2 = wave_sum(s2) / n;
     for (int i = lane; i < n; i += 64) {
         const float xh = (xr[i] - mean) * rstd;

@@ -118,6 +118,23 @@ __global__ __launch_bounds__(256) void loc_energy_bwd_kernel(const float* __rest
     if (threadIdx.x == 0) atomicAdd(dbg, gsum);
 }
 
+// sum over the taps j0 <= j < j1 of w[j] * x[j * ldx] with four independent accumulators; the callers add one such partial sum
+// per filter row, so a chain of additions has (2 Ks + 1) / 4 + NH (or Kn) terms instead of (2 Ks + 1) * NH: at 101 taps and
+// ten filters the single accumulator measured 3.9x torch's float32 error (tests/test_hip_variant_kernels_vs_float64.py).
+// x + j * ldx is only formed for the taps inside [j0, j1), which the callers clamp to the frames that exist.
+__device__ __forceinline__ float taps_sum(const float* __restrict__ w, const float* x, long ldx, int j0, int j1) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int j = j0;
+    for (; j + 4 <= j1; j += 4) {
+        a0 += w[j] * x[(long)j * ldx];
+        a1 += w[j + 1] * x[(long)(j + 1) * ldx];
+        a2 += w[j + 2] * x[(long)(j + 2) * ldx];
+        a3 += w[j + 3] * x[(long)(j + 3) * ldx];
+    }
+    for (; j < j1; ++j) a0 += w[j] * x[(long)j * ldx];
+    return (a0 + a1) + (a2 + a3);
+}
+
 // out[b, t, k] = sum_h sum_j W[k, h, j] prev[b, h, t + j - Ks]       (nn.Conv1d(NH, Kn, 2 Ks + 1, padding Ks, bias False), then transpose)
 __global__ void loc_conv_fwd_kernel(const float* __restrict__ prev, const float* __restrict__ W, int B, int NH, int T, int Kn, int Ks,
                                     float* __restrict__ out) {
@@ -130,7 +147,7 @@ __global__ void loc_conv_fwd_kernel(const float* __restrict__ prev, const float*
         const float* p = prev + ((long)b * NH + h) * T;
         const float* w = W + ((long)k * NH + h) * taps;
         const int j0 = max(0, Ks - t), j1 = min(taps, T + Ks - t);
-        for (int j = j0; j < j1; ++j) acc += w[j] * p[t + j - Ks];
+        acc += taps_sum(w, p + (t - Ks), 1, j0, j1);
     }
     out[i] = acc;
 }
@@ -145,7 +162,7 @@ __global__ void loc_conv_bwd_data_kernel(const float* __restrict__ dout, const f
     for (int k = 0; k < Kn; ++k) {
         const float* w = W + ((long)k * NH + h) * taps;
         const int j0 = max(0, tp + Ks - (T - 1)), j1 = min(taps, tp + Ks + 1);
-        for (int j = j0; j < j1; ++j) acc += w[j] * dout[((long)b * T + (tp - j + Ks)) * Kn + k];
+        acc += taps_sum(w, dout + ((long)b * T + (tp + Ks)) * Kn + k, -(long)Kn, j0, j1);
     }
     dprev[i] = acc;
 }
@@ -229,6 +246,26 @@ __global__ void gru_cell_bwd_kernel(const float* __restrict__ saved, const float
     dh_prev[i] = g * z;
 }
 
+// sum_i a[i] * b[i * ldb] in blocks of 64 terms with four independent accumulators: no chain of additions is longer than
+// 16 + n / 64 terms (a single accumulator over 3H = 6144 terms measured 13x torch's float32 error in the gradients,
+// tests/test_hip_variant_kernels_vs_float64.py), and the loads of a block are independent of each other
+__device__ __forceinline__ float dot_blocked(const float* __restrict__ a, const float* __restrict__ b, long ldb, int n, float acc) {
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i1 = min(n, i0 + 64);
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int i = i0;
+        for (; i + 4 <= i1; i += 4) {
+            a0 += a[i] * b[(long)i * ldb];
+            a1 += a[i + 1] * b[(long)(i + 1) * ldb];
+            a2 += a[i + 2] * b[(long)(i + 2) * ldb];
+            a3 += a[i + 3] * b[(long)(i + 3) * ldb];
+        }
+        for (; i < i1; ++i) a0 += a[i] * b[(long)i * ldb];
+        acc += (a0 + a1) + (a2 + a3);
+    }
+    return acc;
+}
+
 // ---- nn.GRU over a whole (padded) sequence: one workgroup per (batch row, direction), h in LDS, W_hh^T streamed from L2 ----------
 // gi (B, T, ND, 3H) = x W_ih^T + b_ih (asr_gemm); whhT (ND, H, 3H) = weight_hh transposed; bhh (ND, 3H)
 // y (B, T, ND*H); saved (B, T, ND, 4H) = r | z | n | gh_n (bias included)
@@ -244,9 +281,7 @@ __global__ __launch_bounds__(1024) void gru_seq_fwd_kernel(const float* __restri
     for (int s = 0; s < T; ++s) {
         const int t = dir ? (T - 1 - s) : s;
         for (int row = tid; row < G; row += blockDim.x) {
-            float acc = bhh[dir * G + row];
-            for (int k = 0; k < Hd; ++k) acc += W[(long)k * G + row] * s_h[k];
-            s_gh[row] = acc;
+            s_gh[row] = dot_blocked(s_h, W + row, G, Hd, bhh[dir * G + row]);
         }
         __syncthreads();
         const float* gi_ = gi + (((long)b * T + t) * ND + dir) * G;
@@ -300,9 +335,7 @@ __global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(const float* __restri
         }
         __syncthreads();
         for (int k = tid, it = 0; k < Hd; k += blockDim.x, ++it) {
-            float acc = carry[it];
-            for (int row = 0; row < G; ++row) acc += s_dg[row] * W[(long)row * Hd + k];
-            carry[it] = acc;
+            carry[it] = dot_blocked(s_dg, W + k, Hd, G, carry[it]);
         }
         __syncthreads();
         for (int k = tid, it = 0; k < Hd; k += blockDim.x, ++it) s_m[k] = carry[it];
