@@ -5,7 +5,9 @@ prefix-score launch, one LM step and ONE bookkeeping kernel (asr_beam_step: fusi
 for all U x beam rows; nothing is copied to the host until the search has ended.  `forward_host` is the first
 implementation (score table on the host each step), kept as a cross-check for the shipped decoder.  Models the decode
 kernels do not cover (GRU, dot / multi-head attention, v_proj, deep LSTM) take the step of src/decode_variants.py; both
-searches share the bookkeeping of _BeamBook."""
+searches share the bookkeeping of _BeamBook.  A CTC-only model (ctc_weight = 1: no attention decoder) is decoded by a CTC
+prefix beam search instead, the whole search of all utterances in ONE launch (asr_ctc_beam_search, csrc/ctc_decode.hip); the
+reference has no counterpart (`# ToDo : implement pure ctc decode`)."""
 import ctypes
 import math
 
@@ -58,13 +60,40 @@ class Hypothesis(object):
         return None, new_hyps
 
 
+class CTCHypothesis(object):
+    """One result of the CTC prefix beam search: the collapsed token sequence (a trailing <eos> included when the model
+    emits one) and its log-probability.  CTC gives a sequence no per-token scores, so avgScore() IS the sequence
+    log-probability (not divided by the length) - the quantity the search ranks by."""
+
+    def __init__(self, output_seq, score):
+        self.output_seq, self.score = output_seq, score
+
+    def avgScore(self):
+        return self.score
+
+    @property
+    def outIndex(self):
+        return [int(i) for i in self.output_seq]
+
+
 class BeamDecoder(nn.Module):
     def __init__(self, asr, emb_decoder, beam_size, min_len_ratio, max_len_ratio, lm_path='', lm_config='', lm_weight=0.0,
                  ctc_weight=0.0):
         super().__init__()
         assert emb_decoder is None, 'embedding-fusion decoding is outside the HIP path'
         self.beam_size, self.min_len_ratio, self.max_len_ratio, self.asr = beam_size, min_len_ratio, max_len_ratio, asr
-        assert self.asr.enable_att
+        self.ctc_only = not self.asr.enable_att
+        if self.ctc_only:
+            # no attention decoder to search with: CTC prefix beam search.  Nothing to mix the CTC score with (ctc_weight is
+            # ignored), and the frames bound the length (the length ratios are ignored)
+            assert self.asr.ctc_weight > 0, 'ASR was not trained with CTC decoder'
+            if lm_weight > 0:
+                raise NotImplementedError('RNN-LM fusion for CTC-only decoding is not built')
+            if not 1 <= beam_size <= H.CTC_BEAM_MAX:
+                raise ValueError('CTC-only decoding takes a beam of 1..%d, got %d' % (H.CTC_BEAM_MAX, beam_size))
+            self.fast, self.apply_ctc, self.apply_lm = False, True, False
+            self.ctc_cand = min(self.asr.vocab_size - 1, int(CTC_BEAM_RATIO * self.beam_size))
+            return
         # the decode kernels of the shipped decoder (asr_att_decoder_step) cover an LSTM of <= MAX_DEC_LAYERS layers with
         # location-aware single-head attention and no value projection, whatever its dropout (inactive in eval); every other
         # model runs the variant search of src/decode_variants.py
@@ -84,9 +113,15 @@ class BeamDecoder(nn.Module):
                     self.lm.load_state_dict(torch.load(lm_path, map_location='cpu')['model'])
 
     def set_lm(self, lm, weight):
+        if self.ctc_only:
+            raise NotImplementedError('RNN-LM fusion for CTC-only decoding is not built')
         self.apply_lm, self.lm_w, self.lm = True, weight, lm
 
     def create_msg(self):
+        if self.ctc_only:
+            return ['Decode spec| CTC-only model: CTC prefix beam search\t| Beam size = {}\t| Tokens extended per frame = {}'.format(
+                        self.beam_size, self.ctc_cand),
+                    '           |Min/Max len ratio, ctc_weight are ignored (the frames bound the length; nothing to mix with)']
         msg = ['Decode spec| Beam size = {}\t| Min/Max len ratio = {}/{}'.format(self.beam_size, self.min_len_ratio, self.max_len_ratio)]
         if self.apply_ctc:
             msg.append('           |Joint CTC decoding enabled \t| weight = {:.2f}\t'.format(self.ctc_w))
@@ -125,6 +160,8 @@ class BeamDecoder(nn.Module):
     def forward(self, audio_feature, feature_len):
         """audio_feature (U,T,D) zero-padded, feature_len (U).  U == 1: the reference's return value (list of <= beam
         Hypothesis, best first); U > 1: a list of such lists.  No device-to-host copy inside the search loop."""
+        if self.ctc_only:
+            return self._forward_ctc(audio_feature, feature_len)
         U = audio_feature.shape[0]
         flens = [int(x) for x in feature_len.reshape(-1).tolist()]
         max_lens = [int(math.ceil(f * self.max_len_ratio)) for f in flens]
@@ -143,6 +180,23 @@ class BeamDecoder(nn.Module):
             if (t & 15) == 15 and book.all_done():          # every 16 positions: stop early when every search has ended
                 break
         return book.readout()
+
+    def _forward_ctc(self, audio_feature, feature_len):
+        """CTC-only model: one asr_ctc_beam_search launch runs every frame of every utterance; the results are read back
+        once, after it.  Returns CTCHypothesis objects in the shape of forward's contract."""
+        _, _, tlen, ctc_lp = self._encode(audio_feature, feature_len)
+        U, Tp, V = ctc_lp.shape
+        K, dev = self.beam_size, ctc_lp.device
+        toks = torch.empty((U, K, Tp), dtype=torch.int32, device=dev)
+        lens, n = torch.empty((U, K), dtype=torch.int32, device=dev), torch.empty(U, dtype=torch.int32, device=dev)
+        score = torch.empty((U, K), dtype=torch.float32, device=dev)
+        nbytes = int(H.lib().asr_ctc_beam_search_workspace_bytes(U, Tp, K))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        H.call('asr_ctc_beam_search', H.ptr(ctc_lp), H.ptr(tlen), U, Tp, V, K, self.ctc_cand, Tp, H.ptr(toks), H.ptr(lens), H.ptr(score),
+               H.ptr(n), H.ptr(ws), nbytes, H.stream_ptr())
+        n_c, len_c, tok_c, sc_c = n.cpu(), lens.cpu(), toks.cpu(), score.cpu()
+        out = [[CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(sc_c[u, i])) for i in range(int(n_c[u]))] for u in range(U)]
+        return out[0] if U == 1 else out
 
     @torch.no_grad()
     def forward_host(self, audio_feature, feature_len):

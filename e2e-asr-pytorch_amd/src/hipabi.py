@@ -49,6 +49,7 @@ class BeamStep(ctypes.Structure):
 
 ATT_DOT, ATT_LOC = 0, 1
 BEAM_ATTEND_MAX_ROWS, BEAM_ATTEND_MAX_T = 16, 8192
+CTC_BEAM_MAX = 16                  # ASR_CTC_BEAM_MAX: widest beam of asr_ctc_beam_search
 
 
 class BeamAttend(ctypes.Structure):
@@ -137,6 +138,7 @@ SIGNATURES = {
     'asr_beam_attend': [ctypes.POINTER(BeamAttend), _vp],
     'asr_ctc_prefix_init_batched': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'asr_ctc_prefix_score_batched': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    'asr_ctc_beam_search': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_gemm16': [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     'asr_lstm16_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, ctypes.c_uint, _i, _vp],
     'asr_lstm16_bwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, ctypes.c_uint, _i, _vp],
@@ -163,6 +165,7 @@ _RESTYPES = {
     'asr_lstm_plan': (ctypes.c_int, [_i, _i, _i, _i, _i]),
     'asr_lstm16_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_ctc_loss_workspace_bytes': (_sz, [_i, _i, _i]),
+    'asr_ctc_beam_search_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_fbank_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_att_decoder_bwd_workspace_bytes': (_sz, [_P(DecDims)]),
     'asr_att_decoder_fwd_work_bytes': (_sz, [_P(DecDims)]),

@@ -533,6 +533,25 @@ int asr_ctc_prefix_score_batched(const float* logp, const int* tlen, const float
                                  const int* prefix_len, const int* last_token, float* psi, float* r_out,
                                  int N, int C, int Tmax, int V, int rows_per_utt, asr_stream_t stream);
 
+/* CTC prefix beam search of a CTC-only model (csrc/ctc_decode.hip): the decoder the reference does not have (`# ToDo :
+ * implement pure ctc decode`, src/decode.py:26), behind the BeamDecoder.forward contract (src/decode.py:65-183: at most `beam`
+ * hypotheses per utterance, best first).  ONE launch for all U utterances and all their frames, one workgroup per utterance,
+ * the beam in LDS; blank = 0.  logp (U,Tmax,V) fp32 log-probabilities (the CTC head's output), tlen (U) valid frames: frames at
+ * and past tlen[u] are never read.  Per frame every beam prefix stays (blank / repeated last token) and is extended by every
+ * allowed non-blank token; an extension that is a beam member itself accumulates into that member; the K entries with the
+ * largest logaddexp(p_blank, p_nonblank) survive, ties to the smaller (parent slot, token), entries at -inf never.  cand = 0:
+ * every non-blank token extends; cand > 0: the `cand` tokens with the largest logp of the frame (ties: lower index).
+ * Outputs per utterance, best first: out_tokens (U,K,Lcap) collapsed token ids (0 behind the end), out_len (U,K),
+ * out_score (U,K) = log-probability of the token sequence under the pruned search (-inf in unused rows), out_n (U) = number of
+ * hypotheses (tlen[u] = 0: the empty one, score 0).  Lcap >= Tmax.  workspace: asr_ctc_beam_search_workspace_bytes(U,Tmax,K)
+ * (the prefix trie, 1 + K*Tmax nodes per utterance; need not be cleared).  Any V > 1, any Tmax > 0,
+ * 1 <= K <= ASR_CTC_BEAM_MAX; anything else returns ASR_E_ARG and launches nothing.  No language-model fusion. */
+#define ASR_CTC_BEAM_MAX 16
+size_t asr_ctc_beam_search_workspace_bytes(int U, int Tmax, int K);
+int asr_ctc_beam_search(const float* logp, const int* tlen, int U, int Tmax, int V, int K, int cand, int Lcap,
+                        int* out_tokens, int* out_len, float* out_score, int* out_n,
+                        void* workspace, size_t workspace_bytes, asr_stream_t stream);
+
 /* Beam-search attention of the model variants (csrc/decode_variants.hip; src/decode_variants.py): one output position of
  * BeamDecoder.forward's attention (src/decode.py:107-110 -> src/asr.py:331-364, ScaleDotAttention / LocationAwareAttention
  * src/module.py:1121-1189) for U utterances x rows_per_utt hypothesis rows (row r belongs to utterance u = r / rows_per_utt),

@@ -3,8 +3,11 @@ RNN-LM of config/librispeech_lm.yaml (4 x LSTM-1024, tied, random weights) with 
 U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Prints one JSON line.
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
        [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
+       [--ctc-only]
 The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one; --lm-module GRU
-fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one."""
+fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one.  --ctc-only decodes the config's
+model built with ctc_weight = 1 (no attention decoder, no LM) by the CTC prefix beam search (csrc/ctc_decode.hip) and also
+times the search launch alone on the encoded batch."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'e2e-asr-pytorch_amd')
@@ -21,18 +24,20 @@ ap.add_argument('--beam', type=int, default=8); ap.add_argument('--host', action
 ap.add_argument('--model-yaml', default=os.path.join(PKG, 'config', 'librispeech_asr.yaml'))
 ap.add_argument('--attention-mode'); ap.add_argument('--num-head', type=int); ap.add_argument('--decoder-module')
 ap.add_argument('--lm-module', choices=('LSTM', 'GRU'), default='LSTM')
+ap.add_argument('--ctc-only', action='store_true')
 a = ap.parse_args()
 torch.manual_seed(0)
 mc = yaml.safe_load(open(a.model_yaml))['model']
 if a.attention_mode: mc['attention']['mode'] = a.attention_mode
 if a.num_head: mc['attention']['num_head'] = a.num_head
 if a.decoder_module: mc['decoder']['module'] = a.decoder_module
+if a.ctc_only: mc['ctc_weight'] = 1
 model = ASR(160, 31, 1, prec=a.prec, **mc).cuda().eval()
 lmc = yaml.safe_load(open(os.path.join(PKG, 'config', 'librispeech_lm.yaml')))['model']
 lmc['module'] = a.lm_module
 lm = RNNLM(31, **lmc).cuda().eval()
 dec = BeamDecoder(model, None, beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio, ctc_weight=0.3)
-dec.set_lm(lm, 0.3)
+if not a.ctc_only: dec.set_lm(lm, 0.3)
 U, T = a.utts, a.frames
 feat = torch.rand(U, T, 160, device='cuda')
 flen = torch.full((U,), T, dtype=torch.int64, device='cuda')
@@ -49,6 +54,25 @@ torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / a.reps
 H.raise_if_aborted()
 n_hyp = len(out[0]) if (U > 1 or a.host) else len(out)
+if a.ctc_only:
+    # the search launch alone: the encoded batch is made once, the launch repeated between two events
+    _, _, tlen, lp = dec._encode(feat, flen)
+    Tp, K = lp.shape[1], a.beam
+    i32 = lambda *s_: torch.empty(s_, dtype=torch.int32, device='cuda')
+    toks, lens, n, score = i32(U, K, Tp), i32(U, K), i32(U), torch.empty(U, K, device='cuda')
+    nb = int(H.lib().asr_ctc_beam_search_workspace_bytes(U, Tp, K))
+    ws = torch.empty(nb, dtype=torch.uint8, device='cuda')
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for i in range(1 + 10):
+        if i == 1: ev[0].record()
+        H.call('asr_ctc_beam_search', H.ptr(lp), H.ptr(tlen), U, Tp, 31, K, dec.ctc_cand, Tp, H.ptr(toks), H.ptr(lens), H.ptr(score),
+               H.ptr(n), H.ptr(ws), nb, H.stream_ptr())
+    ev[1].record(); torch.cuda.synchronize()
+    print(json.dumps({'metric': 'CTC prefix beam search, CTC-only model of config 4', 'utterances_per_s': U / dt, 'ms_per_utterance': dt * 1e3 / U,
+                      'search_launch_ms': ev[0].elapsed_time(ev[1]) / 10, 'batch_utterances': U, 'frames': T, 'encoder_frames': Tp, 'beam': K,
+                      'tokens_extended_per_frame': dec.ctc_cand, 'hyps_first_utt': n_hyp, 'prec': a.prec,
+                      'first_hyp_len': len((out[0] if U > 1 else out)[0].outIndex)}))
+    sys.exit(0)
 print(json.dumps({'metric': 'beam-search decode, config 4', 'utterances_per_s': U / dt, 'ms_per_utterance': dt * 1e3 / U,
                   'decode_positions_per_s': U * steps / dt, 'batch_utterances': U, 'frames': T, 'max_positions': steps, 'beam': a.beam,
                   'ctc_weight': 0.3, 'lm': '4x1024 tied, %s' % a.lm_module, 'lm_weight': 0.3, 'path': 'host score table' if a.host else 'device beam step',
