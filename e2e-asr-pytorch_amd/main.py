@@ -21,12 +21,28 @@ parser.add_argument('--njobs', default=4, type=int)
 parser.add_argument('--cpu', action='store_true', help='not supported: the HIP path has no CPU fallback')
 parser.add_argument('--no-pin', action='store_true')
 parser.add_argument('--test', action='store_true')
+parser.add_argument('--align', action='store_true', help='forced alignment of the transcripts with the CTC head (bin/align_asr.py)')
 parser.add_argument('--no-msg', action='store_true')
 parser.add_argument('--lm', action='store_true')
 parser.add_argument('--amp', action='store_true', help='accepted for compatibility; precision is chosen by hip.prec in the YAML')
 parser.add_argument('--cuda', default=0, type=int)
 parser.add_argument('--deterministic', action='store_true')
 parser.add_argument('--upstream', default=None)
+
+
+def select_solver(paras):
+    """(Solver class, mode) the command line asks for."""
+    if paras.lm:
+        from bin.train_lm import Solver
+        return Solver, 'train'
+    if paras.align:
+        from bin.align_asr import Solver
+        return Solver, 'test'
+    if paras.test:
+        from bin.test_asr import Solver
+        return Solver, 'test'
+    from bin.train_asr import Solver
+    return Solver, 'train'
 
 
 def main():
@@ -43,15 +59,7 @@ def main():
     random.seed(paras.seed)
     np.random.seed(paras.seed)
     torch.manual_seed(paras.seed)
-    if paras.lm:
-        from bin.train_lm import Solver
-        mode = 'train'
-    elif paras.test:
-        from bin.test_asr import Solver
-        mode = 'test'
-    else:
-        from bin.train_asr import Solver
-        mode = 'train'
+    Solver, mode = select_solver(paras)
     solver = Solver(config, paras, mode)
     solver.load_data()
     solver.set_model()

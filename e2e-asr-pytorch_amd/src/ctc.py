@@ -1,5 +1,8 @@
 """CTC prefix scorer for joint decoding (reference src/ctc.py:4-108, Watanabe et al. Algo. 2) on the HIP path:
-states live on the device as (N,T,2) fp32, `score` evaluates N hypotheses x C candidates in one launch."""
+states live on the device as (N,T,2) fp32, `score` evaluates N hypotheses x C candidates in one launch.
+`ctc_forced_align` is the Viterbi alignment of known transcripts (asr_ctc_align; no reference counterpart)."""
+import collections
+
 import torch
 
 from src import hipabi as H
@@ -36,3 +39,29 @@ class CTCPrefixScore(object):
         psi, r = self.score([len(g)], [g[-1] if len(g) > 0 else 0], r_prev.unsqueeze(0),
                             torch.as_tensor(candidates).view(1, -1))
         return psi[0], r[0]
+
+
+CTCAlignment = collections.namedtuple('CTCAlignment', 'frame_token frame_pos tok_start tok_end tok_score score ok')
+
+
+def ctc_forced_align(logp, targets, input_len, target_len):
+    """Most probable CTC alignment of every row's target, one launch for the batch (asr_ctc_align, csrc/ctc_align.hip).
+    logp (B,T,V) fp32 log-probs, targets (B,L), input_len / target_len (B): device tensors.  Returns device tensors, nothing
+    is copied to the host: frame_token, frame_pos (B,T) int32; tok_start, tok_end (B,L) int32 (inclusive frames), tok_score
+    (B,L); score (B) and ok (B) int32 - the contract of include/asr_hip.h."""
+    dev = logp.device
+    logp = logp.contiguous().float()
+    B, T, V = logp.shape
+    targets = targets.to(dev, torch.int64).reshape(B, -1).contiguous()
+    L = targets.shape[1]
+    input_len = input_len.to(dev, torch.int64).contiguous()
+    target_len = target_len.to(dev, torch.int64).contiguous()
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = CTCAlignment(i32(B, T), i32(B, T), i32(B, L), i32(B, L), f32(B, L), f32(B), i32(B))
+    nbytes = int(H.lib().asr_ctc_align_workspace_bytes(B, T, L))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    H.call('asr_ctc_align', H.ptr(logp), H.ptr(targets), H.ptr(input_len), H.ptr(target_len), B, T, V, L,
+           H.ptr(out.frame_token), H.ptr(out.frame_pos), H.ptr(out.tok_start), H.ptr(out.tok_end), H.ptr(out.tok_score),
+           H.ptr(out.score), H.ptr(out.ok), H.ptr(ws), nbytes, H.stream_ptr())
+    return out

@@ -24,6 +24,35 @@ CTC_BEAM_RATIO = 1.5
 LOG_ZERO = -10000000.0
 
 
+def encode_unpadded(asr, audio_feature, feature_len, with_ctc):
+    """Encoder (+ CTC log-probs when `with_ctc`) of every utterance on its own, unpadded - the reference decodes one
+    utterance at a time (src/decode.py:67) and a padded BiLSTM pass is not equivalent (the reverse direction would start
+    inside the padding) - written into zero-padded (U,T'max,.) tensors for a batched search or alignment.  Returns
+    (enc, enc_len int64 (U), tlen int32 (U), ctc log-probs or None)."""
+    dev = audio_feature.device
+    ctx = type('C', (), {'anchor': asr._anchor, 'prec': asr.prec, 'next_seed': lambda s: 0})()
+    U = audio_feature.shape[0]
+    encs, lens, ctcs = [], [], []
+    for u in range(U):
+        n = int(feature_len[u])
+        e, el = asr.encoder(audio_feature[u:u + 1, :n].float(), feature_len[u:u + 1].to(dev), ctx)
+        e = F_hip.to_f32(e)
+        encs.append(e[0])
+        lens.append(int(el[0]))
+        if with_ctc:
+            ctcs.append(F_hip.CTCHeadFn.apply(asr._anchor, e, asr.ctc_layer[0], asr.prec, False)[0])
+    Tp = max(e.shape[0] for e in encs)
+    enc = torch.zeros((U, Tp, encs[0].shape[1]), dtype=torch.float32, device=dev)
+    ctc = torch.zeros((U, Tp, asr.vocab_size), dtype=torch.float32, device=dev) if with_ctc else None
+    for u in range(U):
+        enc[u, :encs[u].shape[0]] = encs[u]
+        if ctc is not None:
+            ctc[u, :ctcs[u].shape[0]] = ctcs[u]
+    # the reference takes T' from the encoder OUTPUT (its masks / CTC scorer see every output frame of the unpadded pass)
+    tlen = torch.tensor([e.shape[0] for e in encs], dtype=torch.int32, device=dev)
+    return enc, torch.tensor(lens, dtype=torch.int64, device=dev), tlen, ctc
+
+
 class Hypothesis(object):
     """History of one partial transcript (reference src/decode.py:186-281); `row` = its row in the device state."""
 
@@ -130,31 +159,7 @@ class BeamDecoder(nn.Module):
         return msg
 
     def _encode(self, audio_feature, feature_len):
-        """Encoder (+ CTC log-probs) of every utterance on its own, unpadded - the reference decodes one utterance at a
-        time (src/decode.py:67) and a padded BiLSTM pass is not equivalent (the reverse direction would start inside the
-        padding) - written into zero-padded (U,T'max,.) tensors for the batched search."""
-        asr, dev = self.asr, audio_feature.device
-        ctx = type('C', (), {'anchor': asr._anchor, 'prec': asr.prec, 'next_seed': lambda s: 0})()
-        U = audio_feature.shape[0]
-        encs, lens, ctcs = [], [], []
-        for u in range(U):
-            n = int(feature_len[u])
-            e, el = asr.encoder(audio_feature[u:u + 1, :n].float(), feature_len[u:u + 1].to(dev), ctx)
-            e = F_hip.to_f32(e)
-            encs.append(e[0])
-            lens.append(int(el[0]))
-            if self.apply_ctc:
-                ctcs.append(F_hip.CTCHeadFn.apply(asr._anchor, e, asr.ctc_layer[0], asr.prec, False)[0])
-        Tp = max(e.shape[0] for e in encs)
-        enc = torch.zeros((U, Tp, encs[0].shape[1]), dtype=torch.float32, device=dev)
-        ctc = torch.zeros((U, Tp, asr.vocab_size), dtype=torch.float32, device=dev) if self.apply_ctc else None
-        for u in range(U):
-            enc[u, :encs[u].shape[0]] = encs[u]
-            if ctc is not None:
-                ctc[u, :ctcs[u].shape[0]] = ctcs[u]
-        # the reference takes T' from the encoder OUTPUT (its masks / CTC scorer see every output frame of the unpadded pass)
-        tlen = torch.tensor([e.shape[0] for e in encs], dtype=torch.int32, device=dev)
-        return enc, torch.tensor(lens, dtype=torch.int64, device=dev), tlen, ctc
+        return encode_unpadded(self.asr, audio_feature, feature_len, self.apply_ctc)
 
     @torch.no_grad()
     def forward(self, audio_feature, feature_len):

@@ -139,6 +139,7 @@ SIGNATURES = {
     'asr_ctc_prefix_init_batched': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'asr_ctc_prefix_score_batched': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'asr_ctc_beam_search': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    'asr_ctc_align': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_gemm16': [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     'asr_lstm16_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, ctypes.c_uint, _i, _vp],
     'asr_lstm16_bwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, ctypes.c_uint, _i, _vp],
@@ -166,6 +167,7 @@ _RESTYPES = {
     'asr_lstm16_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_ctc_loss_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_beam_search_workspace_bytes': (_sz, [_i, _i, _i]),
+    'asr_ctc_align_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_fbank_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_att_decoder_bwd_workspace_bytes': (_sz, [_P(DecDims)]),
     'asr_att_decoder_fwd_work_bytes': (_sz, [_P(DecDims)]),

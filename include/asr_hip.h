@@ -552,6 +552,34 @@ int asr_ctc_beam_search(const float* logp, const int* tlen, int U, int Tmax, int
                         int* out_tokens, int* out_len, float* out_score, int* out_n,
                         void* workspace, size_t workspace_bytes, asr_stream_t stream);
 
+/* CTC forced alignment (csrc/ctc_align.hip): the most probable alignment (Viterbi) of a KNOWN transcript to the CTC
+ * log-probabilities - token and word timestamps, cutting long recordings, finding bad transcripts by their score.  No reference
+ * counterpart.  ONE launch for all B utterances, one workgroup per utterance, one thread per lattice state; nothing is copied
+ * to the host.  logp (B,T,V) fp32 log-probabilities, batch-major like asr_ctc_loss (the `ctc_output` of ASR.forward); targets
+ * (B,L) padded; input_len, target_len (B), clamped to 0..T and 0..L: frames at and past input_len[b] and targets at and past
+ * target_len[b] are never read.  Lattice of the loss, l' = (0, y1, 0, ..., yL, 0), S = 2L+1 states, blank = 0:
+ *   d[t][s] = logp[t][l'_s] + max(d[t-1][s], d[t-1][s-1], d[t-1][s-2])     (s-2 only when l'_s != 0 and l'_s != l'_{s-2})
+ * from d[0][0] and d[0][1], ending at the better of d[Tb-1][S-1] and d[Tb-1][S-2]; all fp32.
+ * Tie rules (deterministic): among predecessors a tie goes to the smaller move - stay, then s-1, then s-2; at the end a tie
+ * goes to S-1; -inf never wins over a finite value.  A row whose end value is -inf (too few frames for the target, or every
+ * alignment runs through a -inf entry), a row with a target token outside 1..V-1, and a row with no frames and a non-empty
+ * target have no alignment: ok = 0.  A row with no frames and an empty target is aligned (ok = 1, score 0).
+ * Outputs, all fully written by the call:
+ *   frame_token (B,T) token emitted at frame t, 0 = blank; -1 for t >= input_len[b] and in rows that are not ok
+ *   frame_pos   (B,T) index into the target of that token; -1 where frame_token <= 0
+ *   tok_start, tok_end (B,L) first / last frame of target token j, inclusive; -1 for j >= target_len[b] and in rows not ok
+ *   tok_score   (B,L) sum of logp[t, y_j] over the frames of token j, added in frame order; 0 where tok_start is -1
+ *   score       (B)   log-probability of the best alignment; -inf when not ok
+ *   ok          (B)   1 aligned, 0 no alignment exists
+ * L = 0 is legal (every frame blank; targets and the three tok_* pointers may then be NULL).  workspace:
+ * asr_ctc_align_workspace_bytes(B,T,L) bytes, 4-byte aligned, need not be cleared (the moves: 2 bits per frame and state).
+ * A null pointer, B, T <= 0, V <= 1, L < 0 or a too-small workspace return ASR_E_ARG, 2L+1 > 1024 states (the limit of
+ * asr_ctc_loss) returns ASR_E_UNSUPPORTED; either way nothing is launched and no output is touched. */
+size_t asr_ctc_align_workspace_bytes(int B, int T, int L);
+int asr_ctc_align(const float* logp, const int64_t* targets, const int64_t* input_len, const int64_t* target_len,
+                  int B, int T, int V, int L, int* frame_token, int* frame_pos, int* tok_start, int* tok_end,
+                  float* tok_score, float* score, int* ok, void* workspace, size_t workspace_bytes, asr_stream_t stream);
+
 /* Beam-search attention of the model variants (csrc/decode_variants.hip; src/decode_variants.py): one output position of
  * BeamDecoder.forward's attention (src/decode.py:107-110 -> src/asr.py:331-364, ScaleDotAttention / LocationAwareAttention
  * src/module.py:1121-1189) for U utterances x rows_per_utt hypothesis rows (row r belongs to utterance u = r / rows_per_utt),
