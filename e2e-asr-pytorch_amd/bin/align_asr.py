@@ -1,13 +1,15 @@
 """Forced-alignment Solver (no reference counterpart): loads the model like bin/test_asr.py, aligns the transcript of every
 utterance of each split with the model's CTC head and writes `<name>_<split>_align.tsv`: one line per token with its start
-and end in seconds."""
+and end in seconds.  --decode-batch N > 1 aligns N consecutive utterances per call through the batched encoder pass."""
 import os
 
 import torch
 
+from bin.batch_asr import decode_batch_of, pad_group, utterances
 from bin.test_asr import Solver as TestSolver
 from src.align import CTCAligner
 from src.asr import ASR
+from src.ragged import group_consecutive
 
 HEADER = 'idx\ttoken\tstart_s\tend_s\tscore'
 
@@ -28,7 +30,9 @@ class Solver(TestSolver):
         self.model = ASR(self.feat_dim, self.vocab_size, 1, prec=hip.get('prec', 'bf16'), **self.src_config['model']).to(self.device)
         self.load_ckpt()
         self.model.eval()
-        self.aligner = CTCAligner(self.model)               # no `decode` section needed: there is no search
+        self.decode_batch = decode_batch_of(self.paras)
+        self.aligner = CTCAligner(self.model, batch_encode=self.decode_batch > 1)      # no `decode` section needed: there is no search
+        self.verbose(self.aligner.create_msg())
         self.frame_shift_s = float(self.config['data']['audio'].get('frame_shift', 10)) / 1000.0
 
     def exec(self):
@@ -36,13 +40,11 @@ class Solver(TestSolver):
             path = os.path.join(self.paras.outdir, '{}_{}_align.tsv'.format(self.exp_name, name))
             with open(path, 'w') as f:
                 f.write(HEADER + '\n')
-                for names, feat, feat_len, txt in ds:
-                    if feat.dim() == 2:                      # waveform batch: GPU front-end (eval mode: no SpecAugment)
-                        with torch.no_grad():
-                            feat, feat_len = ds.audio_transform(feat.to(self.device), feat_len.to(self.device))
-                    txt = txt.to(self.device)
-                    aligned, rate = self.aligner(feat.to(self.device), feat_len.to(self.device), txt, torch.sum(txt != 0, dim=-1))
-                    for b, al in enumerate(aligned):
+                for group in group_consecutive(utterances(ds, self.device), self.decode_batch):
+                    feat, feat_len = pad_group([g[1] for g in group])
+                    txt, _ = pad_group([g[2].to(self.device) for g in group])
+                    aligned, rate = self.aligner(feat, feat_len, txt, torch.sum(txt != 0, dim=-1))
+                    for (name, _, _), al in zip(group, aligned):
                         toks = [self.tokenizer.decode([t]) or '<%d>' % t for t in al.tokens]      # <1>: the <eos> of the transcript
-                        f.write('\n'.join(format_alignment(names[b], toks, al, rate * self.frame_shift_s)) + '\n')
+                        f.write('\n'.join(format_alignment(name, toks, al, rate * self.frame_shift_s)) + '\n')
             self.verbose('Wrote {}'.format(path))

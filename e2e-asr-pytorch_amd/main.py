@@ -22,6 +22,9 @@ parser.add_argument('--cpu', action='store_true', help='not supported: the HIP p
 parser.add_argument('--no-pin', action='store_true')
 parser.add_argument('--test', action='store_true')
 parser.add_argument('--align', action='store_true', help='forced alignment of the transcripts with the CTC head (bin/align_asr.py)')
+parser.add_argument('--decode-batch', default=1, type=int,
+                    help='--test / --align: utterances per decoder call; N > 1 pads N consecutive utterances to the longest and runs the '
+                         'length-aware batched encoder pass (results agree with N = 1 to rounding)')
 parser.add_argument('--no-msg', action='store_true')
 parser.add_argument('--lm', action='store_true')
 parser.add_argument('--amp', action='store_true', help='accepted for compatibility; precision is chosen by hip.prec in the YAML')
@@ -39,6 +42,9 @@ def select_solver(paras):
         from bin.align_asr import Solver
         return Solver, 'test'
     if paras.test:
+        if paras.decode_batch > 1:
+            from bin.batch_asr import Solver
+            return Solver, 'test'
         from bin.test_asr import Solver
         return Solver, 'test'
     from bin.train_asr import Solver

@@ -17,6 +17,7 @@ from torch import nn
 
 from src import functions as F_hip
 from src import hipabi as H
+from src import ragged
 from src.ctc import CTCPrefixScore
 from src.lm import RNNLM
 
@@ -51,6 +52,47 @@ def encode_unpadded(asr, audio_feature, feature_len, with_ctc):
     # the reference takes T' from the encoder OUTPUT (its masks / CTC scorer see every output frame of the unpadded pass)
     tlen = torch.tensor([e.shape[0] for e in encs], dtype=torch.int32, device=dev)
     return enc, torch.tensor(lens, dtype=torch.int64, device=dev), tlen, ctc
+
+
+@torch.no_grad()
+def encode_batched(asr, audio_feature, feature_len, with_ctc):
+    """encode_unpadded's result - same return contract, padding rows of enc and ctc exactly 0 - from ONE pass of every
+    encoder layer over the padded batch (src/ragged.py: the data is aligned per row, the recurrence launches are unchanged)
+    and one of the CTC head.  Agrees with encode_unpadded to rounding, not bit for bit.  The caller's feature padding is never
+    used.  More utterances than the recurrence takes at once (ragged.max_batch) go in chunks of that size; a model the pass
+    does not cover (ragged.ineligible_reason: GRU layers, a vgg front-end) is encoded by encode_unpadded."""
+    if ragged.ineligible_reason(asr) is not None:
+        return encode_unpadded(asr, audio_feature, feature_len, with_ctc)
+    dev = audio_feature.device
+    flen = [int(x) for x in feature_len.reshape(-1).tolist()]
+    U, cap = audio_feature.shape[0], ragged.max_batch(asr)
+    parts = []
+    for u0 in range(0, U, cap):
+        fl = flen[u0:u0 + cap]
+        parts.append(ragged.encode_chunk(asr, audio_feature[u0:u0 + cap, :max(fl)], fl, with_ctc))
+    tl = [n for p in parts for n in p[1]]
+    enc_len = torch.tensor([n for p in parts for n in p[2]], dtype=torch.int64, device=dev)
+    tlen = torch.tensor(tl, dtype=torch.int32, device=dev)
+    if len(parts) == 1:
+        return parts[0][0], enc_len, tlen, parts[0][3]
+    Tp = max(tl)
+    enc = torch.zeros((U, Tp, parts[0][0].shape[2]), dtype=torch.float32, device=dev)
+    ctc = torch.zeros((U, Tp, asr.vocab_size), dtype=torch.float32, device=dev) if with_ctc else None
+    for i, p in enumerate(parts):
+        enc[i * cap:i * cap + p[0].shape[0], :p[0].shape[1]] = p[0]
+        if with_ctc:
+            ctc[i * cap:i * cap + p[3].shape[0], :p[3].shape[1]] = p[3]
+    return enc, enc_len, tlen, ctc
+
+
+def encoder_pass_msg(asr, batch_encode):
+    """The line of create_msg that says which encoder pass a decoder / aligner uses."""
+    if not batch_encode:
+        return '           |Encoder pass: one utterance at a time, unpadded'
+    why = ragged.ineligible_reason(asr)
+    if why is not None:
+        return '           |Encoder pass: batch_encode asked for, but fell back to one utterance at a time ({})'.format(why)
+    return '           |Encoder pass: batched, length-aware (one pass per layer over the padded batch)'
 
 
 class Hypothesis(object):
@@ -107,9 +149,10 @@ class CTCHypothesis(object):
 
 class BeamDecoder(nn.Module):
     def __init__(self, asr, emb_decoder, beam_size, min_len_ratio, max_len_ratio, lm_path='', lm_config='', lm_weight=0.0,
-                 ctc_weight=0.0):
+                 ctc_weight=0.0, batch_encode=False):
         super().__init__()
         assert emb_decoder is None, 'embedding-fusion decoding is outside the HIP path'
+        self.batch_encode = bool(batch_encode)      # opt-in: the batched pass agrees with the per-utterance one to rounding only
         self.beam_size, self.min_len_ratio, self.max_len_ratio, self.asr = beam_size, min_len_ratio, max_len_ratio, asr
         self.ctc_only = not self.asr.enable_att
         if self.ctc_only:
@@ -150,16 +193,19 @@ class BeamDecoder(nn.Module):
         if self.ctc_only:
             return ['Decode spec| CTC-only model: CTC prefix beam search\t| Beam size = {}\t| Tokens extended per frame = {}'.format(
                         self.beam_size, self.ctc_cand),
-                    '           |Min/Max len ratio, ctc_weight are ignored (the frames bound the length; nothing to mix with)']
+                    '           |Min/Max len ratio, ctc_weight are ignored (the frames bound the length; nothing to mix with)',
+                    encoder_pass_msg(self.asr, self.batch_encode)]
         msg = ['Decode spec| Beam size = {}\t| Min/Max len ratio = {}/{}'.format(self.beam_size, self.min_len_ratio, self.max_len_ratio)]
         if self.apply_ctc:
             msg.append('           |Joint CTC decoding enabled \t| weight = {:.2f}\t'.format(self.ctc_w))
         if self.apply_lm:
             msg.append('           |Joint LM decoding enabled \t| weight = {:.2f}'.format(self.lm_w))
+        msg.append(encoder_pass_msg(self.asr, self.batch_encode))
         return msg
 
     def _encode(self, audio_feature, feature_len):
-        return encode_unpadded(self.asr, audio_feature, feature_len, self.apply_ctc)
+        encode = encode_batched if self.batch_encode else encode_unpadded
+        return encode(self.asr, audio_feature, feature_len, self.apply_ctc)
 
     @torch.no_grad()
     def forward(self, audio_feature, feature_len):

@@ -157,6 +157,30 @@ int asr_dropout_downsample_bwd(const float* dz, float* dy, int B, int T, int D, 
                                float p, uint64_t seed, asr_stream_t stream);
 int asr_dropout_mask(float* mask, long n, float p, uint64_t seed, asr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ragged batch through the unchanged recurrence launches (csrc/ragged.hip, src/ragged.py): inference on a padded batch
+ * whose row b holds lens[b] valid frames (int64 on the device, clamped to [0,T] there).  Pure copies, bit-exact;
+ * elem_bytes = 4 (fp32 layouts) or 2 (bf16 layouts); out of place (src != dst); no allocation, no synchronisation.
+ *   asr_ragged_align  : gates (B,T,ND,W) -> dst of the same shape, W = 4H contiguous elements per (b,t,direction) in
+ *                       both storage modes.  dst[b,t,0] = src[b,t,0] for t < n, dst[b,t,1] = src[b,t-(T-n),1] for
+ *                       t >= T-n (the reverse walk then STARTS on the row's last valid frame), zeros elsewhere; source rows
+ *                       at t >= n are never read.
+ *   asr_ragged_unalign: y -> z with direction 1 shifted back and the layer's time down-sampling taken in the same pass.
+ *                       y[b,t,d*H+j] is read at src[src_off + b*src_bstride + t*ND*H + d*H + j] (elements; the
+ *                       time-padded y16 (B,T+2,ND*H) is src_bstride = (T+2)*ND*H, src_off = ND*H).  With
+ *                       s_d = (d == 1 ? T-n : 0):
+ *                         style 0 'drop'  : z (B,T2,ND*H),      z[b,t2,d*H+j]        = y[b, t2*rate + s_d, d*H+j]
+ *                         style 1 'concat': z (B,T2,rate*ND*H), z[b,t2,i*ND*H+d*H+j] = y[b, t2*rate+i + s_d, d*H+j]
+ *                       for t2 < ceil(n/rate) resp. n/rate (the frames the unpadded pass produces); every other row of z
+ *                       is exactly 0.  ND = 1 shifts nothing and still zeroes the padding (with rate = 1: a masked copy).
+ * Any extent is accepted: 16-byte accesses when W resp. H, the strides and the addresses allow them, element-wise else.
+ * Null pointers, src == dst, bad dims / rate / style / elem_bytes or a batch stride that cannot hold T frames behind
+ * src_off return ASR_E_ARG; B*T resp. B*T2 >= 2^23 rows returns ASR_E_UNSUPPORTED; nothing is launched then. */
+int asr_ragged_align(const void* src, void* dst, const int64_t* lens, int B, int T, int ND, int W, int elem_bytes,
+                     asr_stream_t stream);
+int asr_ragged_unalign(const void* src, long src_bstride, long src_off, void* dst, const int64_t* lens, int B, int T,
+                       int ND, int H, int T2, int rate, int style, int elem_bytes, asr_stream_t stream);
+
 /* dpre = dout * act'(out) for act in {TANH, RELU} (autograd of torch.tanh / nn.ReLU on the path). */
 int asr_act_bwd(const float* dout, const float* out, float* dpre, long n, int act, asr_stream_t stream);
 /* out[j] += sum_i A[i*lda + j]  (bias gradients). */

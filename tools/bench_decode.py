@@ -3,11 +3,14 @@ RNN-LM of config/librispeech_lm.yaml (4 x LSTM-1024, tied, random weights) with 
 U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Prints one JSON line.
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
        [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
-       [--ctc-only]
+       [--ctc-only] [--batch-encode] [--lengths equal|librispeech]
 The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one; --lm-module GRU
 fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one.  --ctc-only decodes the config's
 model built with ctc_weight = 1 (no attention decoder, no LM) by the CTC prefix beam search (csrc/ctc_decode.hip) and also
-times the search launch alone on the encoded batch."""
+times the search launch alone on the encoded batch.  --batch-encode measures, in the same process, the encoder pass alone and
+the whole decode with the per-utterance encoder pass (the default) and with the length-aware batched one
+(BeamDecoder(batch_encode=True), src/ragged.py): one warm-up each, then the median of --reps runs.  --lengths librispeech
+draws the U lengths from SURVEY 8d's length model clip(N(1270,480),150,2450) instead of --frames for every utterance."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'e2e-asr-pytorch_amd')
@@ -25,6 +28,7 @@ ap.add_argument('--model-yaml', default=os.path.join(PKG, 'config', 'librispeech
 ap.add_argument('--attention-mode'); ap.add_argument('--num-head', type=int); ap.add_argument('--decoder-module')
 ap.add_argument('--lm-module', choices=('LSTM', 'GRU'), default='LSTM')
 ap.add_argument('--ctc-only', action='store_true')
+ap.add_argument('--batch-encode', action='store_true'); ap.add_argument('--lengths', choices=('equal', 'librispeech'), default='equal')
 a = ap.parse_args()
 torch.manual_seed(0)
 mc = yaml.safe_load(open(a.model_yaml))['model']
@@ -41,7 +45,36 @@ if not a.ctc_only: dec.set_lm(lm, 0.3)
 U, T = a.utts, a.frames
 feat = torch.rand(U, T, 160, device='cuda')
 flen = torch.full((U,), T, dtype=torch.int64, device='cuda')
+if a.lengths == 'librispeech':
+    import numpy as np
+    ln = np.clip(np.random.RandomState(1234).normal(1270, 480, U), 150, 2450).astype(np.int64)
+    T = int(ln.max())
+    feat, flen = torch.rand(U, T, 160, device='cuda'), torch.from_numpy(ln).cuda()
+    for u in range(U):
+        feat[u, int(ln[u]):] = 0
 steps = int(-(-T * a.max_len_ratio // 1))
+if a.batch_encode:
+    import statistics
+    dec_b = BeamDecoder(model, None, beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio, ctc_weight=0.3, batch_encode=True)
+    if not a.ctc_only: dec_b.set_lm(lm, 0.3)
+    def median_ms(fn):
+        fn(); torch.cuda.synchronize()                # warm-up: workspaces, packed weights, plans
+        ts = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter(); fn(); torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts)
+    res = {'metric': 'encoder pass per utterance vs batched, %s' % ('CTC-only model of config 4' if a.ctc_only else 'config 4'),
+           'batch_utterances': U, 'lengths': a.lengths, 'frames': flen.tolist() if a.lengths != 'equal' else T, 'beam': a.beam,
+           'prec': a.prec, 'reps': a.reps}
+    for name, d in (('per_utterance', dec), ('batched', dec_b)):
+        enc_ms = median_ms(lambda: d._encode(feat, flen))
+        dec_ms = median_ms(lambda: d(feat, flen))
+        res[name] = {'encode_ms': enc_ms, 'decode_ms': dec_ms, 'utterances_per_s': U * 1e3 / dec_ms}
+    H.raise_if_aborted()
+    res['encode_speedup'] = res['per_utterance']['encode_ms'] / res['batched']['encode_ms']
+    res['decode_speedup'] = res['per_utterance']['decode_ms'] / res['batched']['decode_ms']
+    print(json.dumps(res))
+    sys.exit(0)
 def run():
     if a.host:
         return [dec.forward_host(feat[u:u + 1], flen[u:u + 1]) for u in range(U)]
