@@ -1,4 +1,4 @@
-// Inter-workgroup hand-off primitives of the persistent kernels (lstm_persist2.hip, lstm_persist3.hip, decoder_persist.hip,
+// Inter-workgroup hand-off primitives of the persistent kernels (lstm_persist*.hip, decoder_persist.hip,
 // decoder_stream.hip; core.hip scrubs their work areas): data-tagged 8-byte granules, 16-byte polling sweeps, XCD placement
 // consensus.  See cdna_hip_programming.md G16 form R2 and DESIGN.md 4.2.  Everything here is `static` per translation unit.
 #pragma once

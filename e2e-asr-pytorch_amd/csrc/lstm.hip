@@ -9,6 +9,7 @@
 // tensor y and c_{t-1} from the saved cell states, so there is no hidden state besides the outputs.
 #include "common.h"
 #include <stdlib.h>
+#include "lstm_plan.h"
 
 namespace {
 
@@ -145,19 +146,6 @@ __global__ void transpose_whh_kernel(const float* __restrict__ w, float* __restr
 
 }  // namespace
 
-// lstm_persist.hip
-int lstm_fwd_persistent(float* gates, const float* whh, const float* bias2, float* y, float* c,
-                        int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st);
-int lstm_bwd_persistent(float* gates, const float* whh, const float* dy, const float* c,
-                        int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st);
-size_t lstm_persist_workspace_bytes(int B, int H, int ND);
-// lstm_persist2.hip (bf16, B <= 16, H % 16 == 0)
-int lstm_fwd_persistent2(float* gates, const float* whh, const float* bias2, float* y, float* c,
-                         int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st);
-int lstm_bwd_persistent2(float* gates, const float* whh, const float* dy, const float* c,
-                         int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st);
-size_t lstm_persist2_workspace_bytes(int B, int H, int ND);
-
 // 0: one launch per time step; 1: persistent kernels (lstm_persist2.hip where it applies, else lstm_persist.hip);
 // 2: persistent, first-generation kernels only.  Env ASR_LSTM_PERSIST gives the initial value.
 static int g_persist = -1;
@@ -165,24 +153,52 @@ static int persist_mode() {
     if (g_persist < 0) { const char* e = getenv("ASR_LSTM_PERSIST"); g_persist = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1; }
     return g_persist;
 }
-static bool persist_enabled() { return persist_mode() >= 1; }
 extern "C" int asr_lstm_set_persistent(int on) { int old = persist_mode(); g_persist = (on >= 0 && on <= 2) ? on : 1; return old; }
 
-extern "C" size_t asr_lstm_workspace_bytes(int B, int H, int ND) {
-    size_t step = ((size_t)ND * H * 4 * H + (size_t)ND * B * H) * sizeof(float);
-    size_t per = lstm_persist_workspace_bytes(B, H, ND);
-    const size_t per2 = lstm_persist2_workspace_bytes(B, H, ND);
-    if (per2 > per) per = per2;
-    return (step > per ? step : per) + 256;
-}
+extern "C" size_t asr_lstm_workspace_bytes(int B, int H, int ND) { return lstm_workspace_bytes(B, H, ND); }
 
-// Which recurrence implementation asr_lstm_fwd / asr_lstm_bwd take for this shape with a workspace of
-// asr_lstm_workspace_bytes: 0 = one launch per time step, 1 = first-generation persistent kernel, 2 = second generation.
 extern "C" int asr_lstm_plan(int B, int T, int H, int ND, int prec) {
     (void)T;
-    if (!persist_enabled()) return 0;
-    if (persist_mode() == 1 && prec == ASR_BF16 && lstm_persist2_workspace_bytes(B, H, ND) > 0) return 2;
-    return lstm_persist_workspace_bytes(B, H, ND) > 0 ? 1 : 0;
+    return lstm_plan_query(persist_mode(), B, H, ND, prec == ASR_BF16);
+}
+
+// One pass of the recurrence on fp32 storage (asr_lstm_fwd: dy == nullptr; asr_lstm_bwd: y = dy, read-only), arguments
+// checked by the entry points: the planned generation's launch (lstm_plan.h), or one launch per time step.
+static int lstm_pass(float* gates, const float* whh, const float* bias2, float* y, float* c, bool bwd, int B, int T, int H, int ND, int prec,
+                     void* ws, size_t ws_bytes, hipStream_t st) {
+    LstmCall call;
+    call.ws_ok = ws && ((uintptr_t)ws & 255) == 0;
+    call.ws_bytes = ws_bytes;
+    call.aligned16 = bwd || (((uintptr_t)gates | (uintptr_t)y | (uintptr_t)c) & 15) == 0;
+    switch (lstm_pass_gen(persist_mode(), B, H, ND, prec == ASR_BF16, bwd, call)) {
+    case 2: return lstm_persistent2(gates, whh, bias2, y, c, bwd, B, T, H, ND, ws, st);
+    case 1: return lstm_persistent1(gates, whh, bias2, y, c, bwd, B, T, H, ND, prec, ws, st);
+    }
+    // launch-per-step path: the caller still watches the workspace's abort word (include/asr_hip.h, "Status word"), and the
+    // buffer arrives uninitialised - a stale non-zero word would make the optimizer refuse the step.  The first 256 bytes
+    // belong to the persistent path's status words; backward keeps the transposed W_hh and the dc carry behind them.
+    LstmP p{gates, whh, y, c, nullptr, bias2, B, T, H, ND};
+    if (bwd) {
+        hipMemsetAsync(ws, 0, 256, st);
+        float* wt = (float*)((char*)ws + 256);
+        hipLaunchKernelGGL(transpose_whh_kernel, dim3(256), dim3(256), 0, st, whh, wt, ND, H);
+        p.whh = wt;
+        p.dcf = wt + (size_t)ND * H * 4 * H;
+    } else if (ws && ws_bytes >= 4) {
+        hipMemsetAsync(ws, 0, 4, st);
+    }
+    const dim3 grid(cdiv(H, bwd ? 16 : 4), ND), block(bwd ? 256 : 64);
+    for (int s = 0; s < T; ++s) {
+        if (bwd) {
+            if (prec == ASR_BF16) hipLaunchKernelGGL(lstm_bwd_step<true>, grid, block, 0, st, p, s);
+            else                  hipLaunchKernelGGL(lstm_bwd_step<false>, grid, block, 0, st, p, s);
+        } else {
+            if (prec == ASR_BF16) hipLaunchKernelGGL(lstm_fwd_step<true>, grid, block, 0, st, p, s);
+            else                  hipLaunchKernelGGL(lstm_fwd_step<false>, grid, block, 0, st, p, s);
+        }
+    }
+    ASR_LAUNCH_CHECK(bwd ? "asr_lstm_bwd" : "asr_lstm_fwd");
+    return ASR_OK;
 }
 
 extern "C" int asr_lstm_fwd(float* gates, const float* whh, const float* bias2, float* y, float* c,
@@ -191,26 +207,8 @@ extern "C" int asr_lstm_fwd(float* gates, const float* whh, const float* bias2, 
     ASR_REQUIRE(gates && whh && y && c, ASR_E_ARG, "asr_lstm_fwd: null pointer");
     ASR_REQUIRE(B > 0 && T > 0 && H > 0 && (ND == 1 || ND == 2), ASR_E_ARG, "asr_lstm_fwd: bad dims");
     ASR_REQUIRE(((uintptr_t)whh & 15) == 0 && ((uintptr_t)y & 15) == 0, ASR_E_ARG, "asr_lstm_fwd: unaligned");
-    LstmP p{gates, whh, y, c, nullptr, bias2, B, T, H, ND};
-    hipStream_t st = (hipStream_t)stream;
-    if (workspace && persist_enabled() && ((uintptr_t)workspace & 255) == 0) {
-        int rc = persist_mode() == 1 ? lstm_fwd_persistent2(gates, whh, bias2, y, c, B, T, H, ND, prec, workspace, workspace_bytes, st) : 1;
-        if (rc <= 0) return rc;
-        rc = lstm_fwd_persistent(gates, whh, bias2, y, c, B, T, H, ND, prec, workspace, workspace_bytes, st);
-        if (rc <= 0) return rc;
-    }
-    // launch-per-step path: the caller still watches the workspace's abort word (include/asr_hip.h, "Status word"), and
-    // the buffer arrives uninitialised - a stale non-zero word would make the optimizer refuse the step
-    if (workspace && workspace_bytes >= 4) hipMemsetAsync(workspace, 0, 4, st);
-    dim3 grid(cdiv(H, 4), ND), block(64);
-    for (int s = 0; s < T; ++s) {
-        if (prec == ASR_BF16) hipLaunchKernelGGL(lstm_fwd_step<true>, grid, block, 0, st, p, s);
-        else                  hipLaunchKernelGGL(lstm_fwd_step<false>, grid, block, 0, st, p, s);
-    }
-    ASR_LAUNCH_CHECK("asr_lstm_fwd");
-    return ASR_OK;
+    return lstm_pass(gates, whh, bias2, y, c, false, B, T, H, ND, prec, workspace, workspace_bytes, (hipStream_t)stream);
 }
-
 
 extern "C" int asr_lstm_bwd(float* gates, const float* whh, const float* dy, const float* c,
                             int B, int T, int H, int ND, int prec,
@@ -219,61 +217,37 @@ extern "C" int asr_lstm_bwd(float* gates, const float* whh, const float* dy, con
     ASR_REQUIRE(B > 0 && T > 0 && H > 0 && (ND == 1 || ND == 2), ASR_E_ARG, "asr_lstm_bwd: bad dims");
     ASR_REQUIRE(workspace_bytes >= asr_lstm_workspace_bytes(B, H, ND), ASR_E_ARG, "asr_lstm_bwd: workspace too small");
     ASR_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)gates & 15) == 0, ASR_E_ARG, "asr_lstm_bwd: unaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (persist_enabled()) {
-        int rc = persist_mode() == 1 ? lstm_bwd_persistent2(gates, whh, dy, c, B, T, H, ND, prec, workspace, workspace_bytes, st) : 1;
-        if (rc <= 0) return rc;
-        rc = lstm_bwd_persistent(gates, whh, dy, c, B, T, H, ND, prec, workspace, workspace_bytes, st);
-        if (rc <= 0) return rc;
-    }
-    hipMemsetAsync(workspace, 0, 256, st);          // abort word clear on the launch-per-step path too (see asr_lstm_fwd)
-    float* wt = (float*)((char*)workspace + 256);   // the first 256 bytes belong to the persistent path's status words
-    float* dcf = wt + (size_t)ND * H * 4 * H;
-    hipLaunchKernelGGL(transpose_whh_kernel, dim3(256), dim3(256), 0, st, whh, wt, ND, H);
-    LstmP p{gates, wt, const_cast<float*>(dy), const_cast<float*>(c), dcf, nullptr, B, T, H, ND};
-    dim3 grid(cdiv(H, 16), ND), block(256);
-    for (int s = 0; s < T; ++s) {
-        if (prec == ASR_BF16) hipLaunchKernelGGL(lstm_bwd_step<true>, grid, block, 0, st, p, s);
-        else                  hipLaunchKernelGGL(lstm_bwd_step<false>, grid, block, 0, st, p, s);
-    }
-    ASR_LAUNCH_CHECK("asr_lstm_bwd");
-    return ASR_OK;
+    return lstm_pass(gates, whh, nullptr, const_cast<float*>(dy), const_cast<float*>(c), true, B, T, H, ND, prec,
+                     workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // bf16-storage recurrence (lstm_persist3.hip): gate-minor bf16 gates, time-padded bf16 h, batch-sliced XCD groups.
 // ------------------------------------------------------------------------------------------------------------------
-int lstm_fwd_persistent3(unsigned short* gates, const float* whh, unsigned short* y, float* c, int B, int T, int H, int ND,
-                         void* ws, size_t ws_bytes, unsigned epoch, int reserved_cus, hipStream_t st);
-int lstm_bwd_persistent3(unsigned short* gates, const float* whh, const unsigned short* dy, const float* c, int B, int T, int H, int ND,
-                         void* ws, size_t ws_bytes, unsigned epoch, int reserved_cus, hipStream_t st);
-size_t lstm_persist3_workspace_bytes(int B, int H, int ND, int bwd);
-
 extern "C" size_t asr_lstm16_workspace_bytes(int B, int H, int ND, int backward) {
-    if (!persist_enabled()) return 0;
-    return lstm_persist3_workspace_bytes(B, H, ND, backward);
+    return persist_mode() >= 1 ? lstm_gen3_pass(B, H, ND, backward != 0).bytes : 0;
+}
+
+// asr_lstm16_fwd (dy16 == nullptr) / asr_lstm16_bwd (y16 = dy16, read-only)
+static int lstm16_pass(const char* name, void* gates16, const float* whh, void* y16, float* c, bool bwd, int B, int T, int H, int ND,
+                       void* workspace, size_t workspace_bytes, unsigned epoch, int reserved_cus, asr_stream_t stream) {
+    ASR_REQUIRE(gates16 && whh && y16 && c && workspace, ASR_E_ARG, "%s: null pointer", name);
+    ASR_REQUIRE(B > 0 && T > 0 && H > 0 && (ND == 1 || ND == 2), ASR_E_ARG, "%s: bad dims", name);
+    ASR_REQUIRE((((uintptr_t)gates16 | (uintptr_t)y16 | (uintptr_t)c) & 15) == 0, ASR_E_ARG, "%s: unaligned", name);
+    const int rc = lstm_persistent3((unsigned short*)gates16, whh, (unsigned short*)y16, c, bwd, B, T, H, ND, workspace, workspace_bytes,
+                                    epoch, reserved_cus, (hipStream_t)stream);
+    ASR_REQUIRE(rc <= 0, ASR_E_UNSUPPORTED, "%s: no resident persistent plan for B=%d H=%d ND=%d (workspace %zu bytes, %d compute units reserved)",
+                name, B, H, ND, workspace_bytes, reserved_cus);
+    return rc;
 }
 
 extern "C" int asr_lstm16_fwd(void* gates16, const float* whh, void* y16, float* c, int B, int T, int H, int ND,
                               void* workspace, size_t workspace_bytes, unsigned epoch, int reserved_cus, asr_stream_t stream) {
-    ASR_REQUIRE(gates16 && whh && y16 && c && workspace, ASR_E_ARG, "asr_lstm16_fwd: null pointer");
-    ASR_REQUIRE(B > 0 && T > 0 && H > 0 && (ND == 1 || ND == 2), ASR_E_ARG, "asr_lstm16_fwd: bad dims");
-    ASR_REQUIRE((((uintptr_t)gates16 | (uintptr_t)y16 | (uintptr_t)c) & 15) == 0, ASR_E_ARG, "asr_lstm16_fwd: unaligned");
-    const int rc = lstm_fwd_persistent3((unsigned short*)gates16, whh, (unsigned short*)y16, c, B, T, H, ND, workspace, workspace_bytes,
-                                        epoch, reserved_cus, (hipStream_t)stream);
-    ASR_REQUIRE(rc <= 0, ASR_E_UNSUPPORTED, "asr_lstm16_fwd: no resident persistent plan for B=%d H=%d ND=%d (workspace %zu bytes, %d compute units reserved)",
-                B, H, ND, workspace_bytes, reserved_cus);
-    return rc;
+    return lstm16_pass("asr_lstm16_fwd", gates16, whh, y16, c, false, B, T, H, ND, workspace, workspace_bytes, epoch, reserved_cus, stream);
 }
 
 extern "C" int asr_lstm16_bwd(void* gates16, const float* whh, const void* dy16, const float* c, int B, int T, int H, int ND,
                               void* workspace, size_t workspace_bytes, unsigned epoch, int reserved_cus, asr_stream_t stream) {
-    ASR_REQUIRE(gates16 && whh && dy16 && c && workspace, ASR_E_ARG, "asr_lstm16_bwd: null pointer");
-    ASR_REQUIRE(B > 0 && T > 0 && H > 0 && (ND == 1 || ND == 2), ASR_E_ARG, "asr_lstm16_bwd: bad dims");
-    ASR_REQUIRE((((uintptr_t)gates16 | (uintptr_t)dy16 | (uintptr_t)c) & 15) == 0, ASR_E_ARG, "asr_lstm16_bwd: unaligned");
-    const int rc = lstm_bwd_persistent3((unsigned short*)gates16, whh, (const unsigned short*)dy16, c, B, T, H, ND, workspace, workspace_bytes,
-                                        epoch, reserved_cus, (hipStream_t)stream);
-    ASR_REQUIRE(rc <= 0, ASR_E_UNSUPPORTED, "asr_lstm16_bwd: no resident persistent plan for B=%d H=%d ND=%d (workspace %zu bytes, %d compute units reserved)",
-                B, H, ND, workspace_bytes, reserved_cus);
-    return rc;
+    return lstm16_pass("asr_lstm16_bwd", gates16, whh, const_cast<void*>(dy16), const_cast<float*>(c), true, B, T, H, ND,
+                       workspace, workspace_bytes, epoch, reserved_cus, stream);
 }

@@ -15,11 +15,11 @@
 // Same arithmetic as lstm.hip's launch-per-step kernels (which remain the fallback for shapes that do not
 // fit: H not a multiple of 16, too many rows for the LDS tiles, or more workgroups than CUs).
 #include "common.h"
+#include "handoff.h"
+#include "lstm_persist_common.h"
+#include "lstm_plan.h"
 
 namespace {
-
-typedef unsigned long long u64;
-constexpr int SPIN_LIMIT = 1 << 22;
 
 // Diagnostic build (-DASR_DIAG): workgroup (0,0) accumulates the wall time (100 MHz s_memrealtime ticks) it
 // spends in each phase of the forward step into the status block (u64 words 2..9 of the workspace).
@@ -44,11 +44,8 @@ struct PersistP {
     int B, T, H, ND, P, HS, MT;
 };
 
-__device__ __forceinline__ u64 ld_granule(const u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ void st_granule(u64* p, unsigned tag, unsigned payload) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)payload, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_gran(p, ((u64)tag << 32) | (u64)payload);
 }
 
 // Waits until granules base[0], base[stride], ..., base[(n-1)*stride] (n <= CH) all carry `tag` and returns their
@@ -64,7 +61,7 @@ __device__ __forceinline__ void gather_granules(const u64* base, long stride, in
     while (true) {
         u64 g[CH];
 #pragma unroll
-        for (int i = 0; i < CH; ++i) g[i] = ld_granule(base + (i < n ? i : 0) * stride);
+        for (int i = 0; i < CH; ++i) g[i] = ld_gran(base + (i < n ? i : 0) * stride);
         bool ok = true;
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
@@ -75,7 +72,7 @@ __device__ __forceinline__ void gather_granules(const u64* base, long stride, in
         ++spins;
         if ((spins & 63) == 0) {
             if (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
-            if (spins > SPIN_LIMIT) {
+            if (spins > SPIN_LIMIT2) {
                 __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 return;
             }
@@ -480,10 +477,10 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persist(PersistP p) {
     }
 }
 
-struct Plan { bool ok; int NT, NKS, P, HS, MT; size_t lds; };
+struct Plan { bool ok; int NT, NKS, P, HS, MT; size_t lds; int NE; };   // NE (backward): cell elements per thread
 
 Plan plan_fwd(int B, int H, bool bf16) {
-    Plan pl{false, 0, 0, 0, 0, 0, 0};
+    Plan pl{false, 0, 0, 0, 0, 0, 0, 0};
     if (B > 64 || H > 320) return pl;
     const int nks = (H + 31) / 32;
     pl.NT = 4; pl.NKS = nks; pl.HS = 64; pl.P = (H + 63) / 64; pl.MT = (B + 15) / 16;
@@ -495,7 +492,7 @@ Plan plan_fwd(int B, int H, bool bf16) {
 }
 
 Plan plan_bwd(int B, int H, bool bf16) {
-    Plan pl{false, 0, 0, 0, 0, 0, 0};
+    Plan pl{false, 0, 0, 0, 0, 0, 0, 0};
     if (H % 16 != 0 || B > 64) return pl;
     // slice size HS: K = 4*HS must be a multiple of 32; output tiles per wave NTO = ceil(H/16/4)
     const int nto = (H / 16 + 3) / 4;
@@ -505,20 +502,19 @@ Plan plan_bwd(int B, int H, bool bf16) {
         if (H % c == 0 && nks >= 1 && nto * nks <= 20) { HS = c; break; }
     }
     if (!HS) return pl;
-    pl.HS = HS; pl.P = H / HS; pl.NT = nto; pl.NKS = (4 * HS) / 32; pl.MT = (B + 15) / 16;
+    pl.HS = HS; pl.P = H / HS; pl.NT = nto; pl.NKS = (4 * HS) / 32; pl.MT = (B + 15) / 16; pl.NE = (B * HS + 255) / 256;
     const int K = 4 * HS, ld = bf16 ? K + 8 : K + 4;
     pl.lds = (size_t)pl.MT * 16 * ld * (bf16 ? 2 : 4) + (size_t)B * HS * 4;
     pl.ok = pl.lds <= 150 * 1024 && pl.P * 2 <= 200 && B * HS <= 256 * 8;
     return pl;
 }
 
+// p == nullptr: plan query, only asks whether the dispatch tables below hold an instantiation for `pl`
 template <typename KernelT>
-int launch_persist(KernelT kernel, const PersistP& p, size_t lds, hipStream_t st, const char* name) {
+int launch_persist(KernelT kernel, const PersistP* p, size_t lds, hipStream_t st, const char* name) {
+    if (!p) return ASR_OK;
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3(p.P, p.ND), dim3(256), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("%s: launch failed: %s", name, hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
+    return launch_checked(kernel, dim3(p->P, p->ND), dim3(256), lds, st, name, *p);
 }
 
 #define FWD_CASE(BF, NKS_)                                                                                          \
@@ -529,7 +525,7 @@ int launch_persist(KernelT kernel, const PersistP& p, size_t lds, hipStream_t st
     }
 #define BWD_CASE(BF, NTO_, NKS_)                                                                                              \
     if (pl.NT == NTO_ && pl.NKS == NKS_) {                                                                                    \
-        const int ne = (p.B * p.HS + 255) / 256;                                                                              \
+        const int ne = pl.NE;                                                                                                 \
         if (ne <= 1) return launch_persist(lstm_bwd_persist<BF, NTO_, NKS_, 1>, p, pl.lds, st, "asr_lstm_bwd(persistent)");    \
         if (ne <= 2) return launch_persist(lstm_bwd_persist<BF, NTO_, NKS_, 2>, p, pl.lds, st, "asr_lstm_bwd(persistent)");    \
         if (ne <= 4) return launch_persist(lstm_bwd_persist<BF, NTO_, NKS_, 4>, p, pl.lds, st, "asr_lstm_bwd(persistent)");    \
@@ -537,12 +533,12 @@ int launch_persist(KernelT kernel, const PersistP& p, size_t lds, hipStream_t st
     }
 
 template <bool BF>
-int dispatch_fwd(const Plan& pl, const PersistP& p, hipStream_t st) {
+int dispatch_fwd(const Plan& pl, const PersistP* p, hipStream_t st) {
     FWD_CASE(BF, 1) FWD_CASE(BF, 2) FWD_CASE(BF, 3) FWD_CASE(BF, 4) FWD_CASE(BF, 5) FWD_CASE(BF, 6) FWD_CASE(BF, 8) FWD_CASE(BF, 10)
-    return 1;   // no instantiation: caller falls back
+    return 1;   // no instantiation
 }
 template <bool BF>
-int dispatch_bwd(const Plan& pl, const PersistP& p, hipStream_t st) {
+int dispatch_bwd(const Plan& pl, const PersistP* p, hipStream_t st) {
     // (NTO, NKS): H=16 -> (1,*), H=32 -> (1,*), H=128 -> (2,8), H=320 -> (5,8), H=256 -> (4,8), H=512 -> (8,8)
     BWD_CASE(BF, 1, 1) BWD_CASE(BF, 1, 2) BWD_CASE(BF, 1, 4) BWD_CASE(BF, 1, 8) BWD_CASE(BF, 2, 8) BWD_CASE(BF, 4, 4) BWD_CASE(BF, 5, 4)
     BWD_CASE(BF, 3, 4) BWD_CASE(BF, 2, 4)
@@ -551,43 +547,35 @@ int dispatch_bwd(const Plan& pl, const PersistP& p, hipStream_t st) {
 
 }  // namespace
 
-// Returns ASR_OK when the persistent kernel was launched, 1 when the shape has no persistent plan
-// (caller uses the launch-per-step path), negative on error.
-int lstm_fwd_persistent(float* gates, const float* whh, const float* bias2, float* y, float* c,
-                        int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st) {
-    const bool bf = prec == ASR_BF16;
-    Plan pl = plan_fwd(B, H, bf);
-    if (!pl.ok || !ws) return 1;
-    const size_t need = 256 + 2 * (size_t)ND * B * H * sizeof(u64);
-    if (ws_bytes < need) return 1;
-    hipMemsetAsync(ws, 0, need, st);
-    PersistP p{gates, whh, bias2, y, c, (u64*)((char*)ws + 256), (unsigned*)ws, B, T, H, ND, pl.P, pl.HS, pl.MT};
-    return bf ? dispatch_fwd<true>(pl, p, st) : dispatch_fwd<false>(pl, p, st);
+// The plan of one pass and the bytes of its exchange: forward h (B x H granules per direction and parity), backward P
+// partial slices per consumer (P*P*B*HS = P*B*H granules); 0 for a backward without a plan.
+static Plan plan_pass(int B, int H, int ND, bool bf16, bool bwd, size_t& bytes) {
+    const Plan pl = bwd ? plan_bwd(B, H, bf16) : plan_fwd(B, H, bf16);
+    bytes = (bwd && !pl.ok) ? 0 : 256 + 2 * (size_t)ND * B * H * (bwd ? pl.P : 1) * sizeof(u64);
+    return pl;
 }
 
-int lstm_bwd_persistent(float* gates, const float* whh, const float* dy, const float* c,
-                        int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st) {
-    const bool bf = prec == ASR_BF16;
-    Plan pl = plan_bwd(B, H, bf);
-    if (!pl.ok || !ws) return 1;
-    const size_t need = 256 + 2 * (size_t)ND * pl.P * pl.P * B * pl.HS * sizeof(u64);
-    if (ws_bytes < need) return 1;
-    hipMemsetAsync(ws, 0, need, st);
-    PersistP p{gates, whh, nullptr, const_cast<float*>(dy), const_cast<float*>(c), (u64*)((char*)ws + 256), (unsigned*)ws,
-               B, T, H, ND, pl.P, pl.HS, pl.MT};
-    return bf ? dispatch_bwd<true>(pl, p, st) : dispatch_bwd<false>(pl, p, st);
+template <bool BF>
+static int dispatch(const Plan& pl, bool bwd, const PersistP* p, hipStream_t st) {
+    return bwd ? dispatch_bwd<BF>(pl, p, st) : dispatch_fwd<BF>(pl, p, st);
 }
 
-size_t lstm_persist_workspace_bytes(int B, int H, int ND) {
-    // upper bound of both passes: backward exchanges P partial slices per consumer (P*P*B*HS = P*B*H granules)
-    const int Pmax = H / 8 > 0 ? H / 8 : 1;
-    size_t fwd = 2 * (size_t)ND * B * H * sizeof(u64);
-    Plan pb = plan_bwd(B, H, true);
-    Plan pf = plan_bwd(B, H, false);
-    int P = 1;
-    if (pb.ok) P = pb.P;
-    if (pf.ok && pf.P > P) P = pf.P;
-    (void)Pmax;
-    size_t bwd = 2 * (size_t)ND * P * B * H * sizeof(u64);
-    return 256 + (fwd > bwd ? fwd : bwd);
+LstmPass lstm_gen1_pass(int B, int H, int ND, bool bf16, bool bwd) {
+    size_t bytes;
+    const Plan pl = plan_pass(B, H, ND, bf16, bwd, bytes);
+    // the dispatch tables are asked without a launch (p == nullptr), so the predicate cannot drift from them
+    return LstmPass{pl.ok && (bf16 ? dispatch<true>(pl, bwd, nullptr, 0) : dispatch<false>(pl, bwd, nullptr, 0)) == ASR_OK, bytes};
+}
+
+// Clear the pass's bytes of the workspace (status block + both granule buffers: tag 0 is never valid), then the one launch.
+int lstm_persistent1(float* gates, const float* whh, const float* bias2, float* y, float* c, bool bwd,
+                     int B, int T, int H, int ND, int prec, void* ws, hipStream_t st) {
+    const bool bf = prec == ASR_BF16;
+    size_t bytes;
+    const Plan pl = plan_pass(B, H, ND, bf, bwd, bytes);
+    hipMemsetAsync(ws, 0, bytes, st);
+    const PersistP p{gates, whh, bwd ? nullptr : bias2, y, c, (u64*)((char*)ws + 256), (unsigned*)ws, B, T, H, ND, pl.P, pl.HS, pl.MT};
+    const int rc = bf ? dispatch<true>(pl, bwd, &p, st) : dispatch<false>(pl, bwd, &p, st);
+    ASR_REQUIRE(rc <= 0, ASR_E_UNSUPPORTED, "asr_lstm_%s(persistent): no kernel for B=%d H=%d", bwd ? "bwd" : "fwd", B, H);
+    return rc;
 }

@@ -23,22 +23,10 @@
 #include "common.h"
 #include <stdlib.h>
 #include "handoff.h"
+#include "lstm_persist_common.h"
+#include "lstm_plan.h"
 
 namespace {
-
-// Diagnostic build (make diag, -DASR_DIAG): wave 0 of workgroup (0,0) accumulates the wall time (100 MHz
-// s_memrealtime ticks) of each phase of a step into the status block (u64 words 2..9 of the workspace).
-#ifdef ASR_DIAG
-#define DIAG2_DECL unsigned long long dg_t = __builtin_amdgcn_s_memrealtime(), dg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define DIAG2_MARK(k) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); unsigned long long n_ = __builtin_amdgcn_s_memrealtime(); dg_acc[k] += n_ - dg_t; dg_t = n_; __builtin_amdgcn_sched_barrier(0); }
-#define DIAG2_COUNT(k, v) { dg_acc[k] += (v); }
-#define DIAG2_DUMP(thr, word) { if (blockIdx.x == 0 && threadIdx.x == (thr)) { unsigned long long* o = (unsigned long long*)p.abort_flag + (word); for (int k = 0; k < 8; ++k) o[k] = dg_acc[k]; } }
-#else
-#define DIAG2_DECL
-#define DIAG2_MARK(k)
-#define DIAG2_COUNT(k, v) { (void)(v); }
-#define DIAG2_DUMP(thr, word)
-#endif
 
 struct P2 {
     float* gates;        // (B,T,ND,4H)
@@ -58,9 +46,6 @@ struct P2 {
 #define POLL_DELAY_FWD 12
 #define POLL_DELAY_BWD 8
 
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
@@ -72,12 +57,7 @@ __device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __built
 //                        stores / prefetches would not be seen before those have completed (measured: +1 us per step).
 // Exchange buffer xbuf[parity][dir][b][H/4].
 __host__ __device__ __forceinline__ long fwd_region(int B, int H) { return (long)B * (H >> 2); }   // granules per (parity, direction)
-// tag: bit 14 of each of the four bf16 values (always 0 for |h| <= 1): step sequence in elements 0,1, launch epoch in 2,3
-// (the epoch keeps granules of an earlier launch, which can survive in an L2 with valid sequence bits, from being accepted)
-constexpr u64 FWD_MASK = (1ull << 14) | (1ull << 30) | (1ull << 46) | (1ull << 62);
-__device__ __forceinline__ u64 fwd_want(unsigned seq, unsigned epoch) {
-    return ((u64)(seq & 1u) << 14) | ((u64)(seq >> 1) << 30) | ((u64)(epoch & 1u) << 46) | ((u64)((epoch >> 1) & 1u) << 62);
-}
+// tag of a granule: FWD_MASK / fwd_want (lstm_persist_common.h)
 
 template <int NKS>
 __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
             slot_off[i] = (idx < total2) ? (idx / HG2) * LD + (idx % HG2) * 8 : -1;
             if (idx < total2) cnt = i + 1;
         }
-        DIAG2_DECL
+        LSTM_DIAG_DECL
         for (int s = 0; s < T; ++s) {
             __bf16* tile = tiles + (s & 1) * 16 * LD;
             if (s > 0 && cnt > 0) {
@@ -123,8 +103,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
                 for (int z = 0; z < p.poll_delay; ++z) __builtin_amdgcn_s_sleep(2);
                 const u64* src = p.xbuf + ((long)((s - 1) & 1) * ND + d) * xregion + 2 * gt;
                 const int sp = gather16<CH>(src, 512, cnt, FWD_MASK, fwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
-                DIAG2_MARK(0)
-                DIAG2_COUNT(7, sp)
+                LSTM_DIAG_MARK(0)
+                LSTM_DIAG_COUNT(7, sp)
 #pragma unroll
                 for (int i = 0; i < CH; ++i)
                     if (slot_off[i] >= 0) {
@@ -133,13 +113,13 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
                         dst[1] = ghi[i] & ~FWD_MASK;
                     }
             }
-            DIAG2_MARK(1)
+            LSTM_DIAG_MARK(1)
             __syncthreads();
-            DIAG2_MARK(2)
+            LSTM_DIAG_MARK(2)
             __syncthreads();
-            DIAG2_MARK(3)
+            LSTM_DIAG_MARK(3)
         }
-        DIAG2_DUMP(256, 10)
+        LSTM_DIAG_DUMP(256, 10)
         return;
     }
 
@@ -177,14 +157,14 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
     };
     float4 xgA = ldx(0), xgB = ldx(1), xgC = ldx(2);
     float4 cst = make_float4(0.f, 0.f, 0.f, 0.f);
-    DIAG2_DECL
+    LSTM_DIAG_DECL
 
     for (int s = 0; s < T; ++s) {
         const long t = tix(s);
         const __bf16* tile = tiles + (s & 1) * 16 * LD;
-        DIAG2_MARK(7)
+        LSTM_DIAG_MARK(7)
         __syncthreads();                         // h_{t-1} tile complete
-        DIAG2_MARK(0)
+        LSTM_DIAG_MARK(0)
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         if (s > 0) {
             bf16x8 hb[NKS];
@@ -202,9 +182,9 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
         }
         const float4 o_gate = make_float4(a[0], a[1], a[2], a[3]);
         *reinterpret_cast<float4*>(gbuf + (g * 16 + n) * 20 + 4 * q) = o_gate;
-        DIAG2_MARK(1)
+        LSTM_DIAG_MARK(1)
         __syncthreads();                         // the four gates of this step are in LDS
-        DIAG2_MARK(2)
+        LSTM_DIAG_MARK(2)
         if (g == 0) {
             const float4 gi = *reinterpret_cast<const float4*>(gbuf + (0 * 16 + n) * 20 + 4 * q);
             const float4 gf = *reinterpret_cast<const float4*>(gbuf + (1 * 16 + n) * 20 + 4 * q);
@@ -230,15 +210,15 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
             }
 #endif
         }
-        DIAG2_MARK(3)
+        LSTM_DIAG_MARK(3)
         // saved activated gate (for BPTT) and the input-projection operand three steps ahead
 #ifndef ASR_NOIO
         if (bok) *reinterpret_cast<float4*>(gs_base + t * g_ts) = o_gate;
 #endif
         xgA = xgB; xgB = xgC; xgC = ldx(s + 3);
-        DIAG2_MARK(4)
+        LSTM_DIAG_MARK(4)
     }
-    DIAG2_DUMP(0, 2)
+    LSTM_DIAG_DUMP(0, 2)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -250,13 +230,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
 // Waves 0-3: cell backward, MFMA, publish, bulk traffic.  Waves 4-7: poll and sum the producers' partials
 // (wave 4+k sums producers [k*NTO, (k+1)*NTO)).
 // Exchange buffer xbuf[parity][dir][consumer][producer][b][8 pairs of fp32].
-// tag: three mantissa LSBs of both floats = 2-bit step sequence + 4-bit launch epoch
-constexpr u64 BWD_MASK = 7ull | (7ull << 32);
-__device__ __forceinline__ u64 bwd_want(unsigned seq, unsigned epoch) {
-    epoch = 2u + epoch % 14u;             // epoch field 2..15: non-zero tag bits in BOTH words (see pair_want, decoder_persist.hip)
-    const unsigned tag = ((epoch & 15u) << 2) | seq;
-    return (u64)(tag & 7u) | ((u64)(tag >> 3) << 32);
-}
+// tag of a granule: BWD_MASK / bwd_want (lstm_persist_common.h)
 
 template <int NTO>
 __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
@@ -283,7 +257,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
         const int gt = tid - 256;
         const int gslot = gt & 63, gb = gslot >> 2, g4 = gslot & 3, gq = gt >> 6;
         const int pp_lo = gq * NTO, cntp = max(0, min(P - pp_lo, NTO));
-        DIAG2_DECL
+        LSTM_DIAG_DECL
         for (int s = 0; s < T; ++s) {
             if (s > 0) {
                 float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -301,16 +275,16 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
                             a3 += __uint_as_float((unsigned)(ghi[i] >> 32) & ~7u);
                         }
                 }
-                DIAG2_MARK(0)
+                LSTM_DIAG_MARK(0)
                 *reinterpret_cast<float4*>(s_part + gq * 256 + gb * 16 + 4 * g4) = make_float4(a0, a1, a2, a3);
             }
-            DIAG2_MARK(1)
+            LSTM_DIAG_MARK(1)
             __syncthreads();
-            DIAG2_MARK(2)
+            LSTM_DIAG_MARK(2)
             __syncthreads();
-            DIAG2_MARK(3)
+            LSTM_DIAG_MARK(3)
         }
-        DIAG2_DUMP(256, 10)
+        LSTM_DIAG_DUMP(256, 10)
         return;
     }
 
@@ -382,12 +356,12 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
     Raw rawB = load_raw(1);
     Raw rawC = load_raw(2);
     float carry = 0.f;
-    DIAG2_DECL
+    LSTM_DIAG_DECL
 
     for (int s = 0; s < T; ++s) {
-        DIAG2_MARK(7)
+        LSTM_DIAG_MARK(7)
         __syncthreads();                         // recurrent partial sums of step s are in s_part
-        DIAG2_MARK(0)
+        LSTM_DIAG_MARK(0)
         // cell backward of the owned element -> bf16 operand tile
         float dgv[4];
         {
@@ -403,9 +377,9 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
                 tile[eb * LD + 48 + ej] = (__bf16)dgv[3];
             }
         }
-        DIAG2_MARK(1)
+        LSTM_DIAG_MARK(1)
         __syncthreads();
-        DIAG2_MARK(2)
+        LSTM_DIAG_MARK(2)
         // partial dh_{prev}[b, k'] for every k', handed to the owner of k'
         if (s + 1 < T) {
             const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(tile + n * LD + 8 * q);
@@ -431,7 +405,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
                 }
             }
         }
-        DIAG2_MARK(3)
+        LSTM_DIAG_MARK(3)
         // gradients wrt the gate pre-activations replace the saved gates; operands three steps ahead; next coefficients
         if (eok) {
             float* gp = ge + (long)tix(s) * g_ts;
@@ -440,69 +414,39 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
         coef = make_coef(rawB);
         rawB = rawC;
         rawC = load_raw(s + 3);
-        DIAG2_MARK(4)
+        LSTM_DIAG_MARK(4)
     }
-    DIAG2_DUMP(0, 2)
-}
-
-template <typename KernelT>
-int launch_p2(KernelT kernel, const P2& p, size_t lds, hipStream_t st, const char* name) {
-    hipLaunchKernelGGL(kernel, dim3(8 * p.P), dim3(512), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("%s: launch failed: %s", name, hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
+    LSTM_DIAG_DUMP(0, 2)
 }
 
 int poll_delay(bool bwd) {
-    static int df = -1, db = -1;
-    if (df < 0) {
-        const char* e = getenv("ASR_LSTM_POLL_DELAY_FWD"); df = e ? atoi(e) : POLL_DELAY_FWD;
-        e = getenv("ASR_LSTM_POLL_DELAY_BWD"); db = e ? atoi(e) : POLL_DELAY_BWD;
-    }
-    return bwd ? db : df;
+    static const int d[2] = {env_int("ASR_LSTM_POLL_DELAY_FWD", POLL_DELAY_FWD), env_int("ASR_LSTM_POLL_DELAY_BWD", POLL_DELAY_BWD)};
+    return d[bwd];
 }
 unsigned next_epoch() { static unsigned e = 1; return e++; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-size_t lstm_persist2_workspace_bytes(int B, int H, int ND) {
-    if (H % 16 != 0 || B > 16 || H > 512) return 0;
+LstmPass lstm_gen2_pass(int B, int H, int ND, bool bf16, bool bwd) {
+    if (!bf16 || B > 16 || H % 16 != 0 || H > 512) return LstmPass{false, 0};
     const size_t P = H / 16;
-    const size_t fwd = 2 * (size_t)ND * fwd_region(B, H) * sizeof(u64);
-    const size_t bwd = 2 * (size_t)ND * P * P * B * 8 * sizeof(u64);
-    return 256 + (fwd > bwd ? fwd : bwd);
+    return LstmPass{true, 256 + 2 * (size_t)ND * (bwd ? P * P * B * 8 : (size_t)fwd_region(B, H)) * sizeof(u64)};
 }
 
 #define FWD2_CASE(NKS_) \
-    if (nks <= NKS_) return launch_p2(lstm_fwd_p2<NKS_>, p, 2 * 16 * (NKS_ * 32 + 8) * 2 + 4 * 16 * 20 * 4, st, "asr_lstm_fwd(persistent v2)");
+    if (nks <= NKS_) return launch_checked(lstm_fwd_p2<NKS_>, dim3(8 * p.P), dim3(512), 2 * 16 * (NKS_ * 32 + 8) * 2 + 4 * 16 * 20 * 4, st, "asr_lstm_fwd(persistent v2)", p);
 #define BWD2_CASE(NTO_) \
-    if (nto <= NTO_) return launch_p2(lstm_bwd_p2<NTO_>, p, 0, st, "asr_lstm_bwd(persistent v2)");
+    if (nto <= NTO_) return launch_checked(lstm_bwd_p2<NTO_>, dim3(8 * p.P), dim3(512), 0, st, "asr_lstm_bwd(persistent v2)", p);
 
-// Return ASR_OK when launched, 1 when the shape/precision has no v2 plan, negative on error.
-int lstm_fwd_persistent2(float* gates, const float* whh, const float* bias2, float* y, float* c,
-                         int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (prec != ASR_BF16 || B > 16 || H % 16 != 0 || H > 512 || !ws) return 1;
-    if (!aligned16(gates) || !aligned16(y) || !aligned16(c)) return 1;
-    const size_t need = 256 + 2 * (size_t)ND * fwd_region(B, H) * sizeof(u64);
-    if (ws_bytes < need) return 1;
-    hipMemsetAsync(ws, 0, need, st);
-    P2 p{gates, whh, bias2, y, c, (u64*)((char*)ws + 256), (unsigned*)ws, B, T, H, ND, H / 16, xcd_local_allowed(), poll_delay(false), next_epoch()};
-    const int nks = (H + 31) / 32;
-    FWD2_CASE(1) FWD2_CASE(2) FWD2_CASE(4) FWD2_CASE(6) FWD2_CASE(8) FWD2_CASE(10) FWD2_CASE(12) FWD2_CASE(16)
-    return 1;
-}
-
-int lstm_bwd_persistent2(float* gates, const float* whh, const float* dy, const float* c,
-                         int B, int T, int H, int ND, int prec, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (prec != ASR_BF16 || B > 16 || H % 16 != 0 || H > 512 || !ws) return 1;
-    const size_t P = H / 16;
-    const size_t need = 256 + 2 * (size_t)ND * P * P * B * 8 * sizeof(u64);
-    if (ws_bytes < need) return 1;
-    hipMemsetAsync(ws, 0, need, st);
-    P2 p{gates, whh, nullptr, const_cast<float*>(dy), const_cast<float*>(c), (u64*)((char*)ws + 256), (unsigned*)ws,
-         B, T, H, ND, (int)P, xcd_local_allowed(), poll_delay(true), next_epoch()};
-    const int nto = ((int)P + 3) / 4;
-    BWD2_CASE(1) BWD2_CASE(2) BWD2_CASE(3) BWD2_CASE(4) BWD2_CASE(5) BWD2_CASE(6) BWD2_CASE(8)
-    return 1;
+// Clear the pass's bytes of the workspace (status block + both granule buffers), then the one launch; every planned shape
+// (lstm_gen2_pass) has an instantiation.
+int lstm_persistent2(float* gates, const float* whh, const float* bias2, float* y, float* c, bool bwd,
+                     int B, int T, int H, int ND, void* ws, hipStream_t st) {
+    hipMemsetAsync(ws, 0, lstm_gen2_pass(B, H, ND, true, bwd).bytes, st);
+    const P2 p{gates, whh, bwd ? nullptr : bias2, y, c, (u64*)((char*)ws + 256), (unsigned*)ws, B, T, H, ND, H / 16,
+               xcd_local_allowed(), poll_delay(bwd), next_epoch()};
+    const int nks = (H + 31) / 32, nto = (p.P + 3) / 4;
+    if (bwd) { BWD2_CASE(1) BWD2_CASE(2) BWD2_CASE(3) BWD2_CASE(4) BWD2_CASE(5) BWD2_CASE(6) BWD2_CASE(8) }
+    else { FWD2_CASE(1) FWD2_CASE(2) FWD2_CASE(4) FWD2_CASE(6) FWD2_CASE(8) FWD2_CASE(10) FWD2_CASE(12) FWD2_CASE(16) }
+    ASR_REQUIRE(false, ASR_E_UNSUPPORTED, "asr_lstm_%s(persistent v2): no kernel for H=%d", bwd ? "bwd" : "fwd", H);
 }

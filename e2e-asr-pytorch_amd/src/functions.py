@@ -6,6 +6,7 @@ gradient buffer (the views held in `param.grad`); the Functions therefore return
 activations.  `anchor` is a dummy requires-grad tensor that keeps autograd calling `backward` even when
 the acoustic features themselves need no gradient.
 """
+import contextlib
 import ctypes
 import weakref
 
@@ -22,6 +23,38 @@ def _empty(shape, like):
 # encoder RNN layer: BiLSTM -> [LayerNorm] -> dropout -> time down-sampling -> tanh(Linear)
 # (reference RNNLayer.forward, src/module.py:1040-1081)
 # --------------------------------------------------------------------------------------------------
+def out_frames(layer, T):
+    """(T2, segs) of the layer's time down-sampling: 'drop' keeps ceil(T / rate) frames, 'concat' stacks T // rate groups of
+    segs = rate frames side by side and drops the tail."""
+    r = layer.sample_rate
+    if r == 1:
+        return T, 1
+    return ((T + r - 1) // r, 1) if layer.sample_style == 'drop' else (T // r, r)
+
+
+def lstm_rec(layer, gates, B, T, prec, dy=None, c=None):
+    """The fp32-storage recurrence of one layer on the current stream: forward (dy None; returns the new y, c) or backward
+    (dy, c given; `gates` becomes the gradient wrt the gate pre-activations).  The workspace is a pool area for this one launch
+    and goes back to the pool once its abort word has been collected."""
+    Hd, ND = layer.dim, layer.nd
+    nbytes = H.lib().asr_lstm_workspace_bytes(B, Hd, ND)
+    ws = H.handoff_acquire(nbytes, gates.device)
+    tail = (B, T, Hd, ND, prec, H.ptr(ws), nbytes, H.stream_ptr())
+    if dy is None:
+        y, c = _empty((B, T, ND * Hd), gates), _empty((B, T, ND, Hd), gates)
+        H.call('asr_lstm_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(layer.b_hh_cat), H.ptr(y), H.ptr(c), *tail)
+        layer.last_ws = ws
+        H.watch_abort(ws, release=True)
+        return y, c
+    pre = torch.cuda.Event()
+    pre.record(torch.cuda.current_stream())
+    H.call('asr_lstm_bwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(dy), H.ptr(c), *tail)
+    layer.last_ws_bwd = ws
+    H.watch_abort(ws, release=True)
+    H.flush_side(after=pre)       # the upper layer's parameter gradients run beside this recurrence (40 workgroups)
+    return None, c
+
+
 class RNNLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, x, layer, train, seed, prec):
@@ -33,14 +66,7 @@ class RNNLayerFn(torch.autograd.Function):
         st = H.stream_ptr()
         gates = _empty((B, T, ND, 4 * Hd), x)
         H.gemm(x, layer.w_ih_cat, gates, B * T, G, Din, Din, Din, G, 1, 1, bias=layer.b_ih_cat, prec=prec)
-        y = _empty((B, T, D), x)
-        c = _empty((B, T, ND, Hd), x)
-        nbytes = H.lib().asr_lstm_workspace_bytes(B, Hd, ND)
-        ws = H.handoff_acquire(nbytes, x.device)          # pool area for this one launch, back to the pool once collected
-        H.call('asr_lstm_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(layer.b_hh_cat), H.ptr(y), H.ptr(c),
-               B, T, Hd, ND, prec, H.ptr(ws), nbytes, st)
-        layer.last_ws = ws
-        H.watch_abort(ws, release=True)
+        y, c = lstm_rec(layer, gates, B, T, prec)
         yn, stats = y, None
         if layer.layer_norm:
             yn = _empty((B, T, D), x)
@@ -49,12 +75,8 @@ class RNNLayerFn(torch.autograd.Function):
                    B * T, D, 1e-5, 0, st)
         p = float(layer.dropout) if train else 0.0
         r, style = layer.sample_rate, (0 if layer.sample_style == 'drop' else 1)
-        if r == 1:
-            T2, Dz = T, D
-        elif style == 0:
-            T2, Dz = (T + r - 1) // r, D
-        else:
-            T2, Dz = T // r, D * r
+        T2, segs = out_frames(layer, T)
+        Dz = D * segs
         alias = (r == 1 and p == 0.0)
         if alias:
             z = yn
@@ -107,15 +129,7 @@ class RNNLayerFn(torch.autograd.Function):
                    H.ptr(dy), H.ptr(layer.ln.weight.grad), H.ptr(layer.ln.bias.grad), B * T, D, 0, st)
         else:
             dy = dyn
-        nbytes = H.lib().asr_lstm_workspace_bytes(B, Hd, ND)
-        ws = H.handoff_acquire(nbytes, x.device)
-        pre = torch.cuda.Event()
-        pre.record(torch.cuda.current_stream())
-        H.call('asr_lstm_bwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(dy), H.ptr(c), B, T, Hd, ND, prec,
-               H.ptr(ws), nbytes, st)
-        layer.last_ws_bwd = ws
-        H.watch_abort(ws, release=True)
-        H.flush_side(after=pre)       # the upper layer's parameter gradients run beside this recurrence (40 workgroups)
+        lstm_rec(layer, gates, B, T, prec, dy, c)
         # gates now holds the gradient wrt the gate pre-activations
         g2 = gates.view(B * T, G)
         x2 = x.view(B * T, Din)
@@ -191,17 +205,19 @@ def to_f32_fn(x):
     return CastF32Fn.apply(x) if x.dtype == torch.bfloat16 else x
 
 
-def rnn_fast_ok(layer, x, prec):
-    """The bf16-storage path covers: bf16 contractions, LSTM cell, H % 16 == 0 <= 512, no LayerNorm, 'drop' down-sampling
-    (or none), input width a multiple of 8, B <= 16 * (8 / directions)."""
-    if prec != H.BF16 or layer.layer_norm or not H.fast16_enabled():
+def fast16_layer_ok(layer, B, Din):
+    """What the bf16-storage path asks of a layer: LSTM cell, H % 16 == 0 <= 512, no LayerNorm, 'drop' down-sampling (or
+    none), input width a multiple of 8, B <= 16 * (8 / directions)."""
+    if layer.layer_norm or (layer.sample_rate > 1 and layer.sample_style != 'drop'):
         return False
-    if layer.sample_rate > 1 and layer.sample_style != 'drop':
-        return False
-    B, T, Din = x.shape
     if Din % 8 != 0 or (layer.nd * layer.dim) % 8 != 0:
         return False
     return int(H.lib().asr_lstm16_workspace_bytes(B, layer.dim, layer.nd, 0)) > 0
+
+
+def rnn_fast_ok(layer, x, prec):
+    """The bf16-storage path covers: bf16 contractions and the layers of fast16_layer_ok."""
+    return prec == H.BF16 and H.fast16_enabled() and fast16_layer_ok(layer, x.shape[0], x.shape[2])
 
 
 def _ws16(layer, B, bwd):
@@ -219,6 +235,29 @@ def _ws16(layer, B, bwd):
     return ent[0], ent[1]
 
 
+def lstm16_rec(layer, gates, B, T, reserved, dy=None, c=None, beside=False):
+    """The bf16-storage recurrence of one layer: forward (dy None; returns the new time-padded y and c) or backward (dy, c given;
+    `gates` becomes the gradient wrt the gate pre-activations).  Owns the layer's persistent workspace and its abort words: two
+    status blocks by launch parity (include/asr_hip.h), this launch reports in block epoch & 1 and clears the other one.
+    beside=True: launched on the CU-masked recurrence stream, and the deferred side-stream work is flushed to start with it."""
+    Hd, ND, bwd = layer.dim, layer.nd, dy is not None
+    ws, epoch = _ws16(layer, B, int(bwd))
+    H.abort_guard(ws, ((epoch + 1) & 1) * 1024)
+    y = None if bwd else _empty16((B, T + 2, ND * Hd), gates)      # rows 0 and T+1 (time pads) are zeroed by the recurrence kernel
+    c = c if bwd else _empty((B, T, ND, Hd), gates)
+    pre = torch.cuda.Event() if beside else None
+    if beside:
+        pre.record(torch.cuda.current_stream())
+    with (H.on_rec_stream() if beside else contextlib.nullcontext()):
+        H.call('asr_lstm16_bwd' if bwd else 'asr_lstm16_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(dy if bwd else y), H.ptr(c),
+               B, T, Hd, ND, H.ptr(ws), ws.numel(), epoch, reserved, H.stream_ptr())
+    if beside:
+        H.flush_side(after=pre)       # the deferred gradients (layer above, this layer's projection) start with this recurrence
+    H.watch_abort(ws, (epoch & 1) * 1024)
+    setattr(layer, 'last_ws_bwd' if bwd else 'last_ws', ws)
+    return y, c
+
+
 def prepack16(layers, B, prec):
     """The bf16 weight copies of the later encoder layers, made on the side stream beside the first layer's projection and
     recurrence instead of in front of their own (4 x 13 us of small launches on the step's critical path).  Called once per
@@ -230,9 +269,7 @@ def prepack16(layers, B, prec):
         return
     if any(getattr(l, 'dp', None) is not None for l in layers) and not H.overlap_dp_enabled():
         return                # data parallel: no CU-masked stream beside RCCL's kernels until that has been run
-    todo = [l for l in layers[1:] if not l.layer_norm and (l.sample_rate == 1 or l.sample_style == 'drop')
-            and l.w_ih_cat.shape[1] % 8 == 0 and (l.nd * l.dim) % 8 == 0
-            and int(H.lib().asr_lstm16_workspace_bytes(B, l.dim, l.nd, 0)) > 0]
+    todo = [l for l in layers[1:] if fast16_layer_ok(l, B, l.w_ih_cat.shape[1])]
     if not todo:
         return
     for l in todo:
@@ -279,19 +316,11 @@ class RNNLayerFastFn(torch.autograd.Function):
         pk = _packed16(layer)
         gates = _empty16((B, T, ND, Hd, 4), x16)
         H.gemm16(x16, pk['wih'], gates, B * T, G, Din, Din, Din, G, 1, 1, bias=pk['bias'])
-        y = _empty16((B, T + 2, D), x16)          # rows 0 and T+1 (time pads) are zeroed by the recurrence kernel
-        c = _empty((B, T, ND, Hd), x16)
-        ws, epoch = _ws16(layer, B, 0)
-        # two status blocks by launch parity (include/asr_hip.h): this launch reports in block epoch & 1 and clears the other one
-        H.abort_guard(ws, ((epoch + 1) & 1) * 1024)
         reserved = 64 if (layer.dp is not None and layer.dp.world > 1) else 0
-        H.call('asr_lstm16_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(y), H.ptr(c), B, T, Hd, ND,
-               H.ptr(ws), ws.numel(), epoch, reserved, st)
-        H.watch_abort(ws, (epoch & 1) * 1024)
-        layer.last_ws = ws
+        y, c = lstm16_rec(layer, gates, B, T, reserved)
         p = float(layer.dropout) if train else 0.0
         r = layer.sample_rate
-        T2 = T if r == 1 else (T + r - 1) // r
+        T2 = out_frames(layer, T)[0]
         z = _empty16((B, T2, D), x16)
         H.call('asr_dropout_downsample16_fwd', H.ptr(y), (T + 2) * D, D, H.ptr(z), B, T, D, T2, r, 0, p, seed, st)
         if layer.proj:
@@ -348,20 +377,7 @@ class RNNLayerFastFn(torch.autograd.Function):
             dz = dout
         dy = _empty16((B, T, D), x16)
         H.call('asr_dropout_downsample16_bwd', H.ptr(dz), H.ptr(dy), B, T, D, T2, layer.sample_rate, 0, p, seed, st)
-        ws, epoch = _ws16(layer, B, 1)
-        H.abort_guard(ws, ((epoch + 1) & 1) * 1024)
-        if overlap:
-            pre = torch.cuda.Event()
-            pre.record(torch.cuda.current_stream())
-            with H.on_rec_stream():
-                H.call('asr_lstm16_bwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(dy), H.ptr(c), B, T, Hd, ND,
-                       H.ptr(ws), ws.numel(), epoch, 256 - 8 * H.REC_UNITS, H.stream_ptr())
-            H.flush_side(after=pre)       # the deferred gradients (layer above, this layer's projection) start with this recurrence
-        else:
-            H.call('asr_lstm16_bwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(dy), H.ptr(c), B, T, Hd, ND,
-                   H.ptr(ws), ws.numel(), epoch, reserved, st)
-        H.watch_abort(ws, (epoch & 1) * 1024)
-        layer.last_ws_bwd = ws
+        lstm16_rec(layer, gates, B, T, 256 - 8 * H.REC_UNITS if overlap else reserved, dy, c, beside=overlap)
         # gates now holds the gradient wrt the gate pre-activations (gate-minor); parameter gradients in reference row order
         dx = None
         if ctx.need_dx:

@@ -68,13 +68,6 @@ def _unalign(y, bstride, off, z, lens, B, T, layer, T2, esize):
            esize, H.stream_ptr())
 
 
-def _out_frames(layer, T):
-    r = layer.sample_rate
-    if r == 1:
-        return T, 1
-    return ((T + r - 1) // r, 1) if layer.sample_style == 'drop' else (T // r, r)
-
-
 def ragged_layer(layer, x, lens, prec):
     """One encoder layer over the padded batch x (B,T,Din), fp32 or bf16, rows at t >= lens[b] arbitrary (never used).
     lens int64 (B) on the device, max(lens) == T.  Returns (B,T2,Dz) in the storage mode RNNLayer.forward would choose; its
@@ -82,7 +75,7 @@ def ragged_layer(layer, x, lens, prec):
     B, T, Din = x.shape
     Hd, ND = layer.dim, layer.nd
     G, D = ND * 4 * Hd, ND * Hd
-    T2, segs = _out_frames(layer, T)
+    T2, segs = F_hip.out_frames(layer, T)
     Dz = D * segs
     st = H.stream_ptr()
     if T2 == 0:
@@ -94,12 +87,7 @@ def ragged_layer(layer, x, lens, prec):
         H.gemm16(x16, pk['wih'], raw, B * T, G, Din, Din, Din, G, 1, 1, bias=pk['bias'])
         gates = torch.empty_like(raw)
         H.call('asr_ragged_align', H.ptr(raw), H.ptr(gates), H.ptr(lens), B, T, ND, 4 * Hd, 2, st)
-        y = F_hip._empty16((B, T + 2, D), x16)
-        c = F_hip._empty((B, T, ND, Hd), x16)
-        ws, epoch = F_hip._ws16(layer, B, 0)
-        H.abort_guard(ws, ((epoch + 1) & 1) * 1024)
-        H.call('asr_lstm16_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(y), H.ptr(c), B, T, Hd, ND, H.ptr(ws), ws.numel(), epoch, 0, st)
-        H.watch_abort(ws, (epoch & 1) * 1024)
+        y, _c = F_hip.lstm16_rec(layer, gates, B, T, 0)
         z = F_hip._empty16((B, T2, Dz), x16)
         _unalign(y, (T + 2) * D, D, z, lens, B, T, layer, T2, 2)
         if not layer.proj:
@@ -112,13 +100,7 @@ def ragged_layer(layer, x, lens, prec):
     H.gemm(x, layer.w_ih_cat, raw, B * T, G, Din, Din, Din, G, 1, 1, bias=layer.b_ih_cat, prec=prec)
     gates = torch.empty_like(raw)
     H.call('asr_ragged_align', H.ptr(raw), H.ptr(gates), H.ptr(lens), B, T, ND, 4 * Hd, 4, st)
-    y = F_hip._empty((B, T, D), x)
-    c = F_hip._empty((B, T, ND, Hd), x)
-    nbytes = H.lib().asr_lstm_workspace_bytes(B, Hd, ND)
-    ws = H.handoff_acquire(nbytes, x.device)
-    H.call('asr_lstm_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(layer.b_hh_cat), H.ptr(y), H.ptr(c), B, T, Hd, ND, prec,
-           H.ptr(ws), nbytes, st)
-    H.watch_abort(ws, release=True)
+    y, _c = F_hip.lstm_rec(layer, gates, B, T, prec)
     z = F_hip._empty((B, T2, Dz), x)
     _unalign(y, T * D, 0, z, lens, B, T, layer, T2, 4)
     if layer.layer_norm:
@@ -158,8 +140,7 @@ def encode_chunk(asr, feat, flen, with_ctc):
     tl, el = list(flen), list(flen)
     for layer in enc_m.layers:
         x = ragged_layer(layer, x, lens, asr.prec)
-        chain = [ragged_lengths(n, [layer.sample_rate], layer.sample_style) for n in tl]
-        tl = [c[0] for c in chain]
+        tl = [F_hip.out_frames(layer, n)[0] for n in tl]
         el = [e // layer.sample_rate if layer.sample_rate > 1 else e for e in el]
         lens = torch.tensor(tl, dtype=torch.int64, device=dev)
     enc = masked_copy(F_hip.to_f32(x), lens)

@@ -82,7 +82,14 @@ size_t asr_lstm_workspace_bytes(int B, int H, int ND);
  * 2 = persistent but first-generation kernels only (A/B measurements); returns the old value. */
 int asr_lstm_set_persistent(int on);
 /* which implementation the two calls below take for this shape: 0 = launch per time step, 1 = first-generation
- * persistent kernel, 2 = second-generation persistent kernel (tests assert the plan the bench shape must get) */
+ * persistent kernel, 2 = second-generation persistent kernel (tests assert the plan the bench shape must get).
+ * Both calls launch from the same host plan (csrc/lstm_plan.h).  The answer describes a call with a workspace of
+ * asr_lstm_workspace_bytes and 16-byte aligned tensors: alignment and the workspace are properties of a CALL, which the
+ * query cannot see, and demote at launch time - gates, y or c not 16-byte aligned: 2 -> 1; a workspace shorter than the
+ * generation needs: the next older generation, at last one launch per step; asr_lstm_fwd without a workspace, or with one
+ * that is not 256-byte aligned: one launch per step at once (asr_lstm_bwd rejects such a call with ASR_E_ARG).
+ * 1 covers both passes only where the first generation has a kernel for both (forward: H <= 320, B <= 64; backward:
+ * H % 16 == 0, B <= 64, an instantiated tile shape); a pass it does not cover runs one launch per step. */
 int asr_lstm_plan(int B, int T, int H, int ND, int prec);
 int asr_lstm_fwd(float* gates, const float* whh, const float* bias2, float* y, float* c,
                  int B, int T, int H, int ND, int prec,
