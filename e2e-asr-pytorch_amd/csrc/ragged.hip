@@ -3,15 +3,19 @@
 // unpadded pass of every utterance computes.  Direction 0 of the recurrence walks t = 0.. from the zero state: frames
 // 0..n-1 of a row see exactly the unpadded pass.  Direction 1 walks t = T-1.. from the zero state: it sees the unpadded pass
 // when the row's gate pre-activations are RIGHT-ALIGNED (frame t of the utterance at time row t + T - n), so that the walk
-// starts on the utterance's true last frame.  Two kernels, both pure copies (bit-exact, no arithmetic):
+// starts on the utterance's true last frame.  Two copy kernels (bit-exact, no arithmetic) and one store kernel:
 //
 //   asr_ragged_align   gates (B,T,ND,W) -> gates (B,T,ND,W): direction 0 copied at t < n, direction 1 shifted right by
 //                      T - n, zeros everywhere else (no source row at or past n is read).
 //   asr_ragged_unalign y (B,T,ND*H) -> z (B,T2,Dz): direction 1 shifted back, the layer's time down-sampling taken in the
 //                      same pass ('drop': frame t2*rate; 'concat': frames t2*rate .. t2*rate+rate-1 side by side), exact
 //                      zeros in every row past the row's output length (ceil(n/rate) / n/rate frames).
+//   asr_ragged_zero_tail  in place on an activation of a convolutional front-end seen as (B,Ttot,W): exact zeros in time rows
+//                      t_off + n .. t_off + T - 1 of every batch row, so that the next 3 x 3 convolution reads at t >= n the
+//                      zero padding the unpadded pass reads there (src/vgg.py: conv_stack_lens).  Nothing is read; valid
+//                      frames and the border rows of a bordered image (t_off = 1, Ttot = T + 2) are not touched.
 //
-// Both serve the fp32 layouts (elem_bytes = 4: gates (B,T,ND,4H), y (B,T,ND*H)) and the bf16 ones (elem_bytes = 2: gates16
+// All serve the fp32 layouts (elem_bytes = 4: gates (B,T,ND,4H), y (B,T,ND*H)) and the bf16 ones (elem_bytes = 2: gates16
 // (B,T,ND,H,4) whose (H,4) block is W = 4H contiguous elements, time-padded y16 through src_bstride / src_off).
 // Memory-bound: a thread moves 16 bytes along the contiguous extent when the extents and addresses allow it, one element
 // otherwise; a workgroup of 256 threads covers 256 / lanes-per-row rows, so the grid follows the data; the (b,t)
@@ -82,7 +86,25 @@ __global__ void ragged_unalign_kernel(RgP p, int Hv) {
     }
 }
 
-inline int lanes_log2_for(int units) {                 // smallest power of two >= units, at most 256 threads per row
+struct ZtP {
+    void* buf;
+    const int64_t* lens;      // (B); clamped to [0,T] on the device
+    long bstride, off;        // units of V: one batch row (Ttot * Wv), the first interior time row (t_off * Wv)
+    int T, Wv, chunks;        // workgroups per batch row
+};
+
+// The tail of batch row b is ONE contiguous span: (T - n) time rows of Wv units behind time row t_off + n.  `chunks`
+// workgroups stride over it; those that start behind its end (all of them when n = T) return without a store.
+template <typename V>
+__global__ void ragged_zero_tail_kernel(ZtP p) {
+    const int b = blockIdx.x / p.chunks, chunk = blockIdx.x - b * p.chunks;
+    const int n = clamp_len(p.lens, b, p.T);
+    const long span = (long)(p.T - n) * p.Wv;
+    V* dst = static_cast<V*>(p.buf) + (long)b * p.bstride + p.off + (long)n * p.Wv;
+    for (long k = (long)chunk * 256 + threadIdx.x; k < span; k += (long)p.chunks * 256) dst[k] = zero_of<V>();
+}
+
+inline int lanes_log2_for(int units) {                // smallest power of two >= units, at most 256 threads per row
     int l = 0;
     while (l < 8 && (1 << l) < units) ++l;
     return l;
@@ -133,5 +155,27 @@ extern "C" int asr_ragged_unalign(const void* src, long src_bstride, long src_of
     else if (elem_bytes == 4) hipLaunchKernelGGL(ragged_unalign_kernel<uint32_t>, grid, block, 0, st, p, Hv);
     else                      hipLaunchKernelGGL(ragged_unalign_kernel<uint16_t>, grid, block, 0, st, p, Hv);
     ASR_LAUNCH_CHECK("asr_ragged_unalign");
+    return ASR_OK;
+}
+
+extern "C" int asr_ragged_zero_tail(void* buf, const int64_t* lens, int B, int T, int Ttot, int t_off, int W, int elem_bytes,
+                                    asr_stream_t stream) {
+    ASR_REQUIRE(buf && lens, ASR_E_ARG, "asr_ragged_zero_tail: null pointer");
+    ASR_REQUIRE(B > 0 && T > 0 && W > 0 && t_off >= 0 && (long)t_off + T <= Ttot, ASR_E_ARG,
+                "asr_ragged_zero_tail: bad dims (B %d, T %d behind %d of %d time rows, W %d)", B, T, t_off, Ttot, W);
+    ASR_REQUIRE(elem_bytes == 4 || elem_bytes == 2, ASR_E_ARG, "asr_ragged_zero_tail: elem_bytes must be 4 (fp32) or 2 (bf16)");
+    ASR_REQUIRE((long)B * Ttot < (1L << 31) / 256, ASR_E_UNSUPPORTED, "asr_ragged_zero_tail: %ld time rows", (long)B * Ttot);
+    ASR_REQUIRE(((uintptr_t)buf & (uintptr_t)(elem_bytes - 1)) == 0, ASR_E_ARG, "asr_ragged_zero_tail: unaligned");
+    const int per = 16 / elem_bytes;
+    const bool vec = W % per == 0 && ((uintptr_t)buf & 15) == 0;          // then every time row starts on 16 bytes
+    const int Wv = vec ? W / per : W;
+    const long most = ((long)T * Wv + 255) / 256;                        // workgroups that cover a whole row's T frames once
+    ZtP p{buf, lens, (long)Ttot * Wv, (long)t_off * Wv, T, Wv, (int)(most < 256 ? most : 256)};
+    const dim3 grid((unsigned)((long)B * p.chunks)), block(256);          // B * chunks <= B * 256 < 2^31 by the row bound
+    hipStream_t st = (hipStream_t)stream;
+    if (vec)                  hipLaunchKernelGGL(ragged_zero_tail_kernel<uint4>, grid, block, 0, st, p);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(ragged_zero_tail_kernel<uint32_t>, grid, block, 0, st, p);
+    else                      hipLaunchKernelGGL(ragged_zero_tail_kernel<uint16_t>, grid, block, 0, st, p);
+    ASR_LAUNCH_CHECK("asr_ragged_zero_tail");
     return ASR_OK;
 }

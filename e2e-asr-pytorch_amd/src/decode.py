@@ -56,16 +56,19 @@ def encode_unpadded(asr, audio_feature, feature_len, with_ctc):
 
 @torch.no_grad()
 def encode_batched(asr, audio_feature, feature_len, with_ctc):
-    """encode_unpadded's result - same return contract, padding rows of enc and ctc exactly 0 - from ONE pass of every
-    encoder layer over the padded batch (src/ragged.py: the data is aligned per row, the recurrence launches are unchanged)
-    and one of the CTC head.  Agrees with encode_unpadded to rounding, not bit for bit.  The caller's feature padding is never
-    used.  More utterances than the recurrence takes at once (ragged.max_batch) go in chunks of that size; a model the pass
-    does not cover (ragged.ineligible_reason: GRU layers, a vgg front-end) is encoded by encode_unpadded."""
+    """encode_unpadded's result - same return contract, padding rows of enc and ctc exactly 0 - from ONE pass of the front-end
+    (vgg 1..7, when the model has one) and of every encoder layer over the padded batch (src/ragged.py: the data is aligned and
+    masked per row, the convolution and recurrence launches are unchanged) and one of the CTC head.  Agrees with
+    encode_unpadded to rounding, not bit for bit; tlen and enc_len are equal.  The caller's feature padding is never used,
+    nor are the n % time_div trailing frames a conv front-end drops.  More utterances than the recurrence takes at once
+    (ragged.max_batch) or than keep the largest front-end activation under ragged.FRONTEND_ACT_BYTES
+    (ragged.frontend_max_batch) go in chunks; a model the pass does not cover (ragged.ineligible_reason: GRU layers) is
+    encoded by encode_unpadded."""
     if ragged.ineligible_reason(asr) is not None:
         return encode_unpadded(asr, audio_feature, feature_len, with_ctc)
     dev = audio_feature.device
     flen = [int(x) for x in feature_len.reshape(-1).tolist()]
-    U, cap = audio_feature.shape[0], ragged.max_batch(asr)
+    U, cap = audio_feature.shape[0], min(ragged.max_batch(asr), ragged.frontend_max_batch(asr, max(flen)))
     parts = []
     for u0 in range(0, U, cap):
         fl = flen[u0:u0 + cap]

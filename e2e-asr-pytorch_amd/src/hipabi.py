@@ -142,6 +142,7 @@ SIGNATURES = {
     'asr_ctc_align': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_ragged_align': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'asr_ragged_unalign': [_vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    'asr_ragged_zero_tail': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     'asr_gemm16': [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     'asr_lstm16_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, ctypes.c_uint, _i, _vp],
     'asr_lstm16_bwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, ctypes.c_uint, _i, _vp],

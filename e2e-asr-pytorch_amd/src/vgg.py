@@ -390,3 +390,164 @@ class FreqVGGExtractor(nn.Module):
 class FreqVGGExtractor2(FreqVGGExtractor):
     def __init__(self, input_dim, split_freq, low_dim=4):
         super().__init__(input_dim, split_freq, low_dim, pool2_freq_only=True)
+
+
+# ---- inference over a padded batch of utterances of different lengths (src/ragged.py) ------------------------------------------
+class _Plain32(object):
+    """_VGGFn's layout for conv_stack_lens: unbordered fp32 images (B,t,f,C), the launches of _VGGFn.forward."""
+
+    def __init__(self, mod, prec, dev):
+        self.mod, self.prec, self.dev, self.st = mod, prec, dev, H.stream_ptr()
+
+    def first(self, feature):
+        mod = self.mod
+        B, T = feature.shape[0], feature.shape[1]
+        fs = getattr(mod, 'freq_slice', None)
+        if fs is not None:
+            feature = feature.reshape(B, T, mod.in_channel, -1)[..., fs[0]:fs[1]]
+        feature = feature.contiguous()
+        x = _e((B, T, mod.freq_dim, mod.in_channel), self.dev)
+        H.call('asr_permute_last2', H.ptr(feature), H.ptr(x), B * T, mod.in_channel, mod.freq_dim, self.st)
+        return x
+
+    def conv(self, li, cur, conv, ln, B, t, f):
+        Co, Ci = conv.weight.shape[0], conv.weight.shape[1]
+        wf = _e((Co, 9 * Ci), self.dev)
+        H.call('asr_conv_weight_permute', H.ptr(conv.weight), H.ptr(wf), Co, Ci, 0, self.st)
+        out = _e((B, t, f, Co), self.dev)
+        if ln is None:
+            H.call('asr_conv3x3', H.ptr(cur), H.ptr(wf), H.ptr(out), H.ptr(conv.bias), B, t, f, Ci, Co, 0, H.ACT_RELU, 0, self.prec, self.st)
+            return out
+        H.call('asr_conv3x3', H.ptr(cur), H.ptr(wf), H.ptr(out), H.ptr(conv.bias), B, t, f, Ci, Co, 0, H.ACT_NONE, 0, self.prec, self.st)
+        act, stats = _e((B, t, f, Co), self.dev), _e((B * t * Co, 2), self.dev)
+        H.call('asr_ln_freq_fwd', H.ptr(out), H.ptr(ln.weight), H.ptr(ln.bias), H.ptr(act), H.ptr(stats), B * t, f, Co, 1e-5, 1, self.st)
+        return act
+
+    def zero_tail(self, act, lens, B, t, f, Co):
+        H.call('asr_ragged_zero_tail', H.ptr(act), H.ptr(lens), B, t, t, 0, f * Co, 4, self.st)
+
+    def pool(self, act, B, t, f, Co, t2, f2, freq_only):
+        pooled, idx = _e((B, t2, f2, Co), self.dev), _e((B, t2, f2, Co), self.dev, torch.uint8)
+        if freq_only:          # MaxPool2d((1, 2)): the 2 x 2 kernel on the image seen as B*t images of ONE row
+            H.call('asr_maxpool2x2_fwd', H.ptr(act), H.ptr(pooled), H.ptr(idx), B * t, 1, f, Co, 1, f2, self.st)
+        else:
+            H.call('asr_maxpool2x2_fwd', H.ptr(act), H.ptr(pooled), H.ptr(idx), B, t, f, Co, t2, f2, self.st)
+        return pooled
+
+    def output(self, cur, B, t, f, Co):
+        out = _e((B, t, Co * f), self.dev)
+        H.call('asr_permute_last2', H.ptr(cur), H.ptr(out), B * t, f, Co, self.st)
+        return out
+
+
+class _Bordered16(object):
+    """_VGG16Fn's layout for conv_stack_lens: zero-bordered bf16 images (B,t+2,f+2,C), the launches of _VGG16Fn.forward."""
+
+    def __init__(self, mod, prec, dev):
+        self.mod, self.dev, self.st = mod, dev, H.stream_ptr()
+        self.K1p = (9 * mod.in_channel + 7) // 8 * 8
+
+    def first(self, feature):
+        return feature.contiguous().float()        # the first convolution reads its patch matrix straight off the features
+
+    def conv(self, li, cur, conv, ln, B, t, f):
+        Co, Ci = conv.weight.shape[0], conv.weight.shape[1]
+        Mp = B * (t + 2) * (f + 2)
+        f32 = 0 if ln is None else 1
+        out = _b16((Mp, Co), self.dev) if ln is None else _e((Mp, Co), self.dev)
+        act_code = H.ACT_RELU if ln is None else H.ACT_NONE
+        if li == 0:
+            K1p = self.K1p
+            x1, w16 = _b16((Mp, K1p), self.dev), _b16((Co, K1p), self.dev)
+            H.call('asr_vgg16_im2col', H.ptr(cur), H.ptr(x1), B, t, f, Ci, K1p, self.st)
+            H.call('asr_conv_weight_pack16', H.ptr(conv.weight), H.ptr(w16), Co, Ci, K1p, 0, self.st)
+            H.call('asr_conv3x3_16', H.ptr(x1), H.ptr(w16), H.ptr(out), H.ptr(conv.bias), B, t, f, Ci, Co, K1p, 0, act_code, f32, self.st)
+        else:
+            w16 = _b16((Co, 9 * Ci), self.dev)
+            H.call('asr_conv_weight_pack16', H.ptr(conv.weight), H.ptr(w16), Co, Ci, 9 * Ci, 0, self.st)
+            H.call('asr_conv3x3_16', H.ptr(cur), H.ptr(w16), H.ptr(out), H.ptr(conv.bias), B, t, f, Ci, Co, 9 * Ci, 1, act_code, f32, self.st)
+        if ln is None:
+            return out
+        act, stats = _b16((Mp, Co), self.dev), _e((B * (t + 2) * Co, 2), self.dev)
+        H.call('asr_ln_freq16_fwd', H.ptr(out), H.ptr(ln.weight), H.ptr(ln.bias), H.ptr(act), H.ptr(stats), B, t, f, Co, 1e-5, 1, self.st)
+        return act
+
+    def zero_tail(self, act, lens, B, t, f, Co):
+        H.call('asr_ragged_zero_tail', H.ptr(act), H.ptr(lens), B, t, t + 2, 1, (f + 2) * Co, 2, self.st)
+
+    def pool(self, act, B, t, f, Co, t2, f2, freq_only):
+        if freq_only:
+            raise NotImplementedError('frequency-only pooling has no kernel on the bordered bf16 images')
+        Mp2 = B * (t2 + 2) * (f2 + 2)
+        pooled, idx = _b16((Mp2, Co), self.dev), torch.empty((Mp2, Co), dtype=torch.uint8, device=self.dev)
+        H.call('asr_maxpool2x2_16_fwd', H.ptr(act), H.ptr(pooled), H.ptr(idx), B, t, f, Co, t2, f2, self.st)
+        return pooled
+
+    def output(self, cur, B, t, f, Co):
+        out = _b16((B, t, Co * f), self.dev)
+        H.call('asr_vgg16_output', H.ptr(cur), H.ptr(out), B, t, f, Co, self.st)
+        return out
+
+
+def conv_stack_lens(mod, lay, feature, lens, lens_dev):
+    """Inference-only forward of one conv stack (an extractor, or one band of a frequency-split one) over a padded batch, in
+    either layout (`lay`: _Plain32 / _Bordered16 - one loop, the launches of _VGGFn.forward / _VGG16Fn.forward).  feature
+    (B,T,D) fp32 with T % time_div == 0 and exact zeros at t >= lens[b]; lens: ints, multiples of time_div, max(lens) == T;
+    lens_dev(list) -> the int64 device tensor of a list of lengths.  Row b comes out as the unpadded pass of its lens[b] frames
+    (to rounding): that pass's 3 x 3 convolutions read zero padding at t = lens[b], where the padded batch holds
+    ReLU(bias + taps that reach into valid frames) (or the CNNLayerNorm of it) - so the tail of EVERY convolution's activation
+    is zeroed in place (asr_ragged_zero_tail) before anything reads it.  Pooling windows never straddle a row's end (lengths
+    are multiples of time_div) and pooling a zero tail gives zeros; a time pooling halves the lengths, a frequency-only one
+    does not.  Returns (out (B, T / time_div, C*F) with zero tails, lens / time_div)."""
+    B, T = feature.shape[0], feature.shape[1]
+    cur, t, f, lens = lay.first(feature), T, mod.freq_dim, list(lens)
+    freq_only2 = getattr(mod, 'pool2_freq_only', False)
+    for li, (conv, ln) in enumerate(mod.conv_layers()):
+        Co = conv.weight.shape[0]
+        act = lay.conv(li, cur, conv, ln, B, t, f)
+        if min(lens) < t:
+            lay.zero_tail(act, lens_dev(lens), B, t, f, Co)
+        if li == 3 and freq_only2:
+            cur, f = lay.pool(act, B, t, f, Co, t, f // 2, True), f // 2
+        elif li in (1, 3):
+            t2, f2 = ((t + 1) // 2, (f + 1) // 2) if mod.ceil_mode else (t // 2, f // 2)
+            cur, t, f, lens = lay.pool(act, B, t, f, Co, t2, f2, False), t2, f2, [n // 2 for n in lens]
+        else:
+            cur = act
+    return lay.output(cur, B, t, f, Co), lens
+
+
+def conv_time_div(ext):
+    """Frames a conv extractor folds into one (it drops n % time_div trailing frames first), None for any other front-end."""
+    if isinstance(ext, (_VGGBase, FreqVGGExtractor)):
+        return getattr(ext, 'time_div', 4)
+    return None
+
+
+def forward_lens(ext, feature, lens, prec):
+    """A conv extractor over a padded batch: conv_stack_lens in the layout ext.forward would take for this precision, both
+    bands and the concatenation for a frequency-split extractor.  Arguments and result as conv_stack_lens."""
+    dev, cache = feature.device, {}
+
+    def lens_dev(ls):
+        key = tuple(ls)
+        if key not in cache:
+            cache[key] = torch.tensor(ls, dtype=torch.int64, device=dev)
+        return cache[key]
+    if isinstance(ext, FreqVGGExtractor):
+        (lo, out_lens), (hi, _) = [conv_stack_lens(b, _Plain32(b, prec, dev), feature, lens, lens_dev) for b in ext._bands]
+        return torch.cat((lo, hi), dim=-1), out_lens
+    lay = _Bordered16 if not isinstance(ext, VGGExtractor2) and vgg16_ok(ext, prec) else _Plain32
+    return conv_stack_lens(ext, lay(ext, prec, dev), feature, lens, lens_dev)
+
+
+def largest_activation_bytes(ext, T, prec):
+    """Bytes of the largest single tensor conv_stack_lens holds for ONE batch row of T frames: the first two convolutions'
+    outputs (full resolution, init_dim channels; the later ones have twice the channels on a quarter of the pixels) - fp32
+    (T,F,C) unbordered, bf16 (T+2,F+2,C) bordered, the latter's CNNLayerNorm pre-activations fp32."""
+    if isinstance(ext, FreqVGGExtractor):
+        return T * max(b.freq_dim * b.seq[0].weight.shape[0] for b in ext._bands) * 4
+    if not isinstance(ext, VGGExtractor2) and vgg16_ok(ext, prec):
+        ln = ext.conv_layers()[0][1] is not None
+        return (T + 2) * (ext.freq_dim + 2) * ext.init_dim * (4 if ln else 2)
+    return T * ext.freq_dim * ext.init_dim * 4

@@ -187,6 +187,19 @@ int asr_ragged_align(const void* src, void* dst, const int64_t* lens, int B, int
                      asr_stream_t stream);
 int asr_ragged_unalign(const void* src, long src_bstride, long src_off, void* dst, const int64_t* lens, int B, int T,
                        int ND, int H, int T2, int rate, int style, int elem_bytes, asr_stream_t stream);
+/* Zero tails for a convolutional front-end on a padded batch (src/vgg.py::conv_stack_lens).  In place, stores only: buf is
+ * seen as (B, Ttot, W) elements of elem_bytes 4 or 2, and time rows t_off + clamp(lens[b],0,T) .. t_off + T - 1 of every batch
+ * row b become exact zeros - what the next 3 x 3 convolution of the unpadded pass reads behind the row's last frame.  Nothing
+ * else is written and nothing is read: valid frames, the rows in front of t_off and behind t_off + T keep their contents.
+ *   unbordered fp32 image (B,t,f,C)    : T = Ttot = t, t_off = 0, W = f*C, elem_bytes 4
+ *   zero-bordered image (B,t+2,f+2,C)  : T = t, Ttot = t+2, t_off = 1, W = (f+2)*C, elem_bytes 2 (bf16 activations) or 4 (the
+ *                                        fp32 pre-activations of a CNNLayerNorm)
+ * 16-byte stores when W*elem_bytes is a multiple of 16 and buf is 16-byte aligned, element-wise else; a batch row without a
+ * tail costs its workgroups one read of lens[b].  Null pointers, B, T, W < 1, t_off < 0, t_off + T > Ttot, another
+ * elem_bytes or a buf that is not elem_bytes-aligned return ASR_E_ARG; B*Ttot >= 2^23 rows returns ASR_E_UNSUPPORTED;
+ * nothing is launched then. */
+int asr_ragged_zero_tail(void* buf, const int64_t* lens, int B, int T, int Ttot, int t_off, int W, int elem_bytes,
+                         asr_stream_t stream);
 
 /* dpre = dout * act'(out) for act in {TANH, RELU} (autograd of torch.tanh / nn.ReLU on the path). */
 int asr_act_bwd(const float* dout, const float* out, float* dpre, long n, int act, asr_stream_t stream);

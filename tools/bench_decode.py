@@ -3,14 +3,16 @@ RNN-LM of config/librispeech_lm.yaml (4 x LSTM-1024, tied, random weights) with 
 U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Prints one JSON line.
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
        [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
-       [--ctc-only] [--batch-encode] [--lengths equal|librispeech]
+       [--ctc-only] [--batch-encode] [--lengths equal|librispeech] [--vgg N]
 The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one; --lm-module GRU
 fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one.  --ctc-only decodes the config's
 model built with ctc_weight = 1 (no attention decoder, no LM) by the CTC prefix beam search (csrc/ctc_decode.hip) and also
 times the search launch alone on the encoded batch.  --batch-encode measures, in the same process, the encoder pass alone and
 the whole decode with the per-utterance encoder pass (the default) and with the length-aware batched one
 (BeamDecoder(batch_encode=True), src/ragged.py): one warm-up each, then the median of --reps runs.  --lengths librispeech
-draws the U lengths from SURVEY 8d's length model clip(N(1270,480),150,2450) instead of --frames for every utterance."""
+draws the U lengths from SURVEY 8d's length model clip(N(1270,480),150,2450) instead of --frames for every utterance.  --vgg N
+overrides the yaml's encoder.vgg (0..7: the front-ends of src/vgg.py / src/module.py), so that --batch-encode measures the
+batched pass of a front-end model."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'e2e-asr-pytorch_amd')
@@ -29,6 +31,7 @@ ap.add_argument('--attention-mode'); ap.add_argument('--num-head', type=int); ap
 ap.add_argument('--lm-module', choices=('LSTM', 'GRU'), default='LSTM')
 ap.add_argument('--ctc-only', action='store_true')
 ap.add_argument('--batch-encode', action='store_true'); ap.add_argument('--lengths', choices=('equal', 'librispeech'), default='equal')
+ap.add_argument('--vgg', type=int, choices=range(8))
 a = ap.parse_args()
 torch.manual_seed(0)
 mc = yaml.safe_load(open(a.model_yaml))['model']
@@ -36,6 +39,7 @@ if a.attention_mode: mc['attention']['mode'] = a.attention_mode
 if a.num_head: mc['attention']['num_head'] = a.num_head
 if a.decoder_module: mc['decoder']['module'] = a.decoder_module
 if a.ctc_only: mc['ctc_weight'] = 1
+if a.vgg is not None: mc['encoder']['vgg'] = a.vgg
 model = ASR(160, 31, 1, prec=a.prec, **mc).cuda().eval()
 lmc = yaml.safe_load(open(os.path.join(PKG, 'config', 'librispeech_lm.yaml')))['model']
 lmc['module'] = a.lm_module
@@ -65,7 +69,7 @@ if a.batch_encode:
         return statistics.median(ts)
     res = {'metric': 'encoder pass per utterance vs batched, %s' % ('CTC-only model of config 4' if a.ctc_only else 'config 4'),
            'batch_utterances': U, 'lengths': a.lengths, 'frames': flen.tolist() if a.lengths != 'equal' else T, 'beam': a.beam,
-           'prec': a.prec, 'reps': a.reps}
+           'prec': a.prec, 'reps': a.reps, 'vgg': mc['encoder']['vgg']}
     for name, d in (('per_utterance', dec), ('batched', dec_b)):
         enc_ms = median_ms(lambda: d._encode(feat, flen))
         dec_ms = median_ms(lambda: d(feat, flen))
