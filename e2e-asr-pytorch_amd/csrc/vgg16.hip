@@ -20,6 +20,11 @@ namespace {
 
 inline int grid_for(long n) { long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
 __device__ __forceinline__ float bfv(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
+// a * b rounded to fp32 on its own, never contracted into a neighbouring add (__fmul_rn is a plain, contractable a * b here)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 
 // feature (B, T, Cin*F) fp32, channel-major -> patch matrix X1 (B*(T+2)*(F+2), Kp) bf16 over the bordered pixel grid:
 // X1[(b,tp,fp)][tap*Cin + ci] = feature[b, tp-1+dt, ci*F + fp-1+df] (0 outside the image; border rows all zero; columns >= 9*Cin zero)
@@ -188,8 +193,11 @@ __global__ __launch_bounds__(256) void ln_f16_bwd_kernel(const unsigned short* _
                 g = bfv(gp[(long)f * C]);
                 if (relu && (xh * w[f - 1] + bia[f - 1]) <= 0.f) g = 0.f;
             }
-            s1 += g * w[f - 1];
-            s2 += g * w[f - 1] * xh;
+            // g w is ROUNDED on its own, here and in the second loop: that loop must subtract the very product this one summed - at
+            // F = 1, where rstd = 1/sqrt(eps), a g w fused into `g w - s1` left rstd ulp(g w) where the gradient is exactly 0
+            const float gwp = mul_rounded(g, w[f - 1]);
+            s1 += gwp;
+            s2 += gwp * xh;
             const float gw = wave_sum(g * xh), gb = wave_sum(g);
             if ((threadIdx.x & 63) == 0) { atomicAdd(&s_dw[f - 1], gw); atomicAdd(&s_db[f - 1], gb); }
         }
@@ -204,7 +212,7 @@ __global__ __launch_bounds__(256) void ln_f16_bwd_kernel(const unsigned short* _
                     const float xh = (xp[(long)f * C] - mean) * rstd;
                     float g = bfv(gp[(long)f * C]);
                     if (relu && (xh * w[f - 1] + bia[f - 1]) <= 0.f) g = 0.f;
-                    o = rstd * (g * w[f - 1] - s1 - xh * s2);
+                    o = rstd * (mul_rounded(g, w[f - 1]) - s1 - xh * s2);
                 }
                 cb += o;
                 dp[(long)f * C] = f2bf_bits(o);
@@ -296,7 +304,8 @@ extern "C" int asr_maxpool2x2_16_fwd(const void* x, void* y, unsigned char* idx,
 }
 
 extern "C" int asr_maxpool2x2_16_bwd(const void* dy, const unsigned char* idx, void* dx, int B, int T, int F, int C, int T2, int F2, asr_stream_t stream) {
-    ASR_REQUIRE(dy && idx && dx && B > 0 && T > 0 && F > 0 && C > 0 && C % 8 == 0, ASR_E_ARG, "asr_maxpool2x2_16_bwd: bad args");
+    ASR_REQUIRE(dy && idx && dx && B > 0 && T > 0 && F > 0 && C > 0 && C % 8 == 0 && T2 > 0 && F2 > 0, ASR_E_ARG, "asr_maxpool2x2_16_bwd: bad args");
+    ASR_REQUIRE(2 * T2 - 1 <= T && 2 * F2 - 1 <= F, ASR_E_ARG, "asr_maxpool2x2_16_bwd: output larger than ceil(T/2) x ceil(F/2)");
     hipLaunchKernelGGL(maxpool16_bwd_kernel, dim3(grid_for((long)B * (T + 2) * (F + 2) * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)dy, idx, (unsigned short*)dx, B, T, F, C, T2, F2);
     ASR_LAUNCH_CHECK("asr_maxpool2x2_16_bwd");
