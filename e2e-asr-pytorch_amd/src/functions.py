@@ -20,8 +20,12 @@ def _empty(shape, like):
 
 
 # --------------------------------------------------------------------------------------------------
-# encoder RNN layer: BiLSTM -> [LayerNorm] -> dropout -> time down-sampling -> tanh(Linear)
-# (reference RNNLayer.forward, src/module.py:1040-1081)
+# encoder RNN layer: input projection -> BiLSTM -> [LayerNorm] -> dropout -> time down-sampling -> tanh(Linear)
+# (reference RNNLayer.forward, src/module.py:1040-1081).  Activations live in one of two storages, and a storage class owns every
+# launch of the layer: LayerF32 (fp32 tensors, any LayerNorm / down-sampling style; also the LM's LSTM stack) and LayerBF16 (the
+# encoder's working point in bf16 contraction mode: gate-minor bf16 gates, time-padded bf16 h, packed bf16 weights, batch-sliced
+# persistent recurrence of csrc/lstm_persist3.hip).  One loop in each direction (layer_forward, layer_backward) walks the stages,
+# for training (RNNLayerFn) and for inference over a padded batch (src/ragged.encode_chunk); rnn_fast_ok picks the storage.
 # --------------------------------------------------------------------------------------------------
 def out_frames(layer, T):
     """(T2, segs) of the layer's time down-sampling: 'drop' keeps ceil(T / rate) frames, 'concat' stacks T // rate groups of
@@ -32,140 +36,6 @@ def out_frames(layer, T):
     return ((T + r - 1) // r, 1) if layer.sample_style == 'drop' else (T // r, r)
 
 
-def lstm_rec(layer, gates, B, T, prec, dy=None, c=None):
-    """The fp32-storage recurrence of one layer on the current stream: forward (dy None; returns the new y, c) or backward
-    (dy, c given; `gates` becomes the gradient wrt the gate pre-activations).  The workspace is a pool area for this one launch
-    and goes back to the pool once its abort word has been collected."""
-    Hd, ND = layer.dim, layer.nd
-    nbytes = H.lib().asr_lstm_workspace_bytes(B, Hd, ND)
-    ws = H.handoff_acquire(nbytes, gates.device)
-    tail = (B, T, Hd, ND, prec, H.ptr(ws), nbytes, H.stream_ptr())
-    if dy is None:
-        y, c = _empty((B, T, ND * Hd), gates), _empty((B, T, ND, Hd), gates)
-        H.call('asr_lstm_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(layer.b_hh_cat), H.ptr(y), H.ptr(c), *tail)
-        layer.last_ws = ws
-        H.watch_abort(ws, release=True)
-        return y, c
-    pre = torch.cuda.Event()
-    pre.record(torch.cuda.current_stream())
-    H.call('asr_lstm_bwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(dy), H.ptr(c), *tail)
-    layer.last_ws_bwd = ws
-    H.watch_abort(ws, release=True)
-    H.flush_side(after=pre)       # the upper layer's parameter gradients run beside this recurrence (40 workgroups)
-    return None, c
-
-
-class RNNLayerFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, anchor, x, layer, train, seed, prec):
-        x = x.contiguous()
-        B, T, Din = x.shape
-        Hd, ND = layer.dim, layer.nd
-        G = ND * 4 * Hd
-        D = ND * Hd
-        st = H.stream_ptr()
-        gates = _empty((B, T, ND, 4 * Hd), x)
-        H.gemm(x, layer.w_ih_cat, gates, B * T, G, Din, Din, Din, G, 1, 1, bias=layer.b_ih_cat, prec=prec)
-        y, c = lstm_rec(layer, gates, B, T, prec)
-        yn, stats = y, None
-        if layer.layer_norm:
-            yn = _empty((B, T, D), x)
-            stats = _empty((B * T, 2), x)
-            H.call('asr_layernorm_fwd', H.ptr(y), H.ptr(layer.ln.weight), H.ptr(layer.ln.bias), H.ptr(yn), H.ptr(stats),
-                   B * T, D, 1e-5, 0, st)
-        p = float(layer.dropout) if train else 0.0
-        r, style = layer.sample_rate, (0 if layer.sample_style == 'drop' else 1)
-        T2, segs = out_frames(layer, T)
-        Dz = D * segs
-        alias = (r == 1 and p == 0.0)
-        if alias:
-            z = yn
-        else:
-            z = _empty((B, T2, Dz), x)
-            H.call('asr_dropout_downsample_fwd', H.ptr(yn), H.ptr(z), B, T, D, T2, r, style, p, seed, st)
-        if layer.proj:
-            out = _empty((B, T2, Dz), x)
-            H.linear_fwd(z.view(B * T2, Dz), layer.pj.weight, layer.pj.bias, out.view(B * T2, Dz), act=H.ACT_TANH, prec=prec)
-        else:
-            out = z
-        ctx.layer, ctx.prec, ctx.meta = layer, prec, (B, T, Din, T2, Dz, p, seed, alias, style)
-        ctx.need_dx = x.requires_grad
-        ctx.save_for_backward(x, gates, c, y, z, out, *( [stats] if stats is not None else []))
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        layer, prec = ctx.layer, ctx.prec
-        B, T, Din, T2, Dz, p, seed, alias, style = ctx.meta
-        saved = ctx.saved_tensors
-        x, gates, c, y, z, out = saved[:6]
-        stats = saved[6] if len(saved) > 6 else None
-        Hd, ND = layer.dim, layer.nd
-        G, D = ND * 4 * Hd, ND * Hd
-        st = H.stream_ptr()
-        dout = dout.contiguous()
-        if layer.dp is not None:
-            # every consumer of the encoder output has finished its backward: the heads/decoder bucket(s) can go - once whatever
-            # was deferred to the side stream (the decoder's parameter gradients under ASR_OVERLAP_DP) has been issued and joined
-            H.join_side()
-            for i in range(layer.bucket - 0):
-                layer.dp.bucket_ready(i)
-        if layer.proj:
-            dpre = _empty((B * T2, Dz), x)
-            H.call('asr_act_bwd', H.ptr(dout), H.ptr(out), H.ptr(dpre), B * T2 * Dz, H.ACT_TANH, st)
-            dz = _empty((B, T2, Dz), x)
-            H.linear_bwd(z.view(B * T2, Dz), layer.pj.weight, dpre, layer.pj.weight.grad, layer.pj.bias.grad,
-                         dz.view(B * T2, Dz), prec=prec)
-        else:
-            dz = dout
-        if alias:
-            dyn = dz
-        else:
-            dyn = _empty((B, T, D), x)
-            H.call('asr_dropout_downsample_bwd', H.ptr(dz), H.ptr(dyn), B, T, D, T2, layer.sample_rate, style, p, seed, st)
-        if layer.layer_norm:
-            dy = _empty((B, T, D), x)
-            H.call('asr_layernorm_bwd', H.ptr(dyn), H.ptr(y), H.ptr(layer.ln.weight), H.ptr(layer.ln.bias), H.ptr(stats),
-                   H.ptr(dy), H.ptr(layer.ln.weight.grad), H.ptr(layer.ln.bias.grad), B * T, D, 0, st)
-        else:
-            dy = dyn
-        lstm_rec(layer, gates, B, T, prec, dy, c)
-        # gates now holds the gradient wrt the gate pre-activations
-        g2 = gates.view(B * T, G)
-        x2 = x.view(B * T, Din)
-        y2 = y.view(B * T, D)
-        splits_ih = H.wgrad_splits(B * T, G, Din)
-        splits_hh = H.wgrad_splits(B * T, 4 * Hd, Hd)
-
-        def weight_grads():
-            s_ = H.stream_ptr()
-            H.gemm(g2, x2, layer.g_w_ih_cat, G, Din, B * T, G, Din, Din, 0, 0, accum=1, splits=splits_ih, prec=prec)
-            H.call('asr_colsum2', H.ptr(g2), G, B * T, G, H.ptr(layer.g_b_ih_cat), H.ptr(layer.g_b_hh_cat), s_)
-            for d in range(ND):
-                H.gemm(g2[:, d * 4 * Hd:], y2[:, d * Hd:], layer.g_w_hh_cat[d], 4 * Hd, Hd, B * T, G, D, Hd, 0, 0,
-                       accum=1, splits=splits_hh, seqT=T, bshift=(-1 if d == 0 else 1), prec=prec)
-
-        # the input gradient continues the chain; the parameter gradients of this layer are needed only by the optimizer
-        # and run beside the next layer's recurrence on the side stream (single-process runs; under data parallelism they
-        # stay in order so that the bucket's all-reduce can start right behind them)
-        use_side = H.side_enabled() and layer.dp is None
-        if use_side:
-            H.defer_side(weight_grads, gates, x, y)      # issued behind the NEXT layer's recurrence launch (flush_side below)
-        dx = None
-        if ctx.need_dx:
-            dx = _empty((B, T, Din), x)
-            H.gemm(g2, layer.w_ih_cat, dx, B * T, Din, G, G, Din, Din, 1, 0, prec=prec)
-        if not use_side:
-            weight_grads()
-        if layer.dp is not None:
-            layer.dp.bucket_ready(layer.bucket)
-        return None, dx, None, None, None, None
-
-
-# --------------------------------------------------------------------------------------------------
-# the same layer on bf16 storage (bf16 contraction mode, the encoder's working point): gate-minor bf16 gates,
-# time-padded bf16 h, batch-sliced persistent recurrence (csrc/lstm_persist3.hip), bf16 contraction operands
-# --------------------------------------------------------------------------------------------------
 def _empty16(shape, like):
     return torch.empty(shape, dtype=torch.bfloat16, device=like.device)
 
@@ -206,8 +76,8 @@ def to_f32_fn(x):
 
 
 def fast16_layer_ok(layer, B, Din):
-    """What the bf16-storage path asks of a layer: LSTM cell, H % 16 == 0 <= 512, no LayerNorm, 'drop' down-sampling (or
-    none), input width a multiple of 8, B <= 16 * (8 / directions)."""
+    """What the bf16 storage asks of a layer: LSTM cell, H % 16 == 0 <= 512, no LayerNorm, 'drop' down-sampling (or none),
+    input width a multiple of 8, B <= 16 * (8 / directions)."""
     if layer.layer_norm or (layer.sample_rate > 1 and layer.sample_style != 'drop'):
         return False
     if Din % 8 != 0 or (layer.nd * layer.dim) % 8 != 0:
@@ -216,46 +86,366 @@ def fast16_layer_ok(layer, B, Din):
 
 
 def rnn_fast_ok(layer, x, prec):
-    """The bf16-storage path covers: bf16 contractions and the layers of fast16_layer_ok."""
+    """LayerBF16 covers: bf16 contractions and the layers of fast16_layer_ok; everything else runs on LayerF32."""
     return prec == H.BF16 and H.fast16_enabled() and fast16_layer_ok(layer, x.shape[0], x.shape[2])
 
 
-def _ws16(layer, B, bwd):
-    """Persistent, zero-initialised workspace of the recurrence per (layer, batch, pass) + its launch counter."""
-    key = (B, bwd)
-    cache = layer.__dict__.setdefault('_ws16_cache', {})
-    dev = layer.w_hh_cat.device
-    if key not in cache or cache[key][0].device != dev:
-        n = int(H.lib().asr_lstm16_workspace_bytes(B, layer.dim, layer.nd, bwd))
-        ws = H.handoff_acquire(n, dev)                    # pool area: scrubbed from every XCD, never returned to the allocator
-        weakref.finalize(layer, H.handoff_release, ws)    # the layer's areas go back to the POOL when the layer dies
-        cache[key] = [ws, 0]
-    ent = cache[key]
-    ent[1] += 1
-    return ent[0], ent[1]
+class _LayerStorage(object):
+    """One layer at one input shape (B,T,Din): the shape arithmetic every stage shares, and the stages that differ between the
+    storages only in the element size, in the `pad` zero frames around y and in the entry point's name."""
+
+    def __init__(self, layer, prec, shape):
+        self.layer, self.prec = layer, prec
+        self.B, self.T, self.Din = shape
+        self.Hd, self.ND = layer.dim, layer.nd
+        self.G, self.D = self.ND * 4 * self.Hd, self.ND * self.Hd
+        self.T2, self.segs = out_frames(layer, self.T)
+        self.Dz = self.D * self.segs
+        self.style = 0 if layer.sample_style == 'drop' else 1
+        self.y_bstride, self.y_off = (self.T + 2 * self.pad) * self.D, self.pad * self.D       # frame 0 of y sits behind the leading pad
+
+    def inputs(self, x):
+        return self.cast(x)
+
+    def align(self, raw, lens):
+        """Direction 0 of the gate pre-activations masked to the row's frames, direction 1 right-aligned."""
+        gates = torch.empty_like(raw)
+        H.call('asr_ragged_align', H.ptr(raw), H.ptr(gates), H.ptr(lens), self.B, self.T, self.ND, 4 * self.Hd, self.esize, H.stream_ptr())
+        return gates
+
+    def unalign(self, y, lens):
+        """Direction 1 of y shifted back, exact zeros past the row's length, the time down-sampling taken."""
+        z = self.new((self.B, self.T2, self.Dz), y)
+        H.call('asr_ragged_unalign', H.ptr(y), self.y_bstride, self.y_off, H.ptr(z), H.ptr(lens), self.B, self.T, self.ND, self.Hd, self.T2,
+               self.layer.sample_rate, self.style, self.esize, H.stream_ptr())
+        return z
+
+    def act_bwd(self, dout, out):
+        dpre = self.new((self.B * self.T2, self.Dz), out)
+        H.call(self.act_bwd_entry, H.ptr(dout), H.ptr(out), H.ptr(dpre), dpre.numel(), H.ACT_TANH, H.stream_ptr())
+        return dpre
 
 
-def lstm16_rec(layer, gates, B, T, reserved, dy=None, c=None, beside=False):
-    """The bf16-storage recurrence of one layer: forward (dy None; returns the new time-padded y and c) or backward (dy, c given;
-    `gates` becomes the gradient wrt the gate pre-activations).  Owns the layer's persistent workspace and its abort words: two
-    status blocks by launch parity (include/asr_hip.h), this launch reports in block epoch & 1 and clears the other one.
-    beside=True: launched on the CU-masked recurrence stream, and the deferred side-stream work is flushed to start with it."""
-    Hd, ND, bwd = layer.dim, layer.nd, dy is not None
-    ws, epoch = _ws16(layer, B, int(bwd))
-    H.abort_guard(ws, ((epoch + 1) & 1) * 1024)
-    y = None if bwd else _empty16((B, T + 2, ND * Hd), gates)      # rows 0 and T+1 (time pads) are zeroed by the recurrence kernel
-    c = c if bwd else _empty((B, T, ND, Hd), gates)
-    pre = torch.cuda.Event() if beside else None
-    if beside:
+class LayerF32(_LayerStorage):
+    """fp32 tensors: gates (B,T,ND,4H), y (B,T,D); the contractions round their operands to `prec` when they stage them.  Never
+    defers its parameter gradients and never runs its recurrence beside them: measured, the fp32 contractions beside the
+    recurrence slow it and each other and the step gains nothing."""
+    overlaps, esize, pad, act_bwd_entry = False, 4, 0, 'asr_act_bwd'
+    new, cast = staticmethod(_empty), staticmethod(to_f32)
+
+    def project(self, x):
+        gates = _empty((self.B, self.T, self.ND, 4 * self.Hd), x)
+        H.gemm(x, self.layer.w_ih_cat, gates, self.B * self.T, self.G, self.Din, self.Din, self.Din, self.G, 1, 1,
+               bias=self.layer.b_ih_cat, prec=self.prec)
+        return gates
+
+    def _rec_workspace(self, gates):
+        """A pool area for this one launch (it goes back to the pool once its abort word has been collected) and the
+        arguments both recurrence entry points end with."""
+        nbytes = H.lib().asr_lstm_workspace_bytes(self.B, self.Hd, self.ND)
+        ws = H.handoff_acquire(nbytes, gates.device)
+        return ws, (self.B, self.T, self.Hd, self.ND, self.prec, H.ptr(ws), nbytes, H.stream_ptr())
+
+    def rec_fwd(self, gates, reserved=0):
+        """`reserved` is not used: the fp32 recurrence kernels take no CU reservation."""
+        layer = self.layer
+        ws, tail = self._rec_workspace(gates)
+        y, c = _empty((self.B, self.T, self.D), gates), _empty((self.B, self.T, self.ND, self.Hd), gates)
+        H.call('asr_lstm_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(layer.b_hh_cat), H.ptr(y), H.ptr(c), *tail)
+        H.watch_abort(ws, release=True)
+        return y, c
+
+    def rec_bwd(self, gates, dy, c, reserved=0, beside=False):
+        """`gates` becomes the gradient wrt the gate pre-activations.  Always in line on the current stream (`reserved` and `beside`
+        are LayerBF16's and not used here); what the layers above, the decoder and the CTC head deferred starts with it."""
+        ws, tail = self._rec_workspace(gates)
+        pre = torch.cuda.Event()
         pre.record(torch.cuda.current_stream())
-    with (H.on_rec_stream() if beside else contextlib.nullcontext()):
-        H.call('asr_lstm16_bwd' if bwd else 'asr_lstm16_fwd', H.ptr(gates), H.ptr(layer.w_hh_cat), H.ptr(dy if bwd else y), H.ptr(c),
-               B, T, Hd, ND, H.ptr(ws), ws.numel(), epoch, reserved, H.stream_ptr())
-    if beside:
-        H.flush_side(after=pre)       # the deferred gradients (layer above, this layer's projection) start with this recurrence
-    H.watch_abort(ws, (epoch & 1) * 1024)
-    setattr(layer, 'last_ws_bwd' if bwd else 'last_ws', ws)
-    return y, c
+        H.call('asr_lstm_bwd', H.ptr(gates), H.ptr(self.layer.w_hh_cat), H.ptr(dy), H.ptr(c), *tail)
+        H.watch_abort(ws, release=True)
+        H.flush_side(after=pre)
+
+    def layer_norm(self, y, rows):
+        ln = self.layer.ln
+        yn, stats = torch.empty_like(y), _empty((rows, 2), y)
+        H.call('asr_layernorm_fwd', H.ptr(y), H.ptr(ln.weight), H.ptr(ln.bias), H.ptr(yn), H.ptr(stats), rows, self.D, 1e-5, 0, H.stream_ptr())
+        return yn, stats
+
+    def layer_norm_bwd(self, dyn, y, stats):
+        ln = self.layer.ln
+        dy = torch.empty_like(y)
+        H.call('asr_layernorm_bwd', H.ptr(dyn), H.ptr(y), H.ptr(ln.weight), H.ptr(ln.bias), H.ptr(stats), H.ptr(dy), H.ptr(ln.weight.grad),
+               H.ptr(ln.bias.grad), self.B * self.T, self.D, 0, H.stream_ptr())
+        return dy
+
+    def downsample(self, yn, p, seed):
+        """Dropout + time down-sampling; with neither, z IS yn and nothing is launched (in either direction)."""
+        if self.layer.sample_rate == 1 and p == 0.0:
+            return yn
+        z = _empty((self.B, self.T2, self.Dz), yn)
+        H.call('asr_dropout_downsample_fwd', H.ptr(yn), H.ptr(z), self.B, self.T, self.D, self.T2, self.layer.sample_rate, self.style, p, seed,
+               H.stream_ptr())
+        return z
+
+    def downsample_bwd(self, dz, p, seed):
+        if self.layer.sample_rate == 1 and p == 0.0:
+            return dz
+        dyn = _empty((self.B, self.T, self.D), dz)
+        H.call('asr_dropout_downsample_bwd', H.ptr(dz), H.ptr(dyn), self.B, self.T, self.D, self.T2, self.layer.sample_rate, self.style, p, seed,
+               H.stream_ptr())
+        return dyn
+
+    def out_proj(self, z):
+        pj, rows = self.layer.pj, self.B * self.T2
+        out = _empty((self.B, self.T2, self.Dz), z)
+        H.linear_fwd(z.view(rows, self.Dz), pj.weight, pj.bias, out.view(rows, self.Dz), act=H.ACT_TANH, prec=self.prec)
+        return out
+
+    def pj_grads(self, dpre, z):
+        pj = self.layer.pj
+        H.linear_bwd(z.view(self.B * self.T2, self.Dz), pj.weight, dpre, pj.weight.grad, pj.bias.grad, None, prec=self.prec)
+
+    def pj_input_grad(self, dpre):
+        dz = _empty((self.B, self.T2, self.Dz), dpre)
+        H.linear_bwd_input(self.layer.pj.weight, dpre, dz.view(self.B * self.T2, self.Dz), prec=self.prec)
+        return dz
+
+    def input_grad(self, gates):
+        dx, rows = _empty((self.B, self.T, self.Din), gates), self.B * self.T
+        H.gemm(gates.view(rows, self.G), self.layer.w_ih_cat, dx, rows, self.Din, self.G, self.G, self.Din, self.Din, 1, 0, prec=self.prec)
+        return dx
+
+    def weight_grads(self, gates, x, y):
+        layer, rows, Hd, G, D, Din = self.layer, self.B * self.T, self.Hd, self.G, self.D, self.Din
+        g2, x2, y2 = gates.view(rows, G), x.view(rows, Din), y.view(rows, D)
+        H.gemm(g2, x2, layer.g_w_ih_cat, G, Din, rows, G, Din, Din, 0, 0, accum=1, splits=H.wgrad_splits(rows, G, Din), prec=self.prec)
+        H.call('asr_colsum2', H.ptr(g2), G, rows, G, H.ptr(layer.g_b_ih_cat), H.ptr(layer.g_b_hh_cat), H.stream_ptr())
+        splits_hh = H.wgrad_splits(rows, 4 * Hd, Hd)
+        for d in range(self.ND):       # dW_hh = sum_t dgates_t^T h_{t -+ 1}: rows of y shifted one step against the direction's walk
+            H.gemm(g2[:, d * 4 * Hd:], y2[:, d * Hd:], layer.g_w_hh_cat[d], 4 * Hd, Hd, rows, G, D, Hd, 0, 0,
+                   accum=1, splits=splits_hh, seqT=self.T, bshift=(-1 if d == 0 else 1), prec=self.prec)
+
+
+class LayerBF16(_LayerStorage):
+    """bf16 tensors: gates gate-minor (B,T,ND,H,4), y time-padded (B,T+2,D) with zero rows 0 and T+1 (written by the recurrence
+    kernel), contraction operands packed to bf16 (`packed`); c and the parameter gradients stay fp32.  No LayerNorm and no
+    'concat' (fast16_layer_ok).  Its parameter gradients may be deferred to the side stream and its backward recurrence may run
+    beside them on the complementary CU mask (layer_backward).  `pk`, the packed weights, is set by the first stage, `inputs`, and
+    read by every contraction behind it, the backward's included."""
+    overlaps, esize, pad, act_bwd_entry = True, 2, 1, 'asr_act_bwd16'
+    new, cast = staticmethod(_empty16), staticmethod(to_bf16)
+
+    @staticmethod
+    def packed(layer, side=False):
+        """bf16 operand copies of the layer's contraction weights, rebuilt from the fp32 master by ONE kernel per call."""
+        Hd, ND = layer.dim, layer.nd
+        G, Din, D = ND * 4 * Hd, layer.w_ih_cat.shape[1], ND * Hd
+        dev = layer.w_ih_cat.device
+        pk = layer.__dict__.get('_pack16')
+        if pk is None or pk['wih'].device != dev:
+            b16 = lambda *s_: torch.empty(s_, dtype=torch.bfloat16, device=dev)
+            pk = {'wih': b16(G, Din), 'wihT': b16(Din, G), 'bias': torch.empty(G, dtype=torch.float32, device=dev),
+                  'pj': b16(D, D) if layer.proj else None, 'pjT': b16(D, D) if layer.proj else None}
+            layer.__dict__['_pack16'] = pk
+        ev = layer.__dict__.pop('_pack16_ev', None)
+        if ev is not None and not side:
+            torch.cuda.current_stream().wait_event(ev)       # packed ahead on the side stream (prepack16) in this forward
+            return pk
+        H.call('asr_rnn_pack_weights', H.ptr(layer.w_ih_cat), H.ptr(layer.b_ih_cat), H.ptr(layer.b_hh_cat),
+               H.ptr(layer.pj.weight) if layer.proj else None, H.ptr(pk['wih']), H.ptr(pk['wihT']), H.ptr(pk['bias']),
+               H.ptr(pk['pj']), H.ptr(pk['pjT']), Hd, ND, Din, D, H.stream_ptr())
+        return pk
+
+    def inputs(self, x):
+        x16 = self.cast(x)
+        self.pk = self.packed(self.layer)       # kept with the storage object from forward to backward
+        return x16
+
+    def project(self, x16):
+        gates = _empty16((self.B, self.T, self.ND, self.Hd, 4), x16)
+        H.gemm16(x16, self.pk['wih'], gates, self.B * self.T, self.G, self.Din, self.Din, self.Din, self.G, 1, 1, bias=self.pk['bias'])
+        return gates
+
+    def _workspace(self, bwd):
+        """Persistent, zero-initialised workspace of the recurrence per (layer, batch, pass) + its launch counter."""
+        layer, key = self.layer, (self.B, bwd)
+        cache = layer.__dict__.setdefault('_ws16_cache', {})
+        dev = layer.w_hh_cat.device
+        if key not in cache or cache[key][0].device != dev:
+            n = int(H.lib().asr_lstm16_workspace_bytes(self.B, self.Hd, self.ND, bwd))
+            ws = H.handoff_acquire(n, dev)                    # pool area: scrubbed from every XCD, never returned to the allocator
+            weakref.finalize(layer, H.handoff_release, ws)    # the layer's areas go back to the POOL when the layer dies
+            cache[key] = [ws, 0]
+        ent = cache[key]
+        ent[1] += 1
+        return ent[0], ent[1]
+
+    def _rec(self, bwd, gates, buf, c, reserved, beside):
+        """One recurrence launch.  Owns the layer's persistent workspace and its abort words: two status blocks by launch parity
+        (include/asr_hip.h), this launch reports in block epoch & 1 and clears the other one.  beside=True: launched on the
+        CU-masked recurrence stream, and the deferred side-stream work is flushed to start with it."""
+        ws, epoch = self._workspace(int(bwd))
+        H.abort_guard(ws, ((epoch + 1) & 1) * 1024)
+        pre = torch.cuda.Event() if beside else None
+        if beside:
+            pre.record(torch.cuda.current_stream())
+        with (H.on_rec_stream() if beside else contextlib.nullcontext()):
+            H.call('asr_lstm16_bwd' if bwd else 'asr_lstm16_fwd', H.ptr(gates), H.ptr(self.layer.w_hh_cat), H.ptr(buf), H.ptr(c),
+                   self.B, self.T, self.Hd, self.ND, H.ptr(ws), ws.numel(), epoch, reserved, H.stream_ptr())
+        if beside:
+            H.flush_side(after=pre)       # the deferred gradients (layer above, this layer's projection) start with this recurrence
+        H.watch_abort(ws, (epoch & 1) * 1024)
+
+    def rec_fwd(self, gates, reserved=0):
+        y, c = _empty16((self.B, self.T + 2 * self.pad, self.D), gates), _empty((self.B, self.T, self.ND, self.Hd), gates)
+        self._rec(False, gates, y, c, reserved, False)
+        return y, c
+
+    def rec_bwd(self, gates, dy, c, reserved=0, beside=False):
+        """`gates` becomes the gradient wrt the gate pre-activations (gate-minor)."""
+        self._rec(True, gates, dy, c, reserved, beside)
+
+    def downsample(self, y, p, seed):
+        z = _empty16((self.B, self.T2, self.D), y)
+        H.call('asr_dropout_downsample16_fwd', H.ptr(y), self.y_bstride, self.y_off, H.ptr(z), self.B, self.T, self.D, self.T2,
+               self.layer.sample_rate, 0, p, seed, H.stream_ptr())
+        return z
+
+    def downsample_bwd(self, dz, p, seed):
+        dy = _empty16((self.B, self.T, self.D), dz)
+        H.call('asr_dropout_downsample16_bwd', H.ptr(dz), H.ptr(dy), self.B, self.T, self.D, self.T2, self.layer.sample_rate, 0, p, seed,
+               H.stream_ptr())
+        return dy
+
+    def out_proj(self, z):
+        D, out = self.D, _empty16((self.B, self.T2, self.D), z)
+        H.gemm16(z, self.pk['pj'], out, self.B * self.T2, D, D, D, D, D, 1, 1, bias=self.layer.pj.bias, act=H.ACT_TANH)
+        return out
+
+    def pj_grads(self, dpre, z):
+        pj, D, rows = self.layer.pj, self.D, self.B * self.T2
+        H.gemm16(dpre, z, pj.weight.grad, D, D, rows, D, D, D, 0, 0, accum=1, splits=H.wgrad_splits(rows, D, D))
+        H.call('asr_colsum16', H.ptr(dpre), D, rows, D, H.ptr(pj.bias.grad), None, 0, H.stream_ptr())
+
+    def pj_input_grad(self, dpre):
+        D, dz = self.D, _empty16((self.B, self.T2, self.D), dpre)
+        H.gemm16(dpre, self.pk['pjT'], dz, self.B * self.T2, D, D, D, D, D, 1, 1)
+        return dz
+
+    def input_grad(self, gates):
+        dx = _empty16((self.B, self.T, self.Din), gates)
+        H.gemm16(gates, self.pk['wihT'], dx, self.B * self.T, self.Din, self.G, self.G, self.G, self.Din, 1, 1)
+        return dx
+
+    def weight_grads(self, gates, x16, y):
+        """Parameter gradients in reference row order (perm_h undoes the gate-minor layout)."""
+        layer, rows, Hd, G, D, Din = self.layer, self.B * self.T, self.Hd, self.G, self.D, self.Din
+        H.gemm16(gates, x16, layer.g_w_ih_cat, G, Din, rows, G, Din, Din, 0, 0, accum=1, splits=H.wgrad_splits(rows, G, Din), perm_h=Hd)
+        H.call('asr_colsum16', H.ptr(gates), G, rows, G, H.ptr(layer.g_b_ih_cat), H.ptr(layer.g_b_hh_cat), Hd, H.stream_ptr())
+        splits_hh = H.wgrad_splits(rows, 4 * Hd, Hd)
+        for d in range(self.ND):
+            H.gemm16(gates, y, layer.g_w_hh_cat[d], 4 * Hd, Hd, rows, G, D, Hd, 0, 0, accum=1, splits=splits_hh,
+                     perm_h=Hd, seqT=self.T, bshift=(-1 if d == 0 else 1), b_time_padded=1, a_off=d * 4 * Hd, b_off=d * Hd)
+
+
+def layer_forward(s, x, train=False, seed=0, lens=None, save=None):
+    """Forward of one layer on the storage object `s` (made for x's shape): x (B,T,Din), fp32 or bf16 -> (B,T2,Dz) in s's storage.
+
+    save: a dict that receives what layer_backward reads (training).
+
+    lens: inference over a padded batch - int64 (B) on the device, max(lens) == T, rows of x at t >= lens[b] arbitrary (never
+    used).  Row b comes out as the unpadded pass of its lens[b] frames (to rounding): the gate pre-activations are aligned
+    behind the projection (the reverse walk starts from the zero state on the row's true last frame), asr_ragged_unalign takes
+    the place of dropout + down-sampling, and the LayerNorm, per frame, follows it over the B * T2 * segs frames that survive
+    (a 'concat' row is `segs` frames side by side).  Rows past the layer's output length hold tanh(bias) when the layer projects,
+    the LayerNorm bias behind a LayerNorm, else zeros: the NEXT align ignores them.  Nothing is kept."""
+    layer = s.layer
+    if lens is not None and s.T2 == 0:
+        raise ValueError("every utterance is shorter than the 'concat' rate %d of an encoder layer: no frame comes out" % layer.sample_rate)
+    x = s.inputs(x)
+    gates = s.project(x)
+    if lens is not None:
+        gates = s.align(gates, lens)
+    # training under data parallelism: 64 compute units stay with the all-reduce kernels
+    reserved = 64 if (lens is None and layer.dp is not None and layer.dp.world > 1) else 0
+    y, c = s.rec_fwd(gates, reserved)
+    p, stats = float(layer.dropout) if train else 0.0, None
+    if lens is not None:
+        z = s.unalign(y, lens)
+        if layer.layer_norm:
+            z = s.layer_norm(z, s.B * s.T2 * s.segs)[0]
+    else:
+        yn = y
+        if layer.layer_norm:
+            yn, stats = s.layer_norm(y, s.B * s.T)
+        z = s.downsample(yn, p, seed)
+    out = s.out_proj(z) if layer.proj else z
+    if save is not None:
+        save.update(tensors=(x, gates, c, y, z, out) + (() if stats is None else (stats,)), p=p, seed=seed, reserved=reserved)
+    return out
+
+
+def layer_backward(s, tensors, kept, dout, need_dx, in_dtype):
+    """dout (B,T2,Dz), the gradient of layer_forward's output, walked back through what it saved: returns the gradient of its
+    input (None without need_dx; fp32 when the input came in as fp32, else in s's storage); the parameter gradients go into
+    the layer's flat gradient views."""
+    layer, dp = s.layer, s.layer.dp
+    x, gates, c, y, z, out = tensors[:6]
+    # Parameter gradients are off the critical path (only the optimizer reads them).  On a storage that `overlaps` they are
+    # deferred to the CU-masked side stream and start together with the NEXT recurrence of the backward pass, which then runs on
+    # the complementary CU mask (H.on_rec_stream: 8 * REC_UNITS compute units, the others reserved) - unless ASR_OVERLAP=0, or
+    # under data parallelism without ASR_OVERLAP_DP=1.  A gradient bucket may be signalled only when everything that writes into
+    # it has been issued: in line the signals stay where they were; deferred, they are deferred too, FIFO behind the work they
+    # depend on, and fire on the side stream.  A storage that does not overlap first runs in line whatever the decoder and the
+    # layers above deferred (H.join_side), since their buckets are signalled here.
+    defer = s.overlaps and H.overlap_enabled() and (dp is None or H.overlap_dp_enabled())
+    later = H.defer_side if defer else (lambda fn, *keep: fn())
+    dout = s.cast(dout)
+    if dp is not None:
+        # every consumer of this layer's output has finished its backward: the buckets of the heads / decoder / upper layers can go
+        if not s.overlaps:
+            H.join_side()
+        def earlier_buckets():
+            for i in range(layer.bucket):
+                dp.bucket_ready(i)
+        later(earlier_buckets)
+    if layer.proj:
+        dpre = s.act_bwd(dout, out)
+        later(lambda: s.pj_grads(dpre, z), dpre, z)
+        dz = s.pj_input_grad(dpre)
+    else:
+        dz = dout
+    dy = s.downsample_bwd(dz, kept['p'], kept['seed'])
+    if layer.layer_norm:
+        dy = s.layer_norm_bwd(dy, y, tensors[6])
+    s.rec_bwd(gates, dy, c, 256 - 8 * H.REC_UNITS if defer else kept['reserved'], beside=defer)
+    # gates now holds the gradient wrt the gate pre-activations; the input gradient continues the chain
+    dx = None
+    if need_dx:
+        dx = s.input_grad(gates)
+        if in_dtype == torch.float32:
+            dx = to_f32(dx)
+    later(lambda: s.weight_grads(gates, x, y), gates, x, y)
+    if dp is not None:
+        later(lambda: dp.bucket_ready(layer.bucket))
+    return dx
+
+
+class RNNLayerFn(torch.autograd.Function):
+    """Training pass of one layer on the storage class `storage`: x fp32 for LayerF32, fp32 or bf16 for LayerBF16."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, layer, train, seed, prec, storage):
+        ctx.store, ctx.kept = storage(layer, prec, x.shape), {}
+        ctx.need_dx, ctx.in_dtype = x.requires_grad, x.dtype
+        out = layer_forward(ctx.store, x, train, seed, save=ctx.kept)
+        ctx.save_for_backward(*ctx.kept.pop('tensors'))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx = layer_backward(ctx.store, ctx.saved_tensors, ctx.kept, dout, ctx.need_dx, ctx.in_dtype)
+        return None, dx, None, None, None, None, None
 
 
 def prepack16(layers, B, prec):
@@ -277,132 +467,10 @@ def prepack16(layers, B, prec):
             return                                        # first step: the copies are allocated on the layers' own stream
     with H.on_side_stream(None):
         for l in todo:
-            _packed16(l, side=True)
+            LayerBF16.packed(l, side=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
             l.__dict__['_pack16_ev'] = ev
-
-
-def _packed16(layer, side=False):
-    """bf16 operand copies of the layer's contraction weights, rebuilt from the fp32 master by ONE kernel per call."""
-    Hd, ND = layer.dim, layer.nd
-    G, Din, D = ND * 4 * Hd, layer.w_ih_cat.shape[1], ND * Hd
-    dev = layer.w_ih_cat.device
-    pk = layer.__dict__.get('_pack16')
-    if pk is None or pk['wih'].device != dev:
-        b16 = lambda *s_: torch.empty(s_, dtype=torch.bfloat16, device=dev)
-        pk = {'wih': b16(G, Din), 'wihT': b16(Din, G), 'bias': torch.empty(G, dtype=torch.float32, device=dev),
-              'pj': b16(D, D) if layer.proj else None, 'pjT': b16(D, D) if layer.proj else None}
-        layer.__dict__['_pack16'] = pk
-    ev = layer.__dict__.pop('_pack16_ev', None)
-    if ev is not None and not side:
-        torch.cuda.current_stream().wait_event(ev)       # packed ahead on the side stream (prepack16) in this forward
-        return pk
-    H.call('asr_rnn_pack_weights', H.ptr(layer.w_ih_cat), H.ptr(layer.b_ih_cat), H.ptr(layer.b_hh_cat),
-           H.ptr(layer.pj.weight) if layer.proj else None, H.ptr(pk['wih']), H.ptr(pk['wihT']), H.ptr(pk['bias']),
-           H.ptr(pk['pj']), H.ptr(pk['pjT']), Hd, ND, Din, D, H.stream_ptr())
-    return pk
-
-
-class RNNLayerFastFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, anchor, x, layer, train, seed):
-        in_dtype = x.dtype
-        x16 = to_bf16(x)
-        B, T, Din = x16.shape
-        Hd, ND = layer.dim, layer.nd
-        G, D = ND * 4 * Hd, ND * Hd
-        st = H.stream_ptr()
-        pk = _packed16(layer)
-        gates = _empty16((B, T, ND, Hd, 4), x16)
-        H.gemm16(x16, pk['wih'], gates, B * T, G, Din, Din, Din, G, 1, 1, bias=pk['bias'])
-        reserved = 64 if (layer.dp is not None and layer.dp.world > 1) else 0
-        y, c = lstm16_rec(layer, gates, B, T, reserved)
-        p = float(layer.dropout) if train else 0.0
-        r = layer.sample_rate
-        T2 = out_frames(layer, T)[0]
-        z = _empty16((B, T2, D), x16)
-        H.call('asr_dropout_downsample16_fwd', H.ptr(y), (T + 2) * D, D, H.ptr(z), B, T, D, T2, r, 0, p, seed, st)
-        if layer.proj:
-            out = _empty16((B, T2, D), x16)
-            H.gemm16(z, pk['pj'], out, B * T2, D, D, D, D, D, 1, 1, bias=layer.pj.bias, act=H.ACT_TANH)
-        else:
-            out = z
-        ctx.layer, ctx.meta = layer, (B, T, Din, T2, p, seed, reserved, in_dtype)
-        ctx.need_dx = x.requires_grad
-        ctx.pk = pk
-        ctx.save_for_backward(x16, gates, c, y, z, out)
-        if H.DEBUG_KEEP:
-            layer._dbg = {'x': x16, 'gates': gates, 'c': c, 'y': y, 'z': z, 'out': out}
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        layer, pk = ctx.layer, ctx.pk
-        B, T, Din, T2, p, seed, reserved, in_dtype = ctx.meta
-        x16, gates, c, y, z, out = ctx.saved_tensors
-        Hd, ND = layer.dim, layer.nd
-        G, D = ND * 4 * Hd, ND * Hd
-        st = H.stream_ptr()
-        dout = to_bf16(dout)
-        # Parameter gradients are off the critical path (only the optimizer reads them): they are deferred to the CU-masked side
-        # stream and start together with the NEXT recurrence of the backward pass, which runs on the complementary CU mask
-        # (H.on_rec_stream) - 160 workgroups that leave 96 compute units idle.  Under data parallelism a bucket may be signalled
-        # only when everything that writes into it has been issued: in line (default) the signals stay where they were; with
-        # ASR_OVERLAP_DP=1 they are deferred too, FIFO behind the work they depend on, and fire on the side stream.
-        dp = layer.dp
-        overlap = H.overlap_enabled() and (dp is None or H.overlap_dp_enabled())
-        if dp is not None:
-            def earlier_buckets():          # every consumer of this layer's output has finished its backward: heads / decoder / upper layers
-                for i in range(layer.bucket):
-                    dp.bucket_ready(i)
-            if overlap:
-                H.defer_side(earlier_buckets)
-            else:
-                earlier_buckets()
-        if layer.proj:
-            dpre = _empty16((B * T2, D), x16)
-            H.call('asr_act_bwd16', H.ptr(dout), H.ptr(out), H.ptr(dpre), B * T2 * D, H.ACT_TANH, st)
-
-            def pj_grads():
-                H.gemm16(dpre, z, layer.pj.weight.grad, D, D, B * T2, D, D, D, 0, 0, accum=1, splits=H.wgrad_splits(B * T2, D, D))
-                H.call('asr_colsum16', H.ptr(dpre), D, B * T2, D, H.ptr(layer.pj.bias.grad), None, 0, H.stream_ptr())
-            if overlap:
-                H.defer_side(pj_grads, dpre, z)
-            else:
-                pj_grads()
-            dz = _empty16((B, T2, D), x16)
-            H.gemm16(dpre, pk['pjT'], dz, B * T2, D, D, D, D, D, 1, 1)
-        else:
-            dz = dout
-        dy = _empty16((B, T, D), x16)
-        H.call('asr_dropout_downsample16_bwd', H.ptr(dz), H.ptr(dy), B, T, D, T2, layer.sample_rate, 0, p, seed, st)
-        lstm16_rec(layer, gates, B, T, 256 - 8 * H.REC_UNITS if overlap else reserved, dy, c, beside=overlap)
-        # gates now holds the gradient wrt the gate pre-activations (gate-minor); parameter gradients in reference row order
-        dx = None
-        if ctx.need_dx:
-            dx = _empty16((B, T, Din), x16)
-            H.gemm16(gates, pk['wihT'], dx, B * T, Din, G, G, G, Din, 1, 1)
-            if in_dtype == torch.float32:
-                dx = to_f32(dx)
-
-        def weight_grads():
-            H.gemm16(gates, x16, layer.g_w_ih_cat, G, Din, B * T, G, Din, Din, 0, 0, accum=1,
-                     splits=H.wgrad_splits(B * T, G, Din), perm_h=Hd)
-            H.call('asr_colsum16', H.ptr(gates), G, B * T, G, H.ptr(layer.g_b_ih_cat), H.ptr(layer.g_b_hh_cat), Hd, H.stream_ptr())
-            splits_hh = H.wgrad_splits(B * T, 4 * Hd, Hd)
-            for d in range(ND):
-                H.gemm16(gates, y, layer.g_w_hh_cat[d], 4 * Hd, Hd, B * T, G, D, Hd, 0, 0, accum=1, splits=splits_hh,
-                         perm_h=Hd, seqT=T, bshift=(-1 if d == 0 else 1), b_time_padded=1, a_off=d * 4 * Hd, b_off=d * Hd)
-        if overlap:
-            H.defer_side(weight_grads, gates, x16, y)
-            if dp is not None:
-                H.defer_side(lambda: dp.bucket_ready(layer.bucket))
-        else:
-            weight_grads()
-            if dp is not None:
-                dp.bucket_ready(layer.bucket)
-        return None, dx, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------
@@ -728,7 +796,7 @@ class AttDecoderFn(torch.autograd.Function):
             H.watch_abort(ws, status_off)
         if overlap:
             # the decoder's parameter gradients (15 launches, ~0.7 ms) are off the path to the encoder gradient: they run on the
-            # CU-masked side stream beside the encoder's BPTT (issued at its first recurrence, RNNLayerFastFn.backward)
+            # CU-masked side stream beside the encoder's BPTT (issued at its first recurrence, layer_backward)
             keep = [t for t in st.values() if torch.is_tensor(t)]
 
             def param_grads():

@@ -13,7 +13,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ASR_HIP_LIB') or os.path.join(os.path.dirname(_HERE), 'lib', 'libasr_hip.so')      # ASR_HIP_LIB: A/B builds (tools/), never a fallback
 
 F32, BF16 = 0, 1
-DEBUG_KEEP = os.environ.get('ASR_DEBUG_KEEP', '0') == '1'      # layers keep references to their saved activations (tools/dbg_*.py)
 ACT_NONE, ACT_TANH, ACT_RELU = 0, 1, 2
 MAX_DEC_LAYERS = 4
 
@@ -343,9 +342,10 @@ def raise_if_aborted():
 # continues with a 40-workgroup persistent recurrence that leaves most of the chip idle: they run on a second HIP
 # stream beside it.  The backward pass joins the side stream once, when the autograd engine has finished
 # (engine callback), so every reader of .grad on the current stream sees complete gradients.
-# Measured on MI355X (bench.py, 1 GPU): the contractions do run beside the recurrence, but they slow it by 0.7 ms, run
-# 25-40 % slower themselves and the step gains nothing (34.2 vs 34.0 ms) - so this is OFF unless ASR_SIDE_STREAM=1.
-_side = {'stream': None, 'pending': False, 'enabled': os.environ.get('ASR_SIDE_STREAM', '0') == '1', 'deferred': [], 'keep': []}
+# Measured on MI355X (bench.py, 1 GPU) with fp32 operands on an unmasked stream: the contractions do run beside the
+# recurrence, but they slow it by 0.7 ms, run 25-40 % slower themselves and the step gains nothing (34.2 vs 34.0 ms) - so
+# the fp32-storage layers keep their parameter gradients in line (src/functions.LayerF32).
+_side = {'stream': None, 'pending': False, 'deferred': [], 'keep': []}
 
 # Round 2: with bf16 operands AND CU-masked streams the overlap pays.  The recurrence of the bf16 encoder path is launched on
 # a stream restricted to REC_UNITS compute units per XCD, the deferred parameter-gradient work on a stream restricted to the
@@ -470,12 +470,8 @@ class on_rec_stream:
 
 
 def fast16_enabled():
-    """bf16-storage encoder path (src/functions.RNNLayerFastFn); ASR_FAST16=0 keeps the fp32-storage kernels (A/B runs)."""
+    """bf16-storage encoder path (src/functions.LayerBF16); ASR_FAST16=0 keeps the fp32-storage kernels (A/B runs)."""
     return os.environ.get('ASR_FAST16', '1') != '0'
-
-
-def side_enabled():
-    return _side['enabled']
 
 
 class on_side_stream:

@@ -157,7 +157,7 @@ class RNNLM(nn.Module):
                 if train:
                     h = F_.DropoutFn.apply(h, self.dropout, self._seed + 1 + l)
             else:
-                h = F_.RNNLayerFn.apply(self._anchor, h, layer, train, self._seed + 1 + l, self.prec)
+                h = F_.RNNLayerFn.apply(self._anchor, h, layer, train, self._seed + 1 + l, self.prec, F_.LayerF32)
         if self.emb_tying:
             out = F_.LinearFn.apply(self._anchor, h, self.emb.weight, None, self.prec)
         else:

@@ -88,9 +88,9 @@ class RNNLayer(nn.Module):
             from src.variants import gru_layer_forward
             out = gru_layer_forward(self, input_x, ctx, train, seed)
         elif F_hip.rnn_fast_ok(self, input_x, ctx.prec):
-            out = F_hip.RNNLayerFastFn.apply(ctx.anchor, input_x, self, train, seed)       # bf16 out
+            out = F_hip.RNNLayerFn.apply(ctx.anchor, input_x, self, train, seed, ctx.prec, F_hip.LayerBF16)       # bf16 out
         else:
-            out = F_hip.RNNLayerFn.apply(ctx.anchor, F_hip.to_f32_fn(input_x), self, train, seed, ctx.prec)
+            out = F_hip.RNNLayerFn.apply(ctx.anchor, F_hip.to_f32_fn(input_x), self, train, seed, ctx.prec, F_hip.LayerF32)
         if self.sample_rate > 1:
             x_len = x_len // self.sample_rate
         return out, x_len

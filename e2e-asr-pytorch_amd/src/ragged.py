@@ -9,12 +9,12 @@ what moves is the data (csrc/ragged.hip):
          the tail of every convolution's activation zeroed in place (asr_ragged_zero_tail) - the zero padding in time the
          unpadded pass's next convolution reads at t = n' - and halves the lengths at each time pooling
        vgg 6 (every 4th frame) and vgg 7 (one Linear) work per frame: their own kernels on the masked features
-  1. input projection of the padded batch, as in src/functions.py
-  2. asr_ragged_align: direction 0 of the gate pre-activations masked to the row's frames, direction 1 RIGHT-ALIGNED, so the
-     reverse walk starts from the zero state on the row's true last frame and meets only zeros after its first one
-  3. asr_lstm_fwd / asr_lstm16_fwd
-  4. asr_ragged_unalign: direction 1 of y shifted back, exact zeros past the row's length, the time down-sampling taken
-  5. [LayerNorm, fp32 storage only, per frame: after the down-sampling it sees the same rows] projection + tanh
+  1..5. every BiLSTM layer through the training path's loop, src/functions.layer_forward with the lengths: input projection
+     of the padded batch; asr_ragged_align (direction 0 of the gate pre-activations masked to the row's frames, direction 1
+     RIGHT-ALIGNED, so the reverse walk starts from the zero state on the row's true last frame and meets only zeros after its
+     first one); asr_lstm_fwd / asr_lstm16_fwd; asr_ragged_unalign (direction 1 of y shifted back, exact zeros past the row's
+     length, the time down-sampling taken); [LayerNorm, fp32 storage only, per frame: after the down-sampling it sees the same
+     rows] projection + tanh
 
 Inference only (no autograd, no dropout).  Eligible: an encoder of LSTM layers behind any front-end the config accepts
 (vgg = 0..7), any of LayerNorm / 'drop' / 'concat' / projection, either storage mode - per layer the one
@@ -107,60 +107,6 @@ def frontend_max_batch(asr, T):
     return max(1, FRONTEND_ACT_BYTES // largest_activation_bytes(ext, max(1, int(T)), asr.prec))
 
 
-def _unalign(y, bstride, off, z, lens, B, T, layer, T2, esize):
-    style = 0 if layer.sample_style == 'drop' else 1
-    H.call('asr_ragged_unalign', H.ptr(y), bstride, off, H.ptr(z), H.ptr(lens), B, T, layer.nd, layer.dim, T2, layer.sample_rate, style,
-           esize, H.stream_ptr())
-
-
-def ragged_layer(layer, x, lens, prec):
-    """One encoder layer over the padded batch x (B,T,Din), fp32 or bf16, rows at t >= lens[b] arbitrary (never used).
-    lens int64 (B) on the device, max(lens) == T.  Returns (B,T2,Dz) in the storage mode RNNLayer.forward would choose; its
-    rows past the layer's output length hold tanh(bias) when the layer projects (the NEXT align ignores them), else zeros."""
-    B, T, Din = x.shape
-    Hd, ND = layer.dim, layer.nd
-    G, D = ND * 4 * Hd, ND * Hd
-    T2, segs = F_hip.out_frames(layer, T)
-    Dz = D * segs
-    st = H.stream_ptr()
-    if T2 == 0:
-        raise ValueError("every utterance is shorter than the 'concat' rate %d of an encoder layer: no frame comes out" % layer.sample_rate)
-    if F_hip.rnn_fast_ok(layer, x, prec):
-        x16 = F_hip.to_bf16(x)
-        pk = F_hip._packed16(layer)
-        raw = F_hip._empty16((B, T, ND, Hd, 4), x16)
-        H.gemm16(x16, pk['wih'], raw, B * T, G, Din, Din, Din, G, 1, 1, bias=pk['bias'])
-        gates = torch.empty_like(raw)
-        H.call('asr_ragged_align', H.ptr(raw), H.ptr(gates), H.ptr(lens), B, T, ND, 4 * Hd, 2, st)
-        y, _c = F_hip.lstm16_rec(layer, gates, B, T, 0)
-        z = F_hip._empty16((B, T2, Dz), x16)
-        _unalign(y, (T + 2) * D, D, z, lens, B, T, layer, T2, 2)
-        if not layer.proj:
-            return z
-        out = F_hip._empty16((B, T2, Dz), x16)
-        H.gemm16(z, pk['pj'], out, B * T2, D, D, D, D, D, 1, 1, bias=layer.pj.bias, act=H.ACT_TANH)
-        return out
-    x = F_hip.to_f32(x)
-    raw = F_hip._empty((B, T, ND, 4 * Hd), x)
-    H.gemm(x, layer.w_ih_cat, raw, B * T, G, Din, Din, Din, G, 1, 1, bias=layer.b_ih_cat, prec=prec)
-    gates = torch.empty_like(raw)
-    H.call('asr_ragged_align', H.ptr(raw), H.ptr(gates), H.ptr(lens), B, T, ND, 4 * Hd, 4, st)
-    y, _c = F_hip.lstm_rec(layer, gates, B, T, prec)
-    z = F_hip._empty((B, T2, Dz), x)
-    _unalign(y, T * D, 0, z, lens, B, T, layer, T2, 4)
-    if layer.layer_norm:
-        # per frame, so the frames that survive the down-sampling are normalised as the unpadded pass normalises them;
-        # a 'concat' row is `segs` frames side by side.  Padding rows become the LayerNorm bias: masked by the next align
-        zn, stats = torch.empty_like(z), F_hip._empty((B * T2 * segs, 2), x)
-        H.call('asr_layernorm_fwd', H.ptr(z), H.ptr(layer.ln.weight), H.ptr(layer.ln.bias), H.ptr(zn), H.ptr(stats), B * T2 * segs, D, 1e-5, 0, st)
-        z = zn
-    if not layer.proj:
-        return z
-    out = F_hip._empty((B, T2, Dz), x)
-    H.linear_fwd(z.view(B * T2, Dz), layer.pj.weight, layer.pj.bias, out.view(B * T2, Dz), act=H.ACT_TANH, prec=prec)
-    return out
-
-
 def masked_copy(x, lens):
     """Copy of x (B,T,D) with exact zeros at t >= lens[b]; the source rows there are never read."""
     x = x.contiguous()
@@ -213,7 +159,8 @@ def encode_chunk(asr, feat, flen, with_ctc):
         x, tl, el = run_frontend(asr, ext, feat, flen)
     lens = torch.tensor(tl, dtype=torch.int64, device=dev)
     for layer in list(enc_m.layers)[0 if ext is None else 1:]:
-        x = ragged_layer(layer, x, lens, asr.prec)
+        storage = F_hip.LayerBF16 if F_hip.rnn_fast_ok(layer, x, asr.prec) else F_hip.LayerF32      # as RNNLayer.forward chooses
+        x = F_hip.layer_forward(storage(layer, asr.prec, x.shape), x, lens=lens)
         tl = [F_hip.out_frames(layer, n)[0] for n in tl]
         el = [e // layer.sample_rate if layer.sample_rate > 1 else e for e in el]
         lens = torch.tensor(tl, dtype=torch.int64, device=dev)
