@@ -415,9 +415,14 @@ __global__ __launch_bounds__(NT, (FAST && BF16) ? 3 : 1) void gemm_kernel(GemmP 
     }
 }
 
-template <bool BF16>
-int launch_gemm(const GemmP& p0, int a_kc, int b_kc, hipStream_t st, bool io16 = false) {
-    GemmP p = p0;
+int gemm_plain_order_forced() {
+    static int plain = -1;
+    if (plain < 0) { const char* e = getenv("ASR_GEMM_PLAIN_ORDER"); plain = (e && e[0] == '1') ? 1 : 0; }
+    return plain;
+}
+// Host plan of a launch: tile counts, XCD band geometry, loader qualification, tile order and the number of workgroups.
+// Pure arithmetic on the arguments (no device call): launch_gemm and the plan queries all take it from here.
+int gemm_plan(GemmP& p, int a_kc, int b_kc, bool io16, long& nblk) {
     p.nx = cdiv(p.N, BN); p.ny = cdiv(p.M, BM); p.nz = p.batch * p.splits;
     p.rpb = cdiv((long)p.ny * p.nz, 8);
     const long b_slice = (long)BN * cdiv(p.K, p.splits) * (long)(io16 ? 2 : sizeof(float));      // B operand bytes of one column tile
@@ -427,13 +432,23 @@ int launch_gemm(const GemmP& p0, int a_kc, int b_kc, hipStream_t st, bool io16 =
     // fast loader: no convolution operand, 16-byte aligned rows, contiguous extent a multiple of 4 and at least one float4
     p.fastA = (!p.convA && p.vecA && (a_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.M % 4 == 0 && p.M >= 4))) ? 1 : 0;
     p.fastB = (!p.convB && p.vecB && (b_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.N % 4 == 0 && p.N >= 4))) ? 1 : 0;
-    static int plain = -1;
-    if (plain < 0) { const char* e = getenv("ASR_GEMM_PLAIN_ORDER"); plain = (e && e[0] == '1') ? 1 : 0; }
     // measured (tools/bench_gemm.py): the banded order wins when a row of tiles is short (N <= 1024: projection and input-
     // gradient shapes, 1.15-1.2x) and loses for wide outputs and split reductions, which keep the natural order
-    p.plain_order = (plain || p.nz > 1 || p.nx > 8) ? 1 : 0;
-    const long nblk = p.plain_order ? (long)p.nx * p.ny * p.nz : 8L * p.rpb * p.ngx * p.gx;
+    p.plain_order = (gemm_plain_order_forced() || p.nz > 1 || p.nx > 8) ? 1 : 0;
+    nblk = p.plain_order ? (long)p.nx * p.ny * p.nz : 8L * p.rpb * p.ngx * p.gx;
     ASR_REQUIRE(nblk < (1L << 31), ASR_E_UNSUPPORTED, "asr_gemm: %ld tiles", nblk);
+    return ASR_OK;
+}
+void gemm_plan_out(const GemmP& p, int out[8]) {
+    out[0] = p.fastA; out[1] = p.fastB; out[2] = p.plain_order; out[3] = p.nx; out[4] = p.ny; out[5] = p.nz; out[6] = p.gx; out[7] = p.ngx;
+}
+
+template <bool BF16>
+int launch_gemm(const GemmP& p0, int a_kc, int b_kc, hipStream_t st, bool io16 = false) {
+    GemmP p = p0;
+    long nblk = 0;
+    const int prc = gemm_plan(p, a_kc, b_kc, io16, nblk);
+    if (prc != ASR_OK) return prc;
     dim3 grid((unsigned)nblk);
     dim3 block(NT);
     if (io16) {
@@ -462,11 +477,11 @@ int launch_gemm(const GemmP& p0, int a_kc, int b_kc, hipStream_t st, bool io16 =
 
 }  // namespace
 
-extern "C" int asr_gemm(const float* A, const float* B, float* C, const float* bias,
-                        int M, int N, int K, long lda, long ldb, long ldc,
-                        int a_kc, int b_kc, int act, int accum, int splits,
-                        int batch, long sA, long sB, long sC, int seqT, int bshift,
-                        int prec, asr_stream_t stream) {
+// Argument checks of asr_gemm and the launch parameters they give (shared by the launch and the asr_gemm_plan query).
+static int gemm_args(const float* A, const float* B, float* C, const float* bias,
+                     int M, int N, int K, long lda, long ldb, long ldc,
+                     int a_kc, int b_kc, int act, int accum, int splits,
+                     int batch, long sA, long sB, long sC, int seqT, int bshift, int prec, GemmP& p) {
     ASR_REQUIRE(A && B && C, ASR_E_ARG, "asr_gemm: null operand");
     ASR_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, ASR_E_ARG, "asr_gemm: bad dims M=%d N=%d K=%d batch=%d", M, N, K, batch);
     ASR_REQUIRE(splits >= 1, ASR_E_ARG, "asr_gemm: splits must be >= 1");
@@ -475,7 +490,6 @@ extern "C" int asr_gemm(const float* A, const float* B, float* C, const float* b
     ASR_REQUIRE(!(seqT > 0 && b_kc), ASR_E_ARG, "asr_gemm: shifted reduction rows need b_kc=0");
     ASR_REQUIRE(prec == ASR_F32 || prec == ASR_BF16, ASR_E_ARG, "asr_gemm: bad prec %d", prec);
     ASR_REQUIRE(ldc >= N, ASR_E_ARG, "asr_gemm: ldc < N");
-    GemmP p;
     p.A = A; p.B = B; p.C = C; p.bias = bias;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.sA = sA; p.sB = sB; p.sC = sC; p.batch = batch; p.splits = splits;
@@ -483,27 +497,60 @@ extern "C" int asr_gemm(const float* A, const float* B, float* C, const float* b
     p.convA = p.convB = p.cT = p.cF = p.cC = 0;
     p.c16 = p.permH = p.bpadT = 0;
     p.vecA = (((uintptr_t)A & 15) == 0 && (lda % 4) == 0 && (sA % 4) == 0) ? 1 : 0;
+    // vecB also covers the shifted operand: its rows are read at an offset and stay 16-byte aligned because ldb % 4 == 0
     p.vecB = (((uintptr_t)B & 15) == 0 && (ldb % 4) == 0 && (sB % 4) == 0) ? 1 : 0;
-    // the shifted operand reads rows at an offset; stays 16B aligned because ldb%4==0
+    return ASR_OK;
+}
+
+extern "C" int asr_gemm(const float* A, const float* B, float* C, const float* bias,
+                        int M, int N, int K, long lda, long ldb, long ldc,
+                        int a_kc, int b_kc, int act, int accum, int splits,
+                        int batch, long sA, long sB, long sC, int seqT, int bshift,
+                        int prec, asr_stream_t stream) {
+    GemmP p;
+    const int rc = gemm_args(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, batch, sA, sB, sC, seqT, bshift, prec, p);
+    if (rc != ASR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     return prec == ASR_BF16 ? launch_gemm<true>(p, a_kc, b_kc, st) : launch_gemm<false>(p, a_kc, b_kc, st);
+}
+
+// The plan asr_gemm launches with for these arguments (host arithmetic only: nothing is launched, no pointer is followed).
+extern "C" int asr_gemm_plan(const float* A, const float* B, float* C, const float* bias,
+                             int M, int N, int K, long lda, long ldb, long ldc,
+                             int a_kc, int b_kc, int act, int accum, int splits,
+                             int batch, long sA, long sB, long sC, int seqT, int bshift,
+                             int prec, int out[8]) {
+    ASR_REQUIRE(out, ASR_E_ARG, "asr_gemm_plan: null out");
+    GemmP p;
+    const int rc = gemm_args(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, batch, sA, sB, sC, seqT, bshift, prec, p);
+    if (rc != ASR_OK) return rc;
+    long nblk = 0;
+    const int prc = gemm_plan(p, a_kc, b_kc, false, nblk);
+    if (prc != ASR_OK) return prc;
+    gemm_plan_out(p, out);
+    return ASR_OK;
 }
 
 int gemm16_nt(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc,
               int act, hipStream_t st);       // gemm16.hip
 int gemm16_tn(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
               int seqT, int bshift, int padded, hipStream_t st);
+int gemm16_nt_route(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc);
+int gemm16_tn_route(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
+                    int seqT, int bshift, int padded);
+void gemm16_nt_info(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc, int out[8]);
+void gemm16_tn_info(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
+                    int seqT, int bshift, int padded, int out[8]);
 static int nt_fast_enabled() {
     static const int on = [] { const char* e = getenv("ASR_GEMM16_NT"); return (e && e[0] == '0') ? 0 : 1; }();
     return on;
 }
 
-// Contraction on bf16 operands in HBM (the encoder stack's activations, gate gradients and the bf16 weight copies):
-// same index conventions as asr_gemm; C is bf16 (c_bf16 = 1: bias + activation epilogue, no accumulation) or fp32
-// (accumulate / split reduction, optional gate-minor -> reference row permutation for LSTM weight gradients).
-extern "C" int asr_gemm16(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
-                          int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
-                          int seqT, int bshift, int b_time_padded, asr_stream_t stream) {
+// Argument checks of asr_gemm16 and the kernel the call takes: 0 = the generic bf16-storage kernel (gemm_kernel IO16),
+// 1 / 3 = gemm16_nt_kernel at 128 x 128 / 256 x 256, 2 = gemm16_tn_kernel; negative = refused.  Host arithmetic only.
+extern "C" int asr_gemm16_route(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
+                                int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
+                                int seqT, int bshift, int b_time_padded) {
     ASR_REQUIRE(A && B && C, ASR_E_ARG, "asr_gemm16: null operand");
     ASR_REQUIRE(M > 0 && N > 0 && K > 0 && splits >= 1, ASR_E_ARG, "asr_gemm16: bad dims M=%d N=%d K=%d", M, N, K);
     ASR_REQUIRE(!(splits > 1 && (act != ASR_ACT_NONE || !accum || c_bf16)), ASR_E_ARG, "asr_gemm16: split reduction needs an fp32 accumulating output");
@@ -515,15 +562,20 @@ extern "C" int asr_gemm16(const void* A, const void* B, void* C, const float* bi
     ASR_REQUIRE((a_kc ? K : M) % 8 == 0 && (b_kc ? K : N) % 8 == 0, ASR_E_UNSUPPORTED, "asr_gemm16: contiguous extents must be multiples of 8");
     ASR_REQUIRE(perm_h == 0 || M % (4 * perm_h) == 0, ASR_E_ARG, "asr_gemm16: perm_h does not divide M");
     if (a_kc && b_kc && c_bf16 && splits == 1 && nt_fast_enabled()) {
-        // direct-to-LDS 128x128x64 kernel (gemm16.hip); 1 = shape does not qualify, fall through to the generic kernel
-        const int rc = gemm16_nt(A, B, C, bias, M, N, K, lda, ldb, ldc, act, (hipStream_t)stream);
-        if (rc <= 0) return rc;
+        // direct-to-LDS 128x128x64 kernel (gemm16.hip); 0 = shape does not qualify, fall through to the generic kernel
+        const int r = gemm16_nt_route(A, B, C, bias, M, N, K, lda, ldb, ldc);
+        if (r) return r;
     }
     if (!a_kc && !b_kc && !c_bf16 && accum && act == ASR_ACT_NONE && bias == nullptr && nt_fast_enabled()) {
-        const int rc = gemm16_tn(A, B, (float*)C, M, N, K, lda, ldb, ldc, splits, perm_h, seqT, bshift, b_time_padded, (hipStream_t)stream);
-        if (rc <= 0) return rc;
+        const int r = gemm16_tn_route(A, B, (float*)C, M, N, K, lda, ldb, ldc, splits, perm_h, seqT, bshift, b_time_padded);
+        if (r) return r;
     }
-    GemmP p;
+    return 0;
+}
+
+// Launch parameters of the generic kernel for an asr_gemm16 call (shared by the launch and the asr_gemm16_plan query)
+static void gemm16_generic_args(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
+                                int act, int accum, int splits, int c_bf16, int perm_h, int seqT, int bshift, int b_time_padded, GemmP& p) {
     p.A = (const float*)A; p.B = (const float*)B; p.C = (float*)C; p.bias = bias;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.sA = p.sB = p.sC = 0; p.batch = 1; p.splits = splits;
@@ -531,7 +583,54 @@ extern "C" int asr_gemm16(const void* A, const void* B, void* C, const float* bi
     p.convA = p.convB = p.cT = p.cF = p.cC = 0;
     p.c16 = c_bf16; p.permH = perm_h; p.bpadT = b_time_padded;
     p.vecA = p.vecB = 1;
+}
+
+// Contraction on bf16 operands in HBM (the encoder stack's activations, gate gradients and the bf16 weight copies):
+// same index conventions as asr_gemm; C is bf16 (c_bf16 = 1: bias + activation epilogue, no accumulation) or fp32
+// (accumulate / split reduction, optional gate-minor -> reference row permutation for LSTM weight gradients).
+extern "C" int asr_gemm16(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
+                          int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
+                          int seqT, int bshift, int b_time_padded, asr_stream_t stream) {
+    const int route = asr_gemm16_route(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded);
+    if (route < 0) return route;
+    if (route == 1 || route == 3) {
+        const int rc = gemm16_nt(A, B, C, bias, M, N, K, lda, ldb, ldc, act, (hipStream_t)stream);
+        if (rc <= 0) return rc;
+    }
+    if (route == 2) {
+        const int rc = gemm16_tn(A, B, (float*)C, M, N, K, lda, ldb, ldc, splits, perm_h, seqT, bshift, b_time_padded, (hipStream_t)stream);
+        if (rc <= 0) return rc;
+    }
+    GemmP p;
+    gemm16_generic_args(A, B, C, bias, M, N, K, lda, ldb, ldc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded, p);
     return launch_gemm<true>(p, a_kc, b_kc, (hipStream_t)stream, true);
+}
+
+// The plan behind asr_gemm16_route's answer (host arithmetic only).  Returns the route and fills out[8]:
+//   0 (generic kernel): the entries of asr_gemm_plan {fastA, fastB, plain_order, nx, ny, nz, gx, ngx} at bf16 operand size;
+//   1 / 3 (NT kernel):  {tiles along N, tiles along M, tile rows, tile columns, 0...};
+//   2 (TN kernel):      {tiles along I, tiles along J, reduction slices after clipping, k-steps per slice, LDS stages
+//                        (ASR_GEMM16_TN_STAGES), workgroups, 0, 0}.
+extern "C" int asr_gemm16_plan(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
+                               int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
+                               int seqT, int bshift, int b_time_padded, int out[8]) {
+    ASR_REQUIRE(out, ASR_E_ARG, "asr_gemm16_plan: null out");
+    const int route = asr_gemm16_route(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded);
+    if (route < 0) return route;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (route == 1 || route == 3) {
+        gemm16_nt_info(A, B, C, bias, M, N, K, lda, ldb, ldc, out);
+    } else if (route == 2) {
+        gemm16_tn_info(A, B, (float*)C, M, N, K, lda, ldb, ldc, splits, perm_h, seqT, bshift, b_time_padded, out);
+    } else {
+        GemmP p;
+        gemm16_generic_args(A, B, C, bias, M, N, K, lda, ldb, ldc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded, p);
+        long nblk = 0;
+        const int prc = gemm_plan(p, a_kc, b_kc, true, nblk);
+        if (prc != ASR_OK) return prc;
+        gemm_plan_out(p, out);
+    }
+    return route;
 }
 
 // 3x3 / stride 1 / pad 1 convolution over channel-last images as an implicit GEMM.

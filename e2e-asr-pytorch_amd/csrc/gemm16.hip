@@ -205,9 +205,10 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN > 4) ? 1 : 2) void gemm1
 
 }  // namespace
 
-// Returns ASR_OK when launched, 1 when the shape does not qualify (the caller uses the generic kernel).
-int gemm16_nt(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc,
-              int act, hipStream_t st) {
+// Qualification and launch parameters of the NT kernel: 0 = qualifies (p and big filled), 1 = the shape does not.  Host
+// arithmetic only; the launch (gemm16_nt) and the route query (gemm16_nt_route) both decide here.
+static int gemm16_nt_plan(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc,
+                          int act, G16P& p, bool& big_out) {
     if (K % 8 != 0 || N % 8 != 0 || ldx % 8 != 0 || ldw % 8 != 0 || ldc % 8 != 0) return 1;
     if ((((uintptr_t)X | (uintptr_t)W | (uintptr_t)C) & 15) != 0 || (bias && ((uintptr_t)bias & 15) != 0)) return 1;
     const long xb = ((long)(M - 1) * ldx + K) * 2, wb = ((long)(N - 1) * ldw + K) * 2;
@@ -218,10 +219,32 @@ int gemm16_nt(const void* X, const void* W, void* C, const float* bias, int M, i
     // loop, not the fragment traffic, holds both tilings near 0.3 of the MFMA peak.
     static const bool big = [] { const char* e = getenv("ASR_GEMM16_BIG"); return e && atoi(e) > 0; }();
     const int bm = big ? 256 : BM, bn = big ? 256 : BN;
-    G16P p{(const unsigned short*)X, (const unsigned short*)W, (unsigned short*)C, bias, M, N, K, ldx, ldw, ldc, act,
-           (unsigned)xb, (unsigned)wb, cdiv(N, bn), cdiv(M, bm), 0, 0, 0, nullptr};
+    p = G16P{(const unsigned short*)X, (const unsigned short*)W, (unsigned short*)C, bias, M, N, K, ldx, ldw, ldc, act,
+             (unsigned)xb, (unsigned)wb, cdiv(N, bn), cdiv(M, bm), 0, 0, 0, nullptr};
+    if ((long)p.ntx * p.nty >= (1L << 31)) return 1;
+    big_out = big;
+    return 0;
+}
+
+// 0 = the generic kernel, 1 = this kernel's 128 x 128 tiling, 3 = its 256 x 256 tiling
+int gemm16_nt_route(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc) {
+    G16P p; bool big = false;
+    if (gemm16_nt_plan(X, W, C, bias, M, N, K, ldx, ldw, ldc, ASR_ACT_NONE, p, big)) return 0;
+    return big ? 3 : 1;
+}
+
+void gemm16_nt_info(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc, int out[8]) {
+    G16P p; bool big = false;
+    if (gemm16_nt_plan(X, W, C, bias, M, N, K, ldx, ldw, ldc, ASR_ACT_NONE, p, big)) return;
+    out[0] = p.ntx; out[1] = p.nty; out[2] = big ? 256 : BM; out[3] = big ? 256 : BN;
+}
+
+// Returns ASR_OK when launched, 1 when the shape does not qualify (the caller uses the generic kernel).
+int gemm16_nt(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc,
+              int act, hipStream_t st) {
+    G16P p; bool big = false;
+    if (gemm16_nt_plan(X, W, C, bias, M, N, K, ldx, ldw, ldc, act, p, big)) return 1;
     const long ntiles = (long)p.ntx * p.nty;
-    if (ntiles >= (1L << 31)) return 1;
     if (big) {
         static const bool once = [] {
             hipFuncSetAttribute((const void*)gemm16_nt_kernel<2, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
@@ -441,8 +464,10 @@ int gemm16_tn(const void* A, const void* B, float* C, int I, int J, int R, long 
               int seqT, int bshift, int padded, hipStream_t st) {
     return gemm16_tn_taps(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, 0, st);
 }
-int gemm16_tn_taps(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                   int seqT, int bshift, int padded, int tapF2, hipStream_t st) {
+// Qualification and launch parameters of the TN kernel: 0 = qualifies (p and the workgroup count filled), 1 = the shape does
+// not.  Host arithmetic only; the launch (gemm16_tn_taps) and the route query (gemm16_tn_route) both decide here.
+static int gemm16_tn_plan(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
+                          int seqT, int bshift, int padded, int tapF2, T16P& p, long& total) {
     if (I % 8 != 0 || J % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0) return 1;
     if ((((uintptr_t)A | (uintptr_t)B) & 15) != 0) return 1;
     if (seqT > 0 && !padded) return 1;                        // unpadded shifted rows need masking: generic kernel
@@ -452,12 +477,39 @@ int gemm16_tn_taps(const void* A, const void* B, float* C, int I, int J, int R, 
     const int nk = cdiv(R, BK);
     if (splits < 1) splits = 1;
     if (splits > nk) splits = nk;
-    T16P p{(const unsigned short*)A, (const unsigned short*)B, C, I, J, R, lda, ldb, ldc, (unsigned)ab, (unsigned)bb,
-           cdiv(I, BM), cdiv(J, BN), splits, cdiv(nk, splits), seqT, bshift, perm_h, seqT > 0 ? 1.0f / (float)seqT : 0.f, tapF2};
-    const long total = (long)p.nti * p.ntj * p.splits * (tapF2 > 0 ? 9 : 1);
+    p = T16P{(const unsigned short*)A, (const unsigned short*)B, C, I, J, R, lda, ldb, ldc, (unsigned)ab, (unsigned)bb,
+             cdiv(I, BM), cdiv(J, BN), splits, cdiv(nk, splits), seqT, bshift, perm_h, seqT > 0 ? 1.0f / (float)seqT : 0.f, tapF2};
+    total = (long)p.nti * p.ntj * p.splits * (tapF2 > 0 ? 9 : 1);
     if (total >= (1L << 31)) return 1;
-    // ASR_GEMM16_TN_STAGES=2: the double-buffered instantiation (two workgroups per CU); default one stage, three per CU
-    static const int stages = [] { const char* e = getenv("ASR_GEMM16_TN_STAGES"); return e ? atoi(e) : 1; }();
+    return 0;
+}
+
+// 0 = the generic kernel, 2 = this kernel
+int gemm16_tn_route(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
+                    int seqT, int bshift, int padded) {
+    T16P p; long total = 0;
+    return gemm16_tn_plan(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, 0, p, total) ? 0 : 2;
+}
+
+// LDS stages of the TN kernel: ASR_GEMM16_TN_STAGES=2 / 4 select the pipelined instantiations (two / one workgroup per CU);
+// default, and any other value, one stage at three per CU
+static int gemm16_tn_stages() {
+    static const int stages = [] { const char* e = getenv("ASR_GEMM16_TN_STAGES"); const int v = e ? atoi(e) : 1; return (v == 2 || v == 4) ? v : 1; }();
+    return stages;
+}
+
+void gemm16_tn_info(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
+                    int seqT, int bshift, int padded, int out[8]) {
+    T16P p; long total = 0;
+    if (gemm16_tn_plan(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, 0, p, total)) return;
+    out[0] = p.nti; out[1] = p.ntj; out[2] = p.splits; out[3] = p.per; out[4] = gemm16_tn_stages(); out[5] = (int)total;
+}
+
+int gemm16_tn_taps(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
+                   int seqT, int bshift, int padded, int tapF2, hipStream_t st) {
+    T16P p; long total = 0;
+    if (gemm16_tn_plan(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, tapF2, p, total)) return 1;
+    const int stages = gemm16_tn_stages();
     if (stages == 4) {
         static unsigned char attr4_[32];
         if (first_on_device(attr4_)) hipFuncSetAttribute((const void*)gemm16_tn_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * STAGE_BYTES);

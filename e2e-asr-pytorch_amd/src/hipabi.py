@@ -166,6 +166,9 @@ _RESTYPES = {
     'asr_specaug_workspace_bytes': (_sz, [_i]),
     'asr_lstm_set_persistent': (ctypes.c_int, [_i]),
     'asr_lstm_plan': (ctypes.c_int, [_i, _i, _i, _i, _i]),
+    'asr_gemm_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _l, _l, _l, _i, _i, _i, _P(_i)]),
+    'asr_gemm16_route': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    'asr_gemm16_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _P(_i)]),
     'asr_lstm16_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_ctc_loss_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_beam_search_workspace_bytes': (_sz, [_i, _i, _i]),

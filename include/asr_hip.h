@@ -61,6 +61,16 @@ int asr_gemm(const float* A, const float* B, float* C, const float* bias,
              int a_kc, int b_kc, int act, int accum, int splits,
              int batch, long sA, long sB, long sC, int seqT, int bshift,
              int prec, asr_stream_t stream);
+/* The plan asr_gemm launches with for the same arguments (without the stream): out = {fastA, fastB, plain_order, nx, ny,
+ * nz, gx, ngx} - whether operand A / B takes the unconditional 16-byte loader (otherwise the masked one), whether the tiles
+ * run in natural order (otherwise in XCD bands), column tiles, row tiles, batch * splits, column tiles per group and the
+ * number of groups of the banded order.  Pure host arithmetic from the code the launch itself uses: no device call, the
+ * pointers are looked at for their alignment only.  Returns what asr_gemm would return for refused arguments. */
+int asr_gemm_plan(const float* A, const float* B, float* C, const float* bias,
+                  int M, int N, int K, long lda, long ldb, long ldc,
+                  int a_kc, int b_kc, int act, int accum, int splits,
+                  int batch, long sA, long sB, long sC, int seqT, int bshift,
+                  int prec, int out[8]);
 
 /* ------------------------------------------------------------------------------------------------
  * Encoder BiLSTM time recurrence (the sequential half of nn.LSTM(bidirectional, batch_first),
@@ -135,6 +145,21 @@ int asr_lstm16_bwd(void* gates16, const float* whh, const void* dy16, const floa
 int asr_gemm16(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
                int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
                int seqT, int bshift, int b_time_padded, asr_stream_t stream);
+/* Which kernel asr_gemm16 takes for the same arguments (without the stream): 0 = the generic bf16-storage kernel, 1 = the
+ * direct-to-LDS NT kernel at 128 x 128, 2 = the TN (weight-gradient) kernel, 3 = the NT kernel at 256 x 256 (ASR_GEMM16_BIG=1);
+ * a negative ASR_E_* for arguments asr_gemm16 refuses.  Pure host arithmetic from the code the launch itself uses: no device
+ * call, the pointers are looked at for their alignment only. */
+int asr_gemm16_route(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
+                     int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
+                     int seqT, int bshift, int b_time_padded);
+/* The plan behind that route (same arguments, host arithmetic only): returns the route and fills out[8] -
+ *   route 0: the entries of asr_gemm_plan {fastA, fastB, plain_order, nx, ny, nz, gx, ngx} at bf16 operand size;
+ *   route 1 / 3: {tiles along N, tiles along M, tile rows, tile columns, 0, 0, 0, 0};
+ *   route 2: {tiles along M, tiles along N, reduction slices after clipping to the k-steps, k-steps per slice, LDS stages
+ *             (ASR_GEMM16_TN_STAGES: 1, 2 or 4), workgroups, 0, 0}. */
+int asr_gemm16_plan(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
+                    int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
+                    int seqT, int bshift, int b_time_padded, int out[8]);
 int asr_rnn_pack_weights(const float* w_ih, const float* b_ih, const float* b_hh, const float* pj,
                          void* w_ih16, void* w_ihT16, float* bias, void* pj16, void* pjT16,
                          int H, int ND, int Din, int D, asr_stream_t stream);

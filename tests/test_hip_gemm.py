@@ -132,11 +132,15 @@ def test_gemm16_nt_bf16_out(M, N, K, act):
     Hh.gemm16(x.cuda(), w.cuda(), out, M, N, K, K, K, N, 1, 1, bias=b.cuda(), act=act)
     err = (out.float().cpu() - ref).abs().max().item()
     assert err < 2e-2 * max(1.0, ref.abs().max().item()), err          # bf16 rounding of the output
-    # the generic kernel (ASR_GEMM16_NT=0 path) must agree: exercised through a strided output it alone supports
-    out2 = torch.full((M, N + 8), 7.0, dtype=torch.bfloat16, device='cuda')
-    Hh.gemm16(x.cuda(), w.cuda(), out2, M, N, K, K, K, N + 8, 1, 1, bias=b.cuda(), act=act)
+    # the generic bf16-storage kernel must agree: ldc = N + 4 is no multiple of 8 for the six shapes with N % 8 == 0, and the
+    # seventh (N = 132) has N % 8 != 0 - either way the direct-to-LDS kernel refuses the call, and the route query says so
+    xd, wd, bd = x.cuda(), w.cuda(), b.cuda()
+    out2 = torch.full((M, N + 4), 7.0, dtype=torch.bfloat16, device='cuda')
+    assert Hh.lib().asr_gemm16_route(Hh.ptr(xd), Hh.ptr(wd), Hh.ptr(out), Hh.ptr(bd), M, N, K, K, K, N, 1, 1, act, 0, 1, 1, 0, 0, 0, 0) == (1 if N % 8 == 0 else 0)
+    assert Hh.lib().asr_gemm16_route(Hh.ptr(xd), Hh.ptr(wd), Hh.ptr(out2), Hh.ptr(bd), M, N, K, K, K, N + 4, 1, 1, act, 0, 1, 1, 0, 0, 0, 0) == 0
+    Hh.gemm16(xd, wd, out2, M, N, K, K, K, N + 4, 1, 1, bias=bd, act=act)
     assert (out2[:, :N].float().cpu() - ref).abs().max().item() < 2e-2 * max(1.0, ref.abs().max().item())
-    assert float(out2[:, N:].float().min()) == 7.0
+    assert float(out2[:, N:].float().min()) == 7.0 and float(out2[:, N:].float().max()) == 7.0
 
 
 def test_gemm16_tn_weight_gradient_permuted_and_shifted():
