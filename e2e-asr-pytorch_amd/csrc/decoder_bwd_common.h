@@ -261,27 +261,33 @@ __device__ __forceinline__ float sum_groups(float v) {
     return v;
 }
 
-// sweep of this wave's units, then the Q record: the tile's query-gradient partial times (1 - q^2), pairs (a, a+1) from even lanes
-#define DPB_SWEEP_AND_PUBLISH(XB, NU)                                                                                      \
-    {                                                                                                                  \
-        float dqp_[NU];                                                                                                \
-        if (tau0 < len) sweep_step(S, qa, dqp_, nu_cnt, wave, nw, MT, TE, A, AP, s_cvx, s_cvT, s_de, s_key, s_dl, lane); \
-        else { _Pragma("unroll") for (int nu = 0; nu < NU; ++nu) dqp_[nu] = 0.f; }                                     \
-        _Pragma("unroll") for (int nu = 0; nu < NU; ++nu) {                                                            \
-            if (nu < nu_cnt) {                                                                                         \
-                const int a_ = 16 * (wave + nw * nu) + csub;                                                           \
-                const float tot_ = sum_groups(dqp_[nu]);                                                               \
-                const float mine_ = (a_ < A) ? tot_ * (1.f - qa[nu] * qa[nu]) : 0.f;                                   \
-                const float nb_ = __shfl_down(mine_, 1);                                                               \
-                if (qsub == 0 && (lane & 1) == 0 && a_ < 2 * p.QG2) {                                                  \
-                    u64* dst_ = (XB) + offQ + (long)j * p.QG2 + (a_ >> 1);                           \
-                    if (local) publish<true>(dst_, pack2(mine_, nb_, want)); else publish<false>(dst_, pack2(mine_, nb_, want)); \
-                }                                                                                                      \
+// the Q record: the tile's query-gradient partial DQ[nu] times (1 - q^2), pairs (a, a+1) from even lanes
+#define DPB_PUBLISH_Q(XB, NU, DQ)                                                                                      \
+    _Pragma("unroll") for (int nu = 0; nu < NU; ++nu) {                                                                \
+        if (nu < nu_cnt) {                                                                                             \
+            const int a_ = 16 * (wave + nw * nu) + csub;                                                               \
+            const float tot_ = sum_groups(DQ[nu]);                                                                     \
+            const float mine_ = (a_ < A) ? tot_ * (1.f - qa[nu] * qa[nu]) : 0.f;                                       \
+            const float nb_ = __shfl_down(mine_, 1);                                                                   \
+            if (qsub == 0 && (lane & 1) == 0 && a_ < 2 * p.QG2) {                                                      \
+                u64* dst_ = (XB) + offQ + (long)j * p.QG2 + (a_ >> 1);                                                 \
+                if (local) publish<true>(dst_, pack2(mine_, nb_, want)); else publish<false>(dst_, pack2(mine_, nb_, want));\
             }                                                                                                          \
         }                                                                                                              \
     }
-// end of the launch: d w_g and d W_proj of the wave's units -> the workgroup's slot, dkey -> HBM (plain stores, once)
-#define DPB_SWEEP_RESULTS(NU)                                                                                          \
+// sweep of this wave's units (dec_bwd_persist: the whole tile at once), then the Q record
+#define DPB_SWEEP_AND_PUBLISH(XB, NU)                                                                                  \
+    {                                                                                                                  \
+        float dqp_[NU];                                                                                                \
+        if (tau0 < len) sweep_step(S, qa, dqp_, nu_cnt, wave, nw, MT, TE, A, AP, s_cvx, s_cvT, s_de, s_key, s_dl, lane);\
+        else { _Pragma("unroll") for (int nu = 0; nu < NU; ++nu) dqp_[nu] = 0.f; }                                     \
+        DPB_PUBLISH_Q(XB, NU, dqp_)                                                                                    \
+    }
+// end of the launch: d w_g and d W_proj of the wave's units -> the workgroup's slot and, where dkey was kept in registers
+// (HAS_DK: dec_bwd_persist), the dkey of the tile's TEF frames -> DKEY (B, T', A) in HBM (plain stores, once).  dec_bwd_stream added
+// its dkey to dkT step by step: it passes HAS_DK false, and DKEY / TEF are then unused (nullptr, 0).  The dkey stores stay inside
+// the unit loop: as a loop of their own they moved dec_bwd_persist's spills.
+#define DPB_SWEEP_RESULTS(NU, HAS_DK, DKEY, TEF)                                                                       \
     {                                                                                                                  \
         float* sl_ = p.slots + ((long)b * NT + j) * p.slot;                                                            \
         _Pragma("unroll") for (int nu = 0; nu < NU; ++nu) {                                                            \
@@ -293,14 +299,52 @@ __device__ __forceinline__ float sum_groups(float v) {
                     const int a_ = u0_ + 4 * qsub + r;                                                                 \
                     if (csub < Kn && a_ < A) sl_[A + csub * A + a_] = S.dwp[nu][r];                                    \
                 }                                                                                                      \
-                _Pragma("unroll") for (int mt = 0; mt < SW_MT; ++mt)                                                   \
-                    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                    \
-                        const int f_ = 16 * mt + 4 * qsub + r;                                                         \
-                        if (f_ < TE && tau0 + f_ < Tp && u0_ + csub < A)                                               \
-                            p.dkey[((long)b * Tp + tau0 + f_) * A + u0_ + csub] = S.dk[nu][mt][r];                     \
-                    }                                                                                                  \
+                if constexpr (HAS_DK) {                                                                                \
+                    _Pragma("unroll") for (int mt = 0; mt < SW_MT; ++mt)                                               \
+                        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                \
+                            const int f_ = 16 * mt + 4 * qsub + r;                                                     \
+                            if (f_ < (TEF) && tau0 + f_ < Tp && u0_ + csub < A)                                        \
+                                (DKEY)[((long)b * Tp + tau0 + f_) * A + u0_ + csub] = S.dk[nu][mt][r];                 \
+                        }                                                                                              \
+                }                                                                                                      \
             }                                                                                                          \
         }                                                                                                              \
+    }
+
+// S1, the cell backward of ALL hidden units (thread per unit; every workgroup of the cluster computes the same): gate gradients
+// of step t -> s_dg16 (bf16) and, for the own units, dgates.  TEF: frames per tile (the N record is {datt_next[TEF] | dh_q slice})
+#define DPB_S1(TEF)                                                                                                    \
+    {                                                                                                                  \
+        float dh = pdh;                                                                                                \
+        if (s > 0) dh += s_crec[ui * CG2f + p.CPW + uul] + s_nrec[ui * NG2f + (TEF) + uul];                            \
+        const float tc = tanhf(pct);                                                                                   \
+        const float dc = dh * pgo * (1.f - tc * tc) + dc_carry;                                                        \
+        const float d0 = dc * pgg * pgi * (1.f - pgi), d1 = dc * pcp * pgf * (1.f - pgf);                              \
+        const float d2 = dc * pgi * (1.f - pgg * pgg), d3 = dh * tc * pgo * (1.f - pgo);                               \
+        dc_carry = dc * pgf;                                                                                           \
+        if (uok) {                                                                                                     \
+            s_dg16[tz] = f2bf_bits(d0); s_dg16[Dd + tz] = f2bf_bits(d1);                                               \
+            s_dg16[2 * Dd + tz] = f2bf_bits(d2); s_dg16[3 * Dd + tz] = f2bf_bits(d3);                                  \
+        }                                                                                                              \
+        if (uown) {                                                                                                    \
+            float* go = p.dgates + row * 4 * Dd + tz;                                                                  \
+            go[0] = d0; go[Dd] = d1; go[2 * Dd] = d2; go[3 * Dd] = d3;                                                 \
+        }                                                                                                              \
+    }
+// granule I2 of the C record {dctx slice | dh_rec slice} from s_out (the products of P1, clamp OMAX) + global dxin (context part).
+// dec_bwd_persist has at most one granule per thread (`if (tz < CG2)`), dec_bwd_stream loops: the loop form in both moved the
+// resident kernel's spills.
+#define DPB_C_GRANULE(I2, OMAX)                                                                                        \
+    {                                                                                                                  \
+        float v[2];                                                                                                    \
+        _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                                \
+            const int i = 2 * (I2) + h;                                                                                \
+            const bool ok = (i < p.CPW) ? (c_base + i < E) : (i < nout && u_base + (i - p.CPW) < Dd);                  \
+            v[h] = ok ? s_out[min(i, (OMAX))] : 0.f;                                                                   \
+            if (i < p.CPW && c_base + i < E) p.dxin[row * XW + Dd + c_base + i] = v[h];                                \
+        }                                                                                                              \
+        u64* dst = out + offC + (long)j * p.CG2 + (I2);                                                                \
+        if (local) publish<true>(dst, pack2(v[0], v[1], want)); else publish<false>(dst, pack2(v[0], v[1], want));     \
     }
 
 // conv value of (frame f, kernel k) into the two LDS images of the step's conv tile

@@ -73,11 +73,6 @@ __device__ __forceinline__ void dp_jitter(unsigned k, unsigned step, unsigned ep
 #define DP_JIT(k)
 #define DP_DUMP
 #endif
-constexpr int RB = 5;                   // gate rows per batch of the cell contraction
-
-__device__ __forceinline__ float bf2f_(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
-__device__ __forceinline__ float tanh_f(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-__device__ __forceinline__ float sigm_f(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
 // wave-wide sum on the DPP path (quad swaps, mirrors, row broadcasts: 6 VALU steps, no LDS permutes); uniform result
 __device__ __forceinline__ float wave_sum_dpp(float v) {
@@ -96,6 +91,12 @@ __device__ __forceinline__ float sum8_dpp(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, false));
+    return v;
+}
+// sum over aligned groups of 16 lanes, i.e. one DPP row (every lane of the row gets it)
+__device__ __forceinline__ float sum16_dpp(float v) {
+    v = sum8_dpp(v);
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, false));      // row_mirror
     return v;
 }
 __device__ __forceinline__ float wave_max_dpp(float v) {

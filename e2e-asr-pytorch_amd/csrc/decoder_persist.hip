@@ -19,6 +19,7 @@
 // synchronise among themselves through an LDS counter where the polling waves are busy; s_barrier is used where
 // the polled data is handed over.
 #include "decoder_plan.h"
+#include "decoder_fwd_common.h"
 
 static int g_persist_fwd = -1, g_persist_bwd = -1;   // -1: from env ASR_DEC_PERSIST / ASR_DEC_PERSIST_BWD (default on)
 static int g_stream_fwd = -1, g_stream_bwd = -1;     // 1: take the streamed-tile plan (decoder_stream.hip) even where the LDS-resident one exists; -1: env ASR_DEC_STREAM
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
     const unsigned epoch_ = __builtin_amdgcn_readfirstlane(p.status[EPOCH_WORD]);     // launch epoch of this work area (decoder_cluster.h)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int NT = p.NT, A = d.A, E = d.E, Dd = d.Dd, Tp = d.Tp, Kn = d.Kn, Ks = d.Ks, L = d.L;
-    const int taps = 2 * Ks + 1, XW = Dd + E;
+    const int taps = 2 * Ks + 1;
     const int tau0 = j * TE;
     const int len = min((int)p.enc_len[b], Tp);
     const int tmax = max(len - 1, 0);
@@ -111,21 +112,11 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
     float* s_g = s_epart + NCW * EPL;                                                 // [4*UPW]
     float* s_stage = s_g + ((4 * p.UPW + 3) & ~3);                                    // [NT][2*SG2]
     if (tid == 0) s_bar = 0u;
-    const long region = (long)NT * (p.HG2 + p.QG2 + p.SG2);
-    auto xb = [&](int parity) { return p.xbuf + ((long)parity * d.B + b) * region; };
-    // The host memset reaches memory, but granules that an earlier launch stored L2-locally (sc0) can still sit in this
-    // XCD's L2 with perfectly valid tags (observed: wrong data in the first step after a launch with other inputs; a
-    // write-through `sc1` store of zeros did NOT displace the resident copy).  Every producer therefore clears its own
-    // records with the same L2-local store flavour before it joins the consensus - the barrier behind which polling starts.
-    for (int parity = 0; parity < 2; ++parity) {
-        u64* base = xb(parity);
-        for (int i = tid; i < p.HG2; i += blockDim.x) st_gran_local(base + (long)j * p.HG2 + i, 0ull);
-        for (int i = tid; i < p.QG2; i += blockDim.x) st_gran_local(base + (long)NT * p.HG2 + (long)j * p.QG2 + i, 0ull);
-        for (int i = tid; i < p.SG2; i += blockDim.x) st_gran_local(base + (long)NT * (p.HG2 + p.QG2) + (long)j * p.SG2 + i, 0ull);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    FwdCl cl_ = fwd_cl(p, b, j, s_x2, s_q, s_attp, s_g, s_stage, &s_scale[0][0], epoch_);
+    clear_own_records(cl_, tid, blockDim.x);
     __syncthreads();
-    const bool local = xcd_consensus(reinterpret_cast<u64*>(p.status) + 64 + b, NT, p.allow_local, p.status);
+    cl_.local = xcd_consensus(reinterpret_cast<u64*>(p.status) + 64 + b, NT, p.allow_local, p.status);
+    const FwdCl& cl = cl_;
 
     // ---- resident data
     for (int i = tid; i < TE * A; i += blockDim.x) {
@@ -153,61 +144,15 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
         // =========================== polling role ===========================
         const int gt = tid - 64 * NCW, np = 64 * NPW;
         for (int t = 0; t < L; ++t) {
-            // H: h_{t-1} of the utterance -> s_x[E ..]
-            if (t > 0) {
-                const u64* src = xb((t - 1) & 1);
-                const u64 want = pair_want(seq_of(t - 1), epoch_);
-                for (int i0 = gt; 2 * i0 < NT * p.HG2; i0 += np) {
-                    u64 lo[1], hi[1];
-                    gather16<1>(src + 2 * i0, 0, 1, PAIR_MASK, want, lo, hi, p.status);
-                    const int g0 = 2 * i0, prod = g0 / p.HG2, gi = g0 - prod * p.HG2;
-                    const int u = prod * p.UPW + 2 * gi;          // units 2gi, 2gi+1 (lo), 2gi+2, 2gi+3 (hi) of producer prod
-                    const float v[4] = {lo_f(lo[0]), hi_f(lo[0]), lo_f(hi[0]), hi_f(hi[0])};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (2 * gi + k < p.UPW && u + k < Dd) s_x2[(t & 1) * p.KCP + E + u + k] = v[k];
-                }
-            }
+            if (t > 0) poll_h(cl, t, gt, np);
             DP_JIT(0)
             __syncthreads();                                            // B1
             DP_JIT(1)
-            // Q: query of step t -> s_q
-            {
-                const u64* src = xb(t & 1) + (long)NT * p.HG2;
-                const u64 want = pair_want(seq_of(t), epoch_);
-                for (int i0 = gt; 2 * i0 < NT * p.QG2; i0 += np) {
-                    u64 lo[1], hi[1];
-                    gather16<1>(src + 2 * i0, 0, 1, PAIR_MASK, want, lo, hi, p.status);
-                    const int g0 = 2 * i0, prod = g0 / p.QG2, gi = g0 - prod * p.QG2;
-                    const int a = prod * p.QPW + 2 * gi;
-                    const float v[4] = {lo_f(lo[0]), hi_f(lo[0]), lo_f(hi[0]), hi_f(hi[0])};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (2 * gi + k < p.QPW && a + k < A) s_q[a + k] = v[k];
-                }
-            }
+            poll_q(cl, t, gt, np);
             DP_JIT(2)
             __syncthreads();                                            // B2
             DP_JIT(3)
-            // S: softmax records of all tiles -> s_stage (flat copy)
-            {
-                const u64* src = xb(t & 1) + (long)NT * (p.HG2 + p.QG2);
-                const u64 want = pair_want(seq_of(t), epoch_);
-                const int npair = NT * p.SG2 / 2;
-                for (int i0 = gt; i0 < npair; i0 += 10 * np) {
-                    u64 lo[10], hi[10];
-                    int cnt = 0;
-#pragma unroll
-                    for (int k = 0; k < 10; ++k) if (i0 + k * np < npair) cnt = k + 1;
-                    gather16<10>(src + 2 * i0, 2 * np, cnt, PAIR_MASK, want, lo, hi, p.status);
-#pragma unroll
-                    for (int k = 0; k < 10; ++k)
-                        if (k < cnt) {
-                            float4* o = reinterpret_cast<float4*>(s_stage + 4 * (long)(i0 + k * np));
-                            *o = make_float4(lo_f(lo[k]), hi_f(lo[k]), lo_f(hi[k]), hi_f(hi[k]));
-                        }
-                }
-            }
+            poll_s(cl, t, gt, np);
             DP_JIT(4)
             __syncthreads();                                            // B3
             DP_JIT(5)
@@ -217,47 +162,16 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
 
     // =========================== compute role ===========================
     unsigned gen = 0;
-    const int u_base = j * p.UPW, q_base = j * p.QPW, c_base = j * p.CPW;
-    const int SG2f = 2 * p.SG2;                                         // floats per staged record
     const float bg = p.w.bg[0];
     float c_state = 0.f;                                                // cell state of unit u_base + lane (wave 0, lane < UPW)
     const int RPW = (4 * p.UPW + NCW - 1) / NCW;                        // gate rows per wave
-    // sweep operands of this wave's column units (registers): W_proj(a, :) in the {hi, hi, lo} K slots, w_g(a)
     const int nu_cnt = (((A + 15) >> 4) - wave + NCW - 1) / NCW;
     bf16x8 wpx[FSW_NU];
     float wgu[FSW_NU];
-    {
-        const int q = lane >> 4, c = lane & 15;
-#pragma unroll
-        for (int nu = 0; nu < FSW_NU; ++nu) {
-            const int a = 16 * (wave + NCW * nu) + c;
-            const bool ok = a < A;
-            const float* wr = p.w.Wproj + (long)min(a, A - 1) * Kn;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int slot = 8 * q + i;
-                const int k = slot < KNMAX ? slot : (slot < 2 * KNMAX ? slot - KNMAX : slot - 2 * KNMAX);
-                const float w = (ok && slot < 3 * KNMAX && k < Kn) ? wr[min(k, Kn - 1)] : 0.f;
-                const __bf16 hi = (__bf16)w;
-                wpx[nu][i] = (slot < 2 * KNMAX) ? hi : (__bf16)(w - (float)hi);
-            }
-            wgu[nu] = ok ? p.w.wg[min(a, A - 1)] : 0.f;
-        }
-    }
+    sweep_operands<KNMAX>(cl, wave, lane, wpx, wgu);
     constexpr int QR = 2;                                               // query rounds with register-resident W_q rows
-    float wq0[QR][5], wq1[QR][5], bq0[QR], bq1[QR];
-#pragma unroll
-    for (int r2 = 0; r2 < QR; ++r2) {
-        const int o0 = 2 * wave + 2 * NCW * r2;
-        const int a0 = min(q_base + o0, A - 1), a1 = min(q_base + o0 + 1, A - 1);
-        bq0[r2] = p.w.bq[a0]; bq1[r2] = p.w.bq[a1];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int kk = min(lane + 64 * k, Dd - 1);
-            wq0[r2][k] = p.w.Wq[(long)a0 * Dd + kk];
-            wq1[r2][k] = p.w.Wq[(long)a1 * Dd + kk];
-        }
-    }
+    QRows<QR> qrows;
+    query_rows_load(cl, wave, lane, qrows);
     DP_DECL
 
     for (int t = 0; t < L; ++t) {
@@ -267,74 +181,12 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
         asm volatile("" : "+v"(tz), "+v"(lz_));
         const int lane = lz_;
         const long row = (long)b * L + t;
-        float* s_x = s_x2 + (t & 1) * p.KCP;
-        const u64 want = pair_want(seq_of(t), epoch_);
-        u64* out = xb(t & 1);
-        // operands of the cell phase that do not depend on this step's hand-offs: requested now
-        float add_r = 0.f;                                              // lane r of the wave: embproj + both biases of its gate row
-        {
-            const int r = wave * RPW + lane;
-            if (lane < RPW && r < 4 * p.UPW) {
-                const int g = r / p.UPW, ul = r - g * p.UPW, unit = u_base + ul;
-                if (unit < Dd) {
-                    const int grow = g * Dd + unit;
-                    add_r = p.embproj[row * 4 * Dd + grow] + p.w.bih[0][grow] + p.w.bhh[0][grow];
-                }
-            }
-        }
+        const FwdStep st{t, row, s_x2 + (t & 1) * p.KCP, cl.xb(t & 1), pair_want(seq_of(t), epoch_), wave, lane, tz};
+        const float add_r = cell_add_r(cl, st, RPW);                     // requested now, used in the cell phase
         DP_MARK(0)
         __syncthreads();                                                // B1: s_x holds h_{t-1}
         DP_MARK(1)
-        // ---- query slice: outputs q_base + o, two per wave per round, lanes over the reduction; the W_q rows of the first QR
-        //      rounds are register-resident for the whole launch (no L2 round trip on the step's critical path)
-        for (int o0 = 2 * wave, rd = 0; o0 < p.QPW; o0 += 2 * NCW, ++rd) {
-            float acc0 = 0.f, acc1 = 0.f;
-            const int a0 = min(q_base + o0, A - 1), a1 = min(q_base + o0 + 1, A - 1);
-            float b0 = 0.f, b1 = 0.f;                                    // bias: registers for the resident rounds (a load inside
-            if (rd < QR) {                                               // the lane-0 branch below would be a round trip per round)
-#pragma unroll
-                for (int r2 = 0; r2 < QR; ++r2) if (r2 == rd) { b0 = bq0[r2]; b1 = bq1[r2]; }
-            } else {
-                b0 = p.w.bq[a0]; b1 = p.w.bq[a1];
-            }
-            if (t > 0) {
-                float w0[5], w1[5];
-                if (rd < QR) {
-#pragma unroll
-                    for (int r2 = 0; r2 < QR; ++r2)
-                        if (r2 == rd) {
-#pragma unroll
-                            for (int k = 0; k < 5; ++k) { w0[k] = wq0[r2][k]; w1[k] = wq1[r2][k]; }
-                        }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) {
-                        const int kk = min(lane + 64 * k, Dd - 1);
-                        w0[k] = p.w.Wq[(long)a0 * Dd + kk];
-                        w1[k] = p.w.Wq[(long)a1 * Dd + kk];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 5; ++k) {
-                    const float hv = (lane + 64 * k < Dd) ? s_x[E + lane + 64 * k] : 0.f;
-                    acc0 += w0[k] * hv; acc1 += w1[k] * hv;
-                }
-                for (int kk = lane + 320; kk < Dd; kk += 64) { const float hv = s_x[E + kk]; acc0 += p.w.Wq[(long)a0 * Dd + kk] * hv; acc1 += p.w.Wq[(long)a1 * Dd + kk] * hv; }
-                acc0 = wave_sum_dpp(acc0); acc1 = wave_sum_dpp(acc1);
-            }
-            if (lane == 0) {
-                const float q0 = tanh_f(acc0 + b0), q1 = tanh_f(acc1 + b1);
-                u64* dst = out + (long)NT * p.HG2 + (long)j * p.QG2 + (o0 >> 1);
-                if (local) publish<true>(dst, pack2(q0, q1, want)); else publish<false>(dst, pack2(q0, q1, want));     // the hop first
-                if (q_base + o0 < A) p.s.q[row * A + q_base + o0] = q0;
-                if (o0 + 1 < p.QPW && q_base + o0 + 1 < A) p.s.q[row * A + q_base + o0 + 1] = q1;
-            }
-        }
-        // pad granule of an odd record length (the gather reads 16-byte pairs)
-        if (tz == 0 && (p.QPW + 1) / 2 < p.QG2) {
-            u64* dst = out + (long)NT * p.HG2 + (long)j * p.QG2 + p.QG2 - 1;
-            if (local) publish<true>(dst, pack2(0.f, 0.f, want)); else publish<false>(dst, pack2(0.f, 0.f, want));
-        }
+        query_slice<QR>(cl, st, qrows);
         DP_MARK(2)
         // ---- location convolution of the tile from the previous attention row (runs while the query is gathered): a Toeplitz
         //      product on the matrix cores (decoder_cluster.h::conv_mfma).  A lane ends up with four kernels of one frame: the
@@ -406,10 +258,7 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float v = ep[mt][r];
-#define DPF_STEP(CTRL) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-                    DPF_STEP(0xB1) DPF_STEP(0x4E) DPF_STEP(0x141) DPF_STEP(0x140)      // sum over the 16 lanes of the row
-#undef DPF_STEP
+                    const float v = sum16_dpp(ep[mt][r]);                   // sum over the 16 lanes of the row
                     if (c == 0) s_epart[wave * EPL + 16 * mt + 4 * q + r] = v;
                 }
         }
@@ -440,23 +289,22 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
                     x1 += wf * __uint_as_float(pr & 0xffff0000u);
                 }
             }
-            u64* rec = out + (long)NT * (p.HG2 + p.QG2) + (long)j * p.SG2;
+            u64* rec = st.out + cl.offS + (long)j * p.SG2;
             const int ghead = (TE + 2) >> 1;                             // granules of e[TE], m, s
             // context columns 4 at a time as halves (pack4h): the even threads take their neighbour's pair
             const float y0 = __shfl_down(x0, 1), y1 = __shfl_down(x1, 1);
             if (2 * c2 < E && (c2 & 1) == 0) {
-                if (local) publish<true>(rec + ghead + (c2 >> 1), pack4h(x0, x1, y0, y1, want)); else publish<false>(rec + ghead + (c2 >> 1), pack4h(x0, x1, y0, y1, want));
+                publish_gran(cl.local, rec + ghead + (c2 >> 1), pack4h(x0, x1, y0, y1, st.want));
             }
             // e pairs, (m, s) and the pad granule by the last compute wave's lanes
             if (wave == NCW - 1) {
                 const float e0 = __shfl(ev, min(2 * lane, 63)), e1 = __shfl(ev, min(2 * lane + 1, 63));
                 if (lane < TE / 2) {
-                    if (local) publish<true>(rec + lane, pack2(e0, e1, want)); else publish<false>(rec + lane, pack2(e0, e1, want));
+                    publish_gran(cl.local, rec + lane, pack2(e0, e1, st.want));
                 } else if (lane == TE / 2) {
-                    if (local) publish<true>(rec + lane, pack2(m, ssum, want)); else publish<false>(rec + lane, pack2(m, ssum, want));
+                    publish_gran(cl.local, rec + lane, pack2(m, ssum, st.want));
                 } else if (lane == TE / 2 + 1 && ghead + E / 4 < p.SG2) {
-                    u64* dst = rec + p.SG2 - 1;
-                    if (local) publish<true>(dst, pack2(0.f, 0.f, want)); else publish<false>(dst, pack2(0.f, 0.f, want));
+                    publish_gran(cl.local, rec + p.SG2 - 1, pack2(0.f, 0.f, st.want));
                 }
             }
         }
@@ -464,118 +312,16 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_persist(PD p) {
         __syncthreads();                                                // B3: s_stage holds every tile's record
         DP_MARK(8)
         // ---- attention row and context of the utterance
-        {
-            float mi = NEG_BIG, si = 0.f;
-            if (lane < NT) { mi = s_stage[lane * SG2f + TE]; si = s_stage[lane * SG2f + TE + 1]; }
-            const float M = wave_max_dpp(mi);
-            const float wi = (lane < NT) ? si * __expf(mi - M) : 0.f;
-            const float S = fmaxf(wave_sum_dpp(wi), 1e-30f);
-            const float invS = 1.f / S;
-            if (lane < 32) s_scale[wave][lane] = (lane < NT) ? __expf(mi - M) * invS : 0.f;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            for (int tau = tz; tau < Tp; tau += 64 * NCW) {
-                const int i = tau / TE, f = tau - i * TE;
-                const float ev = s_stage[i * SG2f + f];
-                const float av = (ev > 0.5f * NEG_BIG) ? __expf(ev - M) * invS : 0.f;
-                s_attp[Ks + tau] = av;
-                if (i == j) p.s.att[row * Tp + tau] = av;
-            }
-            for (int c2_ = tz; 2 * c2_ < E; c2_ += 64 * NCW) {           // two columns per staged word (halves, pack4h)
-                float a0 = 0.f, a1 = 0.f;
-                for (int i = 0; i < NT; ++i) {
-                    const unsigned w_ = __float_as_uint(s_stage[i * SG2f + TE + 2 + c2_]);
-                    a0 += h2f_lo(w_) * s_scale[wave][i]; a1 += h2f_hi(w_) * s_scale[wave][i];
-                }
-                const int c = 2 * c2_;
-                s_x[c] = a0; s_x[c + 1] = a1;
-                if (c >= c_base && c < c_base + p.CPW) p.s.xin[row * XW + Dd + c] = a0;
-                if (c + 1 >= c_base && c + 1 < c_base + p.CPW) p.s.xin[row * XW + Dd + c + 1] = a1;
-            }
-        }
+        combine_records(cl, st, TE);
         DP_MARK(9)
         compute_barrier(&s_bar, gen);                                   // c5: s_x holds [ctx_t | h_{t-1}]
         DP_MARK(10)
-        // ---- LSTM cell: gate rows r = g*UPW + ul of this workgroup, RPW rows per wave, lanes over 16-byte chunks
-        //      RBF = 10 rows per batch of loads: the 10 rows per wave of the bench shape (80 rows, 8 waves) are ONE L2 round trip, not
-        //      two.  The phase stays near the L2's bandwidth: 32 workgroups per XCD x 151 KB of rows per step.  Keeping rows in registers
-        //      across all twelve waves was tried (round 3): the 168-register budget holds 40 of the 80 rows without spilling
-        //      (4 per polling wave beside its 10-wide polls, 3 per compute wave); cell rows 2.3 -> 1.9 us, but the compute waves' other
-        //      phases lost as much (stats + ctx 1.2 -> 1.8 us) - not adopted.
-        {
-            constexpr int RBF = 10;
-            const int nchunk = p.KCP >> 3;
-            float mine = 0.f;
-#pragma unroll 1
-            for (int bt = 0; bt * RBF < RPW; ++bt) {
-                float part[RBF];
-#pragma unroll
-                for (int rr = 0; rr < RBF; ++rr) part[rr] = 0.f;
-                for (int ch0 = lane; ch0 < nchunk; ch0 += 128) {
-                    uint4 wv[RBF][2];
-#pragma unroll
-                    for (int rr = 0; rr < RBF; ++rr) {
-                        const int r = min(wave * RPW + bt * RBF + rr, 4 * p.UPW - 1);
-                        const int g = r / p.UPW, ul = r - g * p.UPW;
-                        const long grow = (long)g * Dd + min(u_base + ul, Dd - 1);
-#pragma unroll
-                        for (int h2 = 0; h2 < 2; ++h2)
-                            wv[rr][h2] = *reinterpret_cast<const uint4*>(p.wcat16 + grow * p.KCP + 8 * min(ch0 + 64 * h2, nchunk - 1));
-                    }
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int ch = ch0 + 64 * h2;
-                        if (ch < nchunk) {
-                            const float4 xa = *reinterpret_cast<const float4*>(s_x + 8 * ch);
-                            const float4 xb4 = *reinterpret_cast<const float4*>(s_x + 8 * ch + 4);
-#pragma unroll
-                            for (int rr = 0; rr < RBF; ++rr) {
-                                const uint4 w4 = wv[rr][h2];
-                                part[rr] += __uint_as_float(w4.x << 16) * xa.x + __uint_as_float(w4.x & 0xffff0000u) * xa.y +
-                                            __uint_as_float(w4.y << 16) * xa.z + __uint_as_float(w4.y & 0xffff0000u) * xa.w +
-                                            __uint_as_float(w4.z << 16) * xb4.x + __uint_as_float(w4.z & 0xffff0000u) * xb4.y +
-                                            __uint_as_float(w4.w << 16) * xb4.z + __uint_as_float(w4.w & 0xffff0000u) * xb4.w;
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int rr = 0; rr < RBF; ++rr) {
-                    const float sv = wave_sum_dpp(part[rr]);
-                    if (lane == bt * RBF + rr) mine = sv;
-                }
-            }
-            const int r = wave * RPW + lane;
-            if (lane < RPW && r < 4 * p.UPW) s_g[r] = mine + add_r;
-        }
+        // ---- LSTM cell: gate pre-activations, then the update of the UPW <= 64 units by wave 0
+        cell_rows<10>(cl, st, RPW, add_r);
         DP_MARK(11)
         compute_barrier(&s_bar, gen);                                   // c6: s_g holds the gate pre-activations
         DP_MARK(12)
-        if (wave == 0) {
-            const int unit = u_base + lane;
-            const bool uok = lane < p.UPW && unit < Dd;
-            float hv = 0.f;
-            // the hop starts at the publish: the activations use the fast exp / rcp forms (1 - 2 ulp) and the granule leaves
-            // BEFORE the six stores of the step's saved state (one in-order vector-memory queue per wave)
-            float ai = 0.f, af = 0.f, ag = 0.f, ao = 0.f;
-            if (uok) {
-                ai = sigm_f(s_g[lane]); af = sigm_f(s_g[p.UPW + lane]);
-                ag = tanh_f(s_g[2 * p.UPW + lane]); ao = sigm_f(s_g[3 * p.UPW + lane]);
-                c_state = af * c_state + ai * ag;
-                hv = ao * tanh_f(c_state);
-            }
-            const float hn = __shfl_down(hv, 1);
-            if (t + 1 < L && (lane & 1) == 0 && lane < 2 * p.HG2) {
-                u64* dst = out + (long)j * p.HG2 + (lane >> 1);
-                if (local) publish<true>(dst, pack2(hv, hn, want)); else publish<false>(dst, pack2(hv, hn, want));
-            }
-            if (uok) {
-                float* go = p.s.gates + row * 4 * Dd;
-                go[unit] = ai; go[Dd + unit] = af; go[2 * Dd + unit] = ag; go[3 * Dd + unit] = ao;
-                p.s.cs[row * Dd + unit] = c_state;
-                p.s.hs[row * Dd + unit] = hv;
-            }
-        }
+        cell_update<false>(cl, st, c_state);
         DP_MARK(13)
     }
     DP_DUMP
@@ -807,7 +553,7 @@ __global__ __launch_bounds__(512) void dec_bwd_persist(PB p) {
             if (t > 0) poll_copy<4>(base + offN, NT * p.NG2 / 2, s_nrec, gt, np, want, p.status);
             __syncthreads();                                            // H4
         }
-        DPB_SWEEP_RESULTS(SW_NUP)
+        DPB_SWEEP_RESULTS(SW_NUP, true, p.dkey, TE)
         return;
     }
 
@@ -849,23 +595,7 @@ __global__ __launch_bounds__(512) void dec_bwd_persist(PB p) {
         u64* out = xb(s & 1);
         DP_MARK(0)
         // ---- S1: cell backward of ALL hidden units (thread per unit; every workgroup of the cluster computes the same)
-        {
-            float dh = pdh;
-            if (s > 0) dh += s_crec[ui * CG2f + p.CPW + uul] + s_nrec[ui * NG2f + TE + uul];
-            const float tc = tanhf(pct);
-            const float dc = dh * pgo * (1.f - tc * tc) + dc_carry;
-            const float d0 = dc * pgg * pgi * (1.f - pgi), d1 = dc * pcp * pgf * (1.f - pgf);
-            const float d2 = dc * pgi * (1.f - pgg * pgg), d3 = dh * tc * pgo * (1.f - pgo);
-            dc_carry = dc * pgf;
-            if (uok) {
-                s_dg16[tz] = f2bf_bits(d0); s_dg16[Dd + tz] = f2bf_bits(d1);
-                s_dg16[2 * Dd + tz] = f2bf_bits(d2); s_dg16[3 * Dd + tz] = f2bf_bits(d3);
-            }
-            if (uown) {
-                float* go = p.dgates + row * 4 * Dd + tz;
-                go[0] = d0; go[Dd] = d1; go[2 * Dd] = d2; go[3 * Dd] = d3;
-            }
-        }
+        DPB_S1(TE)
         DP_MARK(1)
         __syncthreads();                                                // Ba
         DP_MARK(2)
@@ -875,18 +605,7 @@ __global__ __launch_bounds__(512) void dec_bwd_persist(PB p) {
         __syncthreads();                                                // Bb
         DP_MARK(4)
         // ---- C record {dctx slice | dh_rec slice} + global dxin (context part)
-        if (tz < p.CG2) {
-            float v[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int i = 2 * tz + h;
-                const bool ok = (i < p.CPW) ? (c_base + i < E) : (i < nout && u_base + (i - p.CPW) < Dd);
-                v[h] = ok ? s_out[min(i, RPWB * 8 - 1)] : 0.f;
-                if (i < p.CPW && c_base + i < E) p.dxin[row * XW + Dd + c_base + i] = v[h];
-            }
-            u64* dst = out + offC + (long)j * p.CG2 + tz;
-            if (local) publish<true>(dst, pack2(v[0], v[1], want)); else publish<false>(dst, pack2(v[0], v[1], want));
-        }
+        if (tz < p.CG2) DPB_C_GRANULE(tz, RPWB * 8 - 1)
         // ---- operands of P2/P3 that do not depend on the hand-offs: requested now, used behind H2
         float qa[SW_NU];
 #pragma unroll
@@ -1041,7 +760,7 @@ __global__ __launch_bounds__(512) void dec_bwd_persist(PB p) {
                     const unsigned short* wr = s_wq16 + ul * AQ + lane;
                     float acc = 0.f;
 #pragma unroll
-                    for (int k5 = 0; k5 < 5; ++k5) if (64 * k5 < AQ) acc += dqr[k5] * bf2f_(wr[64 * k5]);
+                    for (int k5 = 0; k5 < 5; ++k5) if (64 * k5 < AQ) acc += dqr[k5] * bf2f(wr[64 * k5]);
                     acc = wave_sum_dpp(acc);
                     if (lane == 0) s_hq[ul] = acc;
                 }
@@ -1081,7 +800,7 @@ __global__ __launch_bounds__(512) void dec_bwd_persist(PB p) {
     }
     DP_DUMP
     // ---- results that were accumulated on chip: the slot of this workgroup, the dkey tile
-    DPB_SWEEP_RESULTS(SW_NU)
+    DPB_SWEEP_RESULTS(SW_NU, true, p.dkey, TE)
     if (dbg != 0.f) atomicAdd(p.slots + ((long)b * NT + j) * p.slot + A * (1 + Kn), dbg);     // slots are zero on entry
 }
 

@@ -14,7 +14,7 @@
 //     utterance's length are skipped, and the softmax statistics / partial context are two passes over the tile
 //     (energies -> (m, s) -> weights in LDS -> weighted sum of the streamed enc rows), so nothing scales with TEB but LDS rows.
 // Exchange records, tags, epochs, XCD-local consensus, poll / compute wave roles: decoder_cluster.h, as in decoder_persist.hip.
-#include "decoder_cluster.h"
+#include "decoder_fwd_common.h"
 
 namespace {
 
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_stream(PSF p) {
     const unsigned epoch_ = __builtin_amdgcn_readfirstlane(p.status[EPOCH_WORD]);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int NT = p.NT, TEB = p.TEB, A = d.A, E = d.E, Dd = d.Dd, Tp = d.Tp, Kn = d.Kn, Ks = d.Ks, L = d.L;
-    const int taps = 2 * Ks + 1, XW = Dd + E;
+    const int taps = 2 * Ks + 1;
     const int tau0 = j * TEB;
     const int len = min((int)p.enc_len[b], Tp);
     const int nf = max(0, min(len - tau0, TEB));                        // valid frames of this tile
@@ -72,18 +72,11 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_stream(PSF p) {
     float* s_cpart = s_f + cv_.cpart;                                                   // [NG][E] partial context per frame group
     float* s_stage = s_f + cv_.stage;                                                   // [NT][2*SG2]
     if (tid == 0) s_bar = 0u;
-    const long region = (long)NT * (p.HG2 + p.QG2 + p.SG2);
-    auto xb = [&](int parity) { return p.xbuf + ((long)parity * d.B + b) * region; };
-    // every producer clears its own records with the L2-local store flavour before the consensus (decoder_persist.hip)
-    for (int parity = 0; parity < 2; ++parity) {
-        u64* base = xb(parity);
-        for (int i = tid; i < p.HG2; i += blockDim.x) st_gran_local(base + (long)j * p.HG2 + i, 0ull);
-        for (int i = tid; i < p.QG2; i += blockDim.x) st_gran_local(base + (long)NT * p.HG2 + (long)j * p.QG2 + i, 0ull);
-        for (int i = tid; i < p.SG2; i += blockDim.x) st_gran_local(base + (long)NT * (p.HG2 + p.QG2) + (long)j * p.SG2 + i, 0ull);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    FwdCl cl_ = fwd_cl(p, b, j, s_x2, s_q, s_attp, s_g, s_stage, &s_scale[0][0], epoch_);
+    clear_own_records(cl_, tid, blockDim.x);       // before the consensus (decoder_fwd_common.h)
     __syncthreads();
-    const bool local = xcd_consensus(reinterpret_cast<u64*>(p.status) + 64 + b, NT, p.allow_local, p.status);
+    cl_.local = xcd_consensus(reinterpret_cast<u64*>(p.status) + 64 + b, NT, p.allow_local, p.status);
+    const FwdCl& cl = cl_;
 
     // ---- resident data (small: nothing here scales with the tile but LDS rows)
     for (int i = tid; i < TEB * FCVX_LD; i += blockDim.x) s_cvx[i] = 0;
@@ -103,70 +96,31 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_stream(PSF p) {
         // =========================== polling role (as in dec_fwd_persist) ===========================
         const int gt = tid - 64 * NCW, np = 64 * NPW;
         for (int t = 0; t < L; ++t) {
-            if (t > 0) {
-                const u64* src = xb((t - 1) & 1);
-                const u64 want = pair_want(seq_of(t - 1), epoch_);
-                for (int i0 = gt; 2 * i0 < NT * p.HG2; i0 += np) {
-                    u64 lo[1], hi[1];
-                    gather16<1>(src + 2 * i0, 0, 1, PAIR_MASK, want, lo, hi, p.status);
-                    const int g0 = 2 * i0, prod = g0 / p.HG2, gi = g0 - prod * p.HG2;
-                    const int u = prod * p.UPW + 2 * gi;
-                    const float v[4] = {lo_f(lo[0]), hi_f(lo[0]), lo_f(hi[0]), hi_f(hi[0])};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (2 * gi + k < p.UPW && u + k < Dd) s_x2[(t & 1) * p.KCP + E + u + k] = v[k];
-                }
-            }
+            if (t > 0) poll_h(cl, t, gt, np);
+            DP_JIT(0)
             __syncthreads();                                            // B1
-            {
-                const u64* src = xb(t & 1) + (long)NT * p.HG2;
-                const u64 want = pair_want(seq_of(t), epoch_);
-                for (int i0 = gt; 2 * i0 < NT * p.QG2; i0 += np) {
-                    u64 lo[1], hi[1];
-                    gather16<1>(src + 2 * i0, 0, 1, PAIR_MASK, want, lo, hi, p.status);
-                    const int g0 = 2 * i0, prod = g0 / p.QG2, gi = g0 - prod * p.QG2;
-                    const int a = prod * p.QPW + 2 * gi;
-                    const float v[4] = {lo_f(lo[0]), hi_f(lo[0]), lo_f(hi[0]), hi_f(hi[0])};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (2 * gi + k < p.QPW && a + k < A) s_q[a + k] = v[k];
-                }
-            }
+            DP_JIT(1)
+            poll_q(cl, t, gt, np);
+            DP_JIT(2)
             __syncthreads();                                            // B2
-            poll_copy<10>(xb(t & 1) + (long)NT * (p.HG2 + p.QG2), NT * p.SG2 / 2, s_stage, gt, np, pair_want(seq_of(t), epoch_), p.status);
+            DP_JIT(3)
+            poll_s(cl, t, gt, np);
+            DP_JIT(4)
             __syncthreads();                                            // B3
+            DP_JIT(5)
         }
         return;
     }
 
     // =========================== compute role ===========================
     unsigned gen = 0;
-    const int u_base = j * p.UPW, q_base = j * p.QPW, c_base = j * p.CPW;
-    const int SG2f = 2 * p.SG2;
     const float bg = p.w.bg[0];
     float c_state = 0.f;                                                // cell state of unit u_base + tid (waves 0, 1; tid < UPW)
     const int RPW = (4 * p.UPW + NCW - 1) / NCW;                        // gate rows per wave (<= 60)
     const int nu_cnt = (((A + 15) >> 4) - wave + NCW - 1) / NCW;
     bf16x8 wpx[FSW_NU];
     float wgu[FSW_NU];
-    {
-        const int q = lane >> 4, c = lane & 15;
-#pragma unroll
-        for (int nu = 0; nu < FSW_NU; ++nu) {
-            const int a = 16 * (wave + NCW * nu) + c;
-            const bool ok = a < A;
-            const float* wr = p.w.Wproj + (long)min(a, A - 1) * Kn;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int sl = 8 * q + i;
-                const int k = sl < KNMAX ? sl : (sl < 2 * KNMAX ? sl - KNMAX : sl - 2 * KNMAX);
-                const float w = (ok && sl < 3 * KNMAX && k < Kn) ? wr[min(k, Kn - 1)] : 0.f;
-                const __bf16 hi = (__bf16)w;
-                wpx[nu][i] = (sl < 2 * KNMAX) ? hi : (__bf16)(w - (float)hi);
-            }
-            wgu[nu] = ok ? p.w.wg[min(a, A - 1)] : 0.f;
-        }
-    }
+    sweep_operands<KNMAX>(cl, wave, lane, wpx, wgu);
     const int G4 = (NT * TEB) >> 2;                                     // frame groups per utterance in key16t
     const int nch = E >> 3;                                             // 16-byte chunks of an enc row
     DP_DECL
@@ -176,56 +130,12 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_stream(PSF p) {
         asm volatile("" : "+v"(tz), "+v"(lz_));                        // ties the index arithmetic to the step (decoder_persist.hip)
         const int lane = lz_;
         const long row = (long)b * L + t;
-        float* s_x = s_x2 + (t & 1) * p.KCP;
-        const u64 want = pair_want(seq_of(t), epoch_);
-        u64* out = xb(t & 1);
-        float add_r = 0.f;                                              // lane r of the wave: embproj + both biases of its gate row
-        {
-            const int r = wave * RPW + lane;
-            if (lane < RPW && r < 4 * p.UPW) {
-                const int g = r / p.UPW, ul = r - g * p.UPW, unit = u_base + ul;
-                if (unit < Dd) {
-                    const int grow = g * Dd + unit;
-                    add_r = p.embproj[row * 4 * Dd + grow] + p.w.bih[0][grow] + p.w.bhh[0][grow];
-                }
-            }
-        }
+        const FwdStep st{t, row, s_x2 + (t & 1) * p.KCP, cl.xb(t & 1), pair_want(seq_of(t), epoch_), wave, lane, tz};
+        const float add_r = cell_add_r(cl, st, RPW);                    // requested now, used in the cell phase
         DP_MARK(0)
         __syncthreads();                                                // B1: s_x holds h_{t-1}
         DP_MARK(1)
-        // ---- query slice: outputs q_base + o, two per wave per round, lanes over the reduction
-        for (int o0 = 2 * wave; o0 < p.QPW; o0 += 2 * NCW) {
-            float acc0 = 0.f, acc1 = 0.f;
-            const int a0 = min(q_base + o0, A - 1), a1 = min(q_base + o0 + 1, A - 1);
-            const float b0 = p.w.bq[a0], b1 = p.w.bq[a1];
-            if (t > 0) {
-                float w0[5], w1[5];
-#pragma unroll
-                for (int k = 0; k < 5; ++k) {
-                    const int kk = min(lane + 64 * k, Dd - 1);
-                    w0[k] = p.w.Wq[(long)a0 * Dd + kk];
-                    w1[k] = p.w.Wq[(long)a1 * Dd + kk];
-                }
-#pragma unroll
-                for (int k = 0; k < 5; ++k) {
-                    const float hv = (lane + 64 * k < Dd) ? s_x[E + lane + 64 * k] : 0.f;
-                    acc0 += w0[k] * hv; acc1 += w1[k] * hv;
-                }
-                for (int kk = lane + 320; kk < Dd; kk += 64) { const float hv = s_x[E + kk]; acc0 += p.w.Wq[(long)a0 * Dd + kk] * hv; acc1 += p.w.Wq[(long)a1 * Dd + kk] * hv; }
-                acc0 = wave_sum_dpp(acc0); acc1 = wave_sum_dpp(acc1);
-            }
-            if (lane == 0) {
-                const float q0 = tanh_f(acc0 + b0), q1 = tanh_f(acc1 + b1);
-                u64* dst = out + (long)NT * p.HG2 + (long)j * p.QG2 + (o0 >> 1);
-                if (local) publish<true>(dst, pack2(q0, q1, want)); else publish<false>(dst, pack2(q0, q1, want));     // the hop first
-                if (q_base + o0 < A) p.s.q[row * A + q_base + o0] = q0;
-                if (o0 + 1 < p.QPW && q_base + o0 + 1 < A) p.s.q[row * A + q_base + o0 + 1] = q1;
-            }
-        }
-        if (tz == 0 && (p.QPW + 1) / 2 < p.QG2) {                       // pad granule of an odd record length
-            u64* dst = out + (long)NT * p.HG2 + (long)j * p.QG2 + p.QG2 - 1;
-            if (local) publish<true>(dst, pack2(0.f, 0.f, want)); else publish<false>(dst, pack2(0.f, 0.f, want));
-        }
+        query_slice<0>(cl, st, QRows<0>{});
         DP_MARK(2)
         // ---- location convolution of the tile from the previous attention row (runs while the query is gathered): a Toeplitz
         //      product on the matrix cores (decoder_cluster.h::conv_mfma).  A lane ends up with four kernels of one frame: the
@@ -313,10 +223,7 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_stream(PSF p) {
                                 }
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
-                                    float v = ep[r];
-#define DPF_STEP(CTRL) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-                                    DPF_STEP(0xB1) DPF_STEP(0x4E) DPF_STEP(0x141) DPF_STEP(0x140)      // sum over the 16 lanes of the row
-#undef DPF_STEP
+                                    const float v = sum16_dpp(ep[r]);   // sum over the 16 lanes of the row
                                     if (c == 0) s_epart[wave * TEB + 16 * mt + 4 * q + r] = v;
                                 }
                             }
@@ -395,137 +302,37 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void dec_fwd_stream(PSF p) {
                 o4[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
             }
             compute_barrier(&s_bar, gen);                               // s_cpart complete
-            u64* rec = out + (long)NT * (p.HG2 + p.QG2) + (long)j * p.SG2;
+            u64* rec = st.out + cl.offS + (long)j * p.SG2;
             const int ghead = (TEB + 2) >> 1;                            // granules of e[TEB], m, s
             const int c4 = tz;                                           // four context columns per granule, as halves (pack4h)
             if (4 * c4 < E) {
                 float x0 = 0.f, x1 = 0.f, x2 = 0.f, x3 = 0.f;
                 for (int g = 0; g < NG; ++g) { const float4 v = *reinterpret_cast<const float4*>(s_cpart + g * E + 4 * c4); x0 += v.x; x1 += v.y; x2 += v.z; x3 += v.w; }
-                if (local) publish<true>(rec + ghead + c4, pack4h(x0, x1, x2, x3, want)); else publish<false>(rec + ghead + c4, pack4h(x0, x1, x2, x3, want));
+                publish_gran(cl.local, rec + ghead + c4, pack4h(x0, x1, x2, x3, st.want));
             }
             for (int i = tz; i < (TEB >> 1); i += 64 * NCW) {
                 const float2 e2 = *reinterpret_cast<const float2*>(s_e + 2 * i);
-                if (local) publish<true>(rec + i, pack2(e2.x, e2.y, want)); else publish<false>(rec + i, pack2(e2.x, e2.y, want));
+                publish_gran(cl.local, rec + i, pack2(e2.x, e2.y, st.want));
             }
             if (tz == 64 * NCW - 1) {
-                if (local) publish<true>(rec + (TEB >> 1), pack2(m, ssum, want)); else publish<false>(rec + (TEB >> 1), pack2(m, ssum, want));
-                if (ghead + E / 4 < p.SG2) {
-                    if (local) publish<true>(rec + p.SG2 - 1, pack2(0.f, 0.f, want)); else publish<false>(rec + p.SG2 - 1, pack2(0.f, 0.f, want));
-                }
+                publish_gran(cl.local, rec + (TEB >> 1), pack2(m, ssum, st.want));
+                if (ghead + E / 4 < p.SG2) publish_gran(cl.local, rec + p.SG2 - 1, pack2(0.f, 0.f, st.want));
             }
         }
         DP_MARK(8)
         __syncthreads();                                                // B3: s_stage holds every tile's record
         DP_MARK(9)
         // ---- attention row and context of the utterance (online-softmax combine of the tiles)
-        {
-            float mi = NEG_BIG, si = 0.f;
-            if (lane < NT) { mi = s_stage[lane * SG2f + TEB]; si = s_stage[lane * SG2f + TEB + 1]; }
-            const float M = wave_max_dpp(mi);
-            const float wi = (lane < NT) ? si * __expf(mi - M) : 0.f;
-            const float S = fmaxf(wave_sum_dpp(wi), 1e-30f);
-            const float invS = 1.f / S;
-            if (lane < 32) s_scale[wave][lane] = (lane < NT) ? __expf(mi - M) * invS : 0.f;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            for (int tau = tz; tau < Tp; tau += 64 * NCW) {
-                const int i = tau / TEB, f = tau - i * TEB;
-                const float ev = s_stage[i * SG2f + f];
-                const float av = (ev > 0.5f * NEG_BIG) ? __expf(ev - M) * invS : 0.f;
-                s_attp[Ks + tau] = av;
-                if (i == j) p.s.att[row * Tp + tau] = av;
-            }
-            for (int c2_ = tz; 2 * c2_ < E; c2_ += 64 * NCW) {           // two columns per staged word (halves, pack4h)
-                float a0 = 0.f, a1 = 0.f;
-                for (int i = 0; i < NT; ++i) {
-                    const unsigned w_ = __float_as_uint(s_stage[i * SG2f + TEB + 2 + c2_]);
-                    a0 += h2f_lo(w_) * s_scale[wave][i]; a1 += h2f_hi(w_) * s_scale[wave][i];
-                }
-                const int c = 2 * c2_;
-                s_x[c] = a0; s_x[c + 1] = a1;
-                if (c >= c_base && c < c_base + p.CPW) p.s.xin[row * XW + Dd + c] = a0;
-                if (c + 1 >= c_base && c + 1 < c_base + p.CPW) p.s.xin[row * XW + Dd + c + 1] = a1;
-            }
-        }
+        combine_records(cl, st, TEB);
         DP_MARK(10)
         compute_barrier(&s_bar, gen);                                   // c5: s_x holds [ctx_t | h_{t-1}]
         DP_MARK(11)
-        // ---- LSTM cell: gate rows r = g*UPW + ul of this workgroup, RPW rows per wave, lanes over 16-byte chunks; RBS = 8 rows
-        //      per batch of loads (each batch is one exposed L2 round trip: 38 rows per wave at config 5 are 5 batches, not 8)
-        {
-            constexpr int RBS = 8;
-            const int nchunk = p.KCP >> 3;
-            float mine = 0.f;
-#pragma unroll 1
-            for (int bt = 0; bt * RBS < RPW; ++bt) {
-                float part[RBS];
-#pragma unroll
-                for (int rr = 0; rr < RBS; ++rr) part[rr] = 0.f;
-                for (int ch0 = lane; ch0 < nchunk; ch0 += 128) {
-                    uint4 wv[RBS][2];
-#pragma unroll
-                    for (int rr = 0; rr < RBS; ++rr) {
-                        const int r = min(wave * RPW + bt * RBS + rr, 4 * p.UPW - 1);
-                        const int g = r / p.UPW, ul = r - g * p.UPW;
-                        const long grow = (long)g * Dd + min(u_base + ul, Dd - 1);
-#pragma unroll
-                        for (int h2 = 0; h2 < 2; ++h2)
-                            wv[rr][h2] = *reinterpret_cast<const uint4*>(p.wcat16 + grow * p.KCP + 8 * min(ch0 + 64 * h2, nchunk - 1));
-                    }
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int ch = ch0 + 64 * h2;
-                        if (ch < nchunk) {
-                            const float4 xa = *reinterpret_cast<const float4*>(s_x + 8 * ch);
-                            const float4 xb4 = *reinterpret_cast<const float4*>(s_x + 8 * ch + 4);
-#pragma unroll
-                            for (int rr = 0; rr < RBS; ++rr) {
-                                const uint4 w4 = wv[rr][h2];
-                                part[rr] += __uint_as_float(w4.x << 16) * xa.x + __uint_as_float(w4.x & 0xffff0000u) * xa.y +
-                                            __uint_as_float(w4.y << 16) * xa.z + __uint_as_float(w4.y & 0xffff0000u) * xa.w +
-                                            __uint_as_float(w4.z << 16) * xb4.x + __uint_as_float(w4.z & 0xffff0000u) * xb4.y +
-                                            __uint_as_float(w4.w << 16) * xb4.z + __uint_as_float(w4.w & 0xffff0000u) * xb4.w;
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int rr = 0; rr < RBS; ++rr) {
-                    const float sv = wave_sum_dpp(part[rr]);
-                    if (lane == bt * RBS + rr) mine = sv;
-                }
-            }
-            const int r = wave * RPW + lane;
-            if (lane < RPW && r < 4 * p.UPW) s_g[r] = mine + add_r;
-        }
+        // ---- LSTM cell: gate pre-activations, then the update of the UPW <= 128 units, thread per unit over two waves
+        cell_rows<8>(cl, st, RPW, add_r);
         DP_MARK(12)
         compute_barrier(&s_bar, gen);                                   // c6: s_g holds the gate pre-activations
         DP_MARK(13)
-        if (wave < 2) {                                                 // UPW <= 128 units: thread per unit over two waves
-            const int ul = tz, unit = u_base + ul;
-            const bool uok = ul < p.UPW && unit < Dd;
-            float hv = 0.f;
-            // the hop starts at the publish: the activations use the fast exp / rcp forms (1 - 2 ulp) and the granule leaves
-            // BEFORE the six stores of the step's saved state (one in-order vector-memory queue per wave)
-            float ai = 0.f, af = 0.f, ag = 0.f, ao = 0.f;
-            if (uok) {
-                ai = sigm_f(s_g[ul]); af = sigm_f(s_g[p.UPW + ul]);
-                ag = tanh_f(s_g[2 * p.UPW + ul]); ao = sigm_f(s_g[3 * p.UPW + ul]);
-                c_state = af * c_state + ai * ag;
-                hv = ao * tanh_f(c_state);
-            }
-            const float hn = __shfl_down(hv, 1);                        // pairs never straddle a wave (64 is even)
-            if (t + 1 < L && (ul & 1) == 0 && ul < 2 * p.HG2) {
-                u64* dst = out + (long)j * p.HG2 + (ul >> 1);
-                if (local) publish<true>(dst, pack2(hv, hn, want)); else publish<false>(dst, pack2(hv, hn, want));
-            }
-            if (uok) {
-                float* go = p.s.gates + row * 4 * Dd;
-                go[unit] = ai; go[Dd + unit] = af; go[2 * Dd + unit] = ag; go[3 * Dd + unit] = ao;
-                p.s.cs[row * Dd + unit] = c_state;
-                p.s.hs[row * Dd + unit] = hv;
-            }
-        }
+        cell_update<true>(cl, st, c_state);
     }
     DP_DUMP
 }
@@ -922,19 +729,7 @@ __global__ __launch_bounds__(512) void dec_bwd_stream(PSB p) {
             float dqt[SW_NUP];
             sweep_tile<KNMAX, SW_NUP, false, !RESIDENT>(p, S, qa, dqt, nu_cnt, wave, nw, lane, tid, nct, b, j, tau0, nf, len, row, AP,
                                               s_cvx, s_cvT, s_de, s_dl, s_wp16, base, offV, local, want);
-#pragma unroll
-            for (int nu = 0; nu < SW_NUP; ++nu) {
-                if (nu < nu_cnt) {
-                    const int a_ = 16 * (wave + nw * nu) + csub;
-                    const float tot_ = sum_groups(dqt[nu]);
-                    const float mine_ = (a_ < A) ? tot_ * (1.f - qa[nu] * qa[nu]) : 0.f;
-                    const float nb_ = __shfl_down(mine_, 1);
-                    if (qsub == 0 && (lane & 1) == 0 && a_ < 2 * p.QG2) {
-                        u64* dst_ = base + offQ + (long)j * p.QG2 + (a_ >> 1);
-                        if (local) publish<true>(dst_, pack2(mine_, nb_, want)); else publish<false>(dst_, pack2(mine_, nb_, want));
-                    }
-                }
-            }
+            DPB_PUBLISH_Q(base, SW_NUP, dqt)
             for (int z = 0; z < p.poll_delay; ++z) __builtin_amdgcn_s_sleep(127);
             {   // Q records of all tiles (flat copy) and the dconv frames [wlo, whi) of the utterance (all Kn rows), ONE polling sweep
                 const int nq = NT * p.QG2 / 2, npk = (whi - wlo) >> 2, nv = Kn * npk;
@@ -971,22 +766,7 @@ __global__ __launch_bounds__(512) void dec_bwd_stream(PSB p) {
             if (t > 0) poll_copy<4>(base + offN, NT * p.NG2 / 2, s_nrec, gt, np, want, p.status);
             __syncthreads();                                            // H4
         }
-        {   // d w_g and d W_proj of the wave's units -> the workgroup's slot
-            float* sl_ = p.slots + ((long)b * NT + j) * p.slot;
-#pragma unroll
-            for (int nu = 0; nu < SW_NUP; ++nu) {
-                if (nu < nu_cnt) {
-                    const int u0_ = 16 * (wave + nw * nu);
-                    const float g_ = sum_groups(S.dwg[nu]);
-                    if (qsub == 0 && u0_ + csub < A) sl_[u0_ + csub] = g_;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int a_ = u0_ + 4 * qsub + r;
-                        if (csub < Kn && a_ < A) sl_[A + csub * A + a_] = S.dwp[nu][r];
-                    }
-                }
-            }
-        }
+        DPB_SWEEP_RESULTS(SW_NUP, false, (float*)nullptr, 0)       // dkey went to dkT step by step: nothing to write here
         return;
     }
 
@@ -1026,23 +806,7 @@ __global__ __launch_bounds__(512) void dec_bwd_stream(PSB p) {
         u64* out = xb(s & 1);
         DP_MARK(0)
         // ---- S1: cell backward of ALL hidden units (thread per unit; every workgroup of the cluster computes the same)
-        {
-            float dh = pdh;
-            if (s > 0) dh += s_crec[ui * CG2f + p.CPW + uul] + s_nrec[ui * NG2f + TEB + uul];
-            const float tc = tanhf(pct);
-            const float dc = dh * pgo * (1.f - tc * tc) + dc_carry;
-            const float d0 = dc * pgg * pgi * (1.f - pgi), d1 = dc * pcp * pgf * (1.f - pgf);
-            const float d2 = dc * pgi * (1.f - pgg * pgg), d3 = dh * tc * pgo * (1.f - pgo);
-            dc_carry = dc * pgf;
-            if (uok) {
-                s_dg16[tz] = f2bf_bits(d0); s_dg16[Dd + tz] = f2bf_bits(d1);
-                s_dg16[2 * Dd + tz] = f2bf_bits(d2); s_dg16[3 * Dd + tz] = f2bf_bits(d3);
-            }
-            if (uown) {
-                float* go = p.dgates + row * 4 * Dd + tz;
-                go[0] = d0; go[Dd] = d1; go[2 * Dd] = d2; go[3 * Dd] = d3;
-            }
-        }
+        DPB_S1(TEB)
         DP_MARK(1)
         __syncthreads();                                                // Ba
         DP_MARK(2)
@@ -1053,18 +817,7 @@ __global__ __launch_bounds__(512) void dec_bwd_stream(PSB p) {
         __syncthreads();                                                // Bb
         DP_MARK(4)
         // ---- C record {dctx slice | dh_rec slice} + global dxin (context part)
-        for (int i2 = tz; i2 < p.CG2; i2 += nct) {
-            float v[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int i = 2 * i2 + h;
-                const bool ok = (i < p.CPW) ? (c_base + i < E) : (i < nout && u_base + (i - p.CPW) < Dd);
-                v[h] = ok ? s_out[min(i, nout - 1)] : 0.f;
-                if (i < p.CPW && c_base + i < E) p.dxin[row * XW + Dd + c_base + i] = v[h];
-            }
-            u64* dst = out + offC + (long)j * p.CG2 + i2;
-            if (local) publish<true>(dst, pack2(v[0], v[1], want)); else publish<false>(dst, pack2(v[0], v[1], want));
-        }
+        for (int i2 = tz; i2 < p.CG2; i2 += nct) DPB_C_GRANULE(i2, nout - 1)
         // ---- operands of P2/P3 that do not depend on the hand-offs: requested now, used behind H2
         float qa[SW_NU];
 #pragma unroll
@@ -1160,19 +913,7 @@ __global__ __launch_bounds__(512) void dec_bwd_stream(PSB p) {
             float dqt[SW_NU];
             sweep_tile<KNMAX, SW_NU, true, !RESIDENT>(p, S, qa, dqt, nu_cnt, wave, nw, lane, tz, nct, b, j, tau0, nf, len, row, AP,
                                             s_cvx, s_cvT, s_de, s_dl, s_wp16, out, offV, local, want);
-#pragma unroll
-            for (int nu = 0; nu < SW_NU; ++nu) {
-                if (nu < nu_cnt) {
-                    const int a_ = 16 * (wave + nw * nu) + csub;
-                    const float tot_ = sum_groups(dqt[nu]);
-                    const float mine_ = (a_ < A) ? tot_ * (1.f - qa[nu] * qa[nu]) : 0.f;
-                    const float nb_ = __shfl_down(mine_, 1);
-                    if (qsub == 0 && (lane & 1) == 0 && a_ < 2 * p.QG2) {
-                        u64* dst_ = out + offQ + (long)j * p.QG2 + (a_ >> 1);
-                        if (local) publish<true>(dst_, pack2(mine_, nb_, want)); else publish<false>(dst_, pack2(mine_, nb_, want));
-                    }
-                }
-            }
+            DPB_PUBLISH_Q(out, SW_NU, dqt)
         }
         DP_MARK(8)
         __syncthreads();                                                // H3: dq partials of all workgroups, the dconv window
@@ -1274,22 +1015,8 @@ __global__ __launch_bounds__(512) void dec_bwd_stream(PSB p) {
         DP_MARK(12)
     }
     DP_DUMP
-    {   // results accumulated on chip: d w_g, d W_proj of the wave's units -> the workgroup's slot
-        float* sl_ = p.slots + ((long)b * NT + j) * p.slot;
-#pragma unroll
-        for (int nu = 0; nu < SW_NU; ++nu) {
-            if (nu < nu_cnt) {
-                const int u0_ = 16 * (wave + nw * nu);
-                const float g_ = sum_groups(S.dwg[nu]);
-                if (qsub == 0 && u0_ + csub < A) sl_[u0_ + csub] = g_;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int a_ = u0_ + 4 * qsub + r;
-                    if (csub < Kn && a_ < A) sl_[A + csub * A + a_] = S.dwp[nu][r];
-                }
-            }
-        }
-    }
+    // ---- results that were accumulated on chip: the slot of this workgroup (dkey went to dkT step by step)
+    DPB_SWEEP_RESULTS(SW_NU, false, (float*)nullptr, 0)
     if (dbg != 0.f) atomicAdd(p.slots + ((long)b * NT + j) * p.slot + A * (1 + Kn), dbg);     // slots are zero on entry
 }
 

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float pre = acc[r] + xr[r] + bias[r];
-            a[r] = (g == 2) ? fast_tanh(pre) : fast_sigmoid(pre);
+            a[r] = (g == 2) ? tanh_f(pre) : sigm_f(pre);
         }
         const float4 o_gate = make_float4(a[0], a[1], a[2], a[3]);
         *reinterpret_cast<float4*>(gbuf + (g * 16 + n) * 20 + 4 * q) = o_gate;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
             const float4 go = *reinterpret_cast<const float4*>(gbuf + (3 * 16 + n) * 20 + 4 * q);
             cst.x = gf.x * cst.x + gi.x * gg.x; cst.y = gf.y * cst.y + gi.y * gg.y;
             cst.z = gf.z * cst.z + gi.z * gg.z; cst.w = gf.w * cst.w + gi.w * gg.w;
-            const float4 o_h = make_float4(go.x * fast_tanh(cst.x), go.y * fast_tanh(cst.y), go.z * fast_tanh(cst.z), go.w * fast_tanh(cst.w));
+            const float4 o_h = make_float4(go.x * tanh_f(cst.x), go.y * tanh_f(cst.y), go.z * tanh_f(cst.z), go.w * tanh_f(cst.w));
             if (s + 1 < T && bok) {
                 // bit 14 of a bf16 is clear for every |x| < 2; clearing it (only NaN/Inf are affected, and those
                 // still reach the loss through y) keeps the sequence bits (bits 14 and 30 of the granule) intact
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
     };
     struct Coef { float dy, c1, c2, c3, c4, c5, f; };
     auto make_coef = [&](const Raw& r) -> Coef {
-        const float tc = fast_tanh(r.c);
+        const float tc = tanh_f(r.c);
         Coef k;
         k.dy = r.dy;
         k.c1 = r.go * (1.f - tc * tc);          // d c / d h

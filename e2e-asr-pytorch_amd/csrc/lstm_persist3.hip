@@ -195,12 +195,12 @@ __global__ __launch_bounds__(512) void lstm_fwd_p3(P3 p) {
                 if (ks & 1) acc2 = mma16(wreg[ks], hb[ks], acc2); else acc = mma16(wreg[ks], hb[ks], acc);                   \
             }                                                                                                               \
         }                                                                                                                   \
-        const float gi = fast_sigmoid(acc[0] + acc2[0] + bf2f((unsigned short)(XG.x & 0xFFFFu)));                           \
-        const float gf = fast_sigmoid(acc[1] + acc2[1] + bf2f((unsigned short)(XG.x >> 16)));                               \
-        const float gg = fast_tanh(acc[2] + acc2[2] + bf2f((unsigned short)(XG.y & 0xFFFFu)));                              \
-        const float go = fast_sigmoid(acc[3] + acc2[3] + bf2f((unsigned short)(XG.y >> 16)));                               \
+        const float gi = sigm_f(acc[0] + acc2[0] + bf2f((unsigned short)(XG.x & 0xFFFFu)));                                 \
+        const float gf = sigm_f(acc[1] + acc2[1] + bf2f((unsigned short)(XG.x >> 16)));                                     \
+        const float gg = tanh_f(acc[2] + acc2[2] + bf2f((unsigned short)(XG.y & 0xFFFFu)));                                 \
+        const float go = sigm_f(acc[3] + acc2[3] + bf2f((unsigned short)(XG.y >> 16)));                                     \
         cst = gf * cst + gi * gg;                                                                                           \
-        const float hv = go * fast_tanh(cst);                                                                              \
+        const float hv = go * tanh_f(cst);                                                                                 \
         LSTM_DIAG_MARK(1)                                                                                                       \
         /* the wave's four units of batch row n sit in lanes n, n+16, n+32, n+48: collect them in lane n                    \
            (bit 14 of a bf16 is clear for |x| < 2; clearing it keeps the tag bits of the granule intact) */                 \
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
     auto make_coef = [&](const Raw& r) -> Coef {
         const float gi = bf2f((unsigned short)(r.g.x & 0xFFFFu)), gf = bf2f((unsigned short)(r.g.x >> 16));
         const float gg = bf2f((unsigned short)(r.g.y & 0xFFFFu)), go = bf2f((unsigned short)(r.g.y >> 16));
-        const float tc = fast_tanh(r.c);
+        const float tc = tanh_f(r.c);
         Coef k;
         k.dy = bf2f((unsigned short)r.dy);
         k.c1 = go * (1.f - tc * tc);          // d c / d h

@@ -1,5 +1,5 @@
 // What the persistent LSTM recurrence kernels share (lstm_persist.hip, lstm_persist2.hip, lstm_persist3.hip): granule tags,
-// fast activations, the diagnostic / jitter macros of the time loops and the checked launch.  Include after handoff.h.
+// the diagnostic / jitter macros of the time loops and the checked launch.  Include after handoff.h.
 // Everything here is `static` per translation unit.
 #pragma once
 #include "handoff.h"
@@ -37,11 +37,6 @@ __device__ __forceinline__ void lstm_jitter(unsigned k, unsigned step, unsigned 
 #define LSTM_DIAG_COUNT(k, v) { (void)(v); }
 #define LSTM_DIAG_DUMP(thr, word)
 #endif
-
-// ---- device math --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-__device__ __forceinline__ float bf2f(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
 
 // ---- granule tags -------------------------------------------------------------------------------------------------------
 // forward: a granule is four bf16 h; bit 14 of each (always 0 for |h| <= 1) carries the tag: step sequence in elements 0,1,
