@@ -4,6 +4,7 @@
 //   asr_ctc_prefix_init  : CTCPrefixScore.init_state (running blank-only path)
 //   asr_lstm_cell        : pointwise LSTM cell on pre-computed gate sums (RNN-LM step; the two projections are asr_gemm)
 //   asr_gather_rows      : row gather (embedding lookup, state re-ordering after pruning)
+//   asr_masked_copy_rows : dst[r,:] = src[r,:] where mask[r] (CTC-only search: the LM rows of the slots that were extended)
 #include "common.h"
 
 namespace {
@@ -85,6 +86,15 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, const int64_t*
     }
 }
 
+__global__ void masked_copy_rows_kernel(const float* __restrict__ src, const int* __restrict__ mask, float* __restrict__ dst,
+                                        int rows, int width, long src_ld, long dst_ld) {
+    const long total = (long)rows * width;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / width), k = (int)(i % width);
+        if (mask[r]) dst[(long)r * dst_ld + k] = src[(long)r * src_ld + k];
+    }
+}
+
 }  // namespace
 
 extern "C" int asr_ctc_prefix_init(const float* logp, float* r, int T, int V, asr_stream_t stream) {
@@ -120,6 +130,17 @@ extern "C" int asr_gather_rows(const float* src, const int64_t* idx, float* dst,
     long g = ((long)rows * width + 255) / 256; if (g > 4096) g = 4096;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, src, idx, dst, rows, width, src_ld, dst_ld, nsrc);
     ASR_LAUNCH_CHECK("asr_gather_rows");
+    return ASR_OK;
+}
+
+extern "C" int asr_masked_copy_rows(const float* src, const int* mask, float* dst, int rows, int width, long src_ld, long dst_ld,
+                                    asr_stream_t stream) {
+    ASR_REQUIRE(src && mask && dst, ASR_E_ARG, "asr_masked_copy_rows: null pointer");
+    ASR_REQUIRE(rows > 0 && width > 0 && src_ld >= width && dst_ld >= width, ASR_E_ARG,
+                "asr_masked_copy_rows: bad dims rows=%d width=%d src_ld=%ld dst_ld=%ld", rows, width, src_ld, dst_ld);
+    long g = ((long)rows * width + 255) / 256; if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(masked_copy_rows_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, src, mask, dst, rows, width, src_ld, dst_ld);
+    ASR_LAUNCH_CHECK("asr_masked_copy_rows");
     return ASR_OK;
 }
 

@@ -6,8 +6,9 @@ for all U x beam rows; nothing is copied to the host until the search has ended.
 implementation (score table on the host each step), kept as a cross-check for the shipped decoder.  Models the decode
 kernels do not cover (GRU, dot / multi-head attention, v_proj, deep LSTM) take the step of src/decode_variants.py; both
 searches share the bookkeeping of _BeamBook.  A CTC-only model (ctc_weight = 1: no attention decoder) is decoded by a CTC
-prefix beam search instead, the whole search of all utterances in ONE launch (asr_ctc_beam_search, csrc/ctc_decode.hip); the
-reference has no counterpart (`# ToDo : implement pure ctc decode`)."""
+prefix beam search instead, the whole search of all utterances in ONE launch (asr_ctc_beam_search, csrc/ctc_decode.hip); with
+an RNN-LM (shallow fusion) by the resumable form of that search, which stops whenever a new prefix needs an LM step
+(asr_ctc_beam_lm_advance).  The reference has no counterpart (`# ToDo : implement pure ctc decode`)."""
 import ctypes
 import math
 
@@ -98,6 +99,18 @@ def encoder_pass_msg(asr, batch_encode):
     return '           |Encoder pass: batched, length-aware (one pass per layer over the padded batch)'
 
 
+def _masked_rows(dst, src, mask):
+    """dst[.., r, :] = src[.., r, :] where mask[r], in place: one asr_masked_copy_rows per (n, width) matrix of an LM table or
+    state (a tensor (n, V) / (layers, n, dim), or a tuple of such)."""
+    if isinstance(dst, (tuple, list)):
+        for d, s_ in zip(dst, src):
+            _masked_rows(d, s_, mask)
+        return
+    n, w = dst.shape[-2], dst.shape[-1]
+    for d, s_ in zip(dst.reshape(-1, n, w), src.reshape(-1, n, w)):
+        H.call('asr_masked_copy_rows', H.ptr(s_), H.ptr(mask), H.ptr(d), n, w, w, w, H.stream_ptr())
+
+
 class Hypothesis(object):
     """History of one partial transcript (reference src/decode.py:186-281); `row` = its row in the device state."""
 
@@ -136,11 +149,13 @@ class Hypothesis(object):
 
 class CTCHypothesis(object):
     """One result of the CTC prefix beam search: the collapsed token sequence (a trailing <eos> included when the model
-    emits one) and its log-probability.  CTC gives a sequence no per-token scores, so avgScore() IS the sequence
-    log-probability (not divided by the length) - the quantity the search ranks by."""
+    emits one) and its score.  CTC gives a sequence no per-token scores, so avgScore() IS the sequence score (not divided by
+    the length) - the quantity the search ranks by: the sequence's CTC log-probability `ctc_score`, plus with an LM
+    lm_weight * its LM log-probability + len_bonus * its length."""
 
-    def __init__(self, output_seq, score):
+    def __init__(self, output_seq, score, ctc_score=None):
         self.output_seq, self.score = output_seq, score
+        self.ctc_score = score if ctc_score is None else ctc_score
 
     def avgScore(self):
         return self.score
@@ -152,7 +167,7 @@ class CTCHypothesis(object):
 
 class BeamDecoder(nn.Module):
     def __init__(self, asr, emb_decoder, beam_size, min_len_ratio, max_len_ratio, lm_path='', lm_config='', lm_weight=0.0,
-                 ctc_weight=0.0, batch_encode=False):
+                 ctc_weight=0.0, batch_encode=False, len_bonus=0.0):
         super().__init__()
         assert emb_decoder is None, 'embedding-fusion decoding is outside the HIP path'
         self.batch_encode = bool(batch_encode)      # opt-in: the batched pass agrees with the per-utterance one to rounding only
@@ -162,12 +177,16 @@ class BeamDecoder(nn.Module):
             # no attention decoder to search with: CTC prefix beam search.  Nothing to mix the CTC score with (ctc_weight is
             # ignored), and the frames bound the length (the length ratios are ignored)
             assert self.asr.ctc_weight > 0, 'ASR was not trained with CTC decoder'
-            if lm_weight > 0:
-                raise NotImplementedError('RNN-LM fusion for CTC-only decoding is not built')
+            if lm_weight > 0 and not lm_config:
+                raise NotImplementedError('RNN-LM fusion for CTC-only decoding is not built into a decoder that names no LM: '
+                                          'give lm_config (and lm_path), or construct with lm_weight = 0 and call set_lm(lm, weight)')
             if not 1 <= beam_size <= H.CTC_BEAM_MAX:
                 raise ValueError('CTC-only decoding takes a beam of 1..%d, got %d' % (H.CTC_BEAM_MAX, beam_size))
             self.fast, self.apply_ctc, self.apply_lm = False, True, False
             self.ctc_cand = min(self.asr.vocab_size - 1, int(CTC_BEAM_RATIO * self.beam_size))
+            self.len_bonus = float(len_bonus)         # per-token insertion bonus of the fused score; the CTC-only search alone uses it
+            if lm_weight > 0:
+                self.set_lm(self._load_lm(lm_config, lm_path), lm_weight)
             return
         # the decode kernels of the shipped decoder (asr_att_decoder_step) cover an LSTM of <= MAX_DEC_LAYERS layers with
         # location-aware single-head attention and no value projection, whatever its dropout (inactive in eval); every other
@@ -182,22 +201,30 @@ class BeamDecoder(nn.Module):
         if self.apply_lm:
             self.lm_w = lm_weight
             if lm_config:
-                cfg = yaml.load(open(lm_config, 'r'), Loader=yaml.FullLoader)
-                self.lm = RNNLM(self.asr.vocab_size, **cfg['model'])
-                if lm_path:
-                    self.lm.load_state_dict(torch.load(lm_path, map_location='cpu')['model'])
+                self.lm = self._load_lm(lm_config, lm_path)
+
+    def _load_lm(self, lm_config, lm_path):
+        cfg = yaml.load(open(lm_config, 'r'), Loader=yaml.FullLoader)
+        lm = RNNLM(self.asr.vocab_size, **cfg['model'])
+        if lm_path:
+            lm.load_state_dict(torch.load(lm_path, map_location='cpu')['model'])
+        return lm
 
     def set_lm(self, lm, weight):
-        if self.ctc_only:
-            raise NotImplementedError('RNN-LM fusion for CTC-only decoding is not built')
+        """Fuse `lm` with `weight`.  A CTC-only model takes anything with RNNLM's decoding interface: init_state(n, device),
+        step(tokens, state) -> (log-probs (n,V), state) and gather_state(state, index), the state one fp32 (layers, n, dim)
+        tensor or a tuple of them."""
         self.apply_lm, self.lm_w, self.lm = True, weight, lm
 
     def create_msg(self):
         if self.ctc_only:
-            return ['Decode spec| CTC-only model: CTC prefix beam search\t| Beam size = {}\t| Tokens extended per frame = {}'.format(
-                        self.beam_size, self.ctc_cand),
-                    '           |Min/Max len ratio, ctc_weight are ignored (the frames bound the length; nothing to mix with)',
-                    encoder_pass_msg(self.asr, self.batch_encode)]
+            msg = ['Decode spec| CTC-only model: CTC prefix beam search\t| Beam size = {}\t| Tokens extended per frame = {}'.format(
+                       self.beam_size, self.ctc_cand),
+                   '           |Min/Max len ratio, ctc_weight are ignored (the frames bound the length; nothing to mix with)']
+            if self.apply_lm:
+                msg.append('           |LM shallow fusion enabled \t| weight = {:.2f}\t| length bonus = {:.2f}'.format(self.lm_w, self.len_bonus))
+            msg.append(encoder_pass_msg(self.asr, self.batch_encode))
+            return msg
         msg = ['Decode spec| Beam size = {}\t| Min/Max len ratio = {}/{}'.format(self.beam_size, self.min_len_ratio, self.max_len_ratio)]
         if self.apply_ctc:
             msg.append('           |Joint CTC decoding enabled \t| weight = {:.2f}\t'.format(self.ctc_w))
@@ -239,6 +266,8 @@ class BeamDecoder(nn.Module):
         """CTC-only model: one asr_ctc_beam_search launch runs every frame of every utterance; the results are read back
         once, after it.  Returns CTCHypothesis objects in the shape of forward's contract."""
         _, _, tlen, ctc_lp = self._encode(audio_feature, feature_len)
+        if self.apply_lm:
+            return self._forward_ctc_lm(ctc_lp, tlen)
         U, Tp, V = ctc_lp.shape
         K, dev = self.beam_size, ctc_lp.device
         toks = torch.empty((U, K, Tp), dtype=torch.int32, device=dev)
@@ -250,6 +279,50 @@ class BeamDecoder(nn.Module):
                H.ptr(n), H.ptr(ws), nbytes, H.stream_ptr())
         n_c, len_c, tok_c, sc_c = n.cpu(), lens.cpu(), toks.cpu(), score.cpu()
         out = [[CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(sc_c[u, i])) for i in range(int(n_c[u]))] for u in range(U)]
+        return out[0] if U == 1 else out
+
+    def _forward_ctc_lm(self, ctc_lp, tlen, max_frames=0):
+        """CTC-only model with an LM: the resumable search.  Row u*K + r of the LM table and state belongs to beam slot r of
+        utterance u.  Every asr_ctc_beam_lm_advance launch runs frames until some slot of an utterance is a new prefix (at least
+        one frame of every unfinished utterance, so T' launches always suffice), then says per slot which row it inherits
+        (src_row), with which token the LM has to step it (step_tok) and whether it is new (need); the glue gathers, steps all
+        rows and keeps the stepped ones where need.  No device-to-host copy inside the loop except the early-stop check every
+        16 launches.  self.launches = the number of advance launches of the last call."""
+        U, Tp, V = ctc_lp.shape
+        K, dev, st = self.beam_size, ctc_lp.device, H.stream_ptr()
+        R = U * K
+        lm = self.lm
+        lm.prec = self.asr.prec
+        i32 = lambda *s_: torch.empty(s_, dtype=torch.int32, device=dev)
+        src_row, step_tok = torch.empty(R, dtype=torch.int64, device=dev), torch.empty(R, dtype=torch.int64, device=dev)
+        need, frame, done = i32(R), i32(U), i32(U)
+        nbytes = int(H.lib().asr_ctc_beam_lm_workspace_bytes(U, Tp, K))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        lm_lp, state = lm.step(torch.zeros(R, dtype=torch.int64, device=dev), lm.init_state(R, dev))         # <sos> = 0
+        lm_lp = lm_lp.contiguous()
+        H.call('asr_ctc_beam_lm_init', U, Tp, K, H.ptr(ws), nbytes, st)
+        self.launches = 0
+        for it in range(Tp):
+            H.call('asr_ctc_beam_lm_advance', H.ptr(ctc_lp), H.ptr(tlen), H.ptr(lm_lp), U, Tp, V, K, self.ctc_cand, float(self.lm_w),
+                   float(self.len_bonus), max_frames, H.ptr(src_row), H.ptr(step_tok), H.ptr(need), H.ptr(frame), H.ptr(done),
+                   H.ptr(ws), nbytes, st)
+            self.launches += 1
+            state_g = lm.gather_state(state, src_row)
+            lp_g = torch.empty_like(lm_lp)
+            H.call('asr_gather_rows', H.ptr(lm_lp), H.ptr(src_row), H.ptr(lp_g), R, V, V, V, R, st)
+            lp_n, state_n = lm.step(step_tok, state_g)
+            _masked_rows(lp_g, lp_n.contiguous(), need)
+            _masked_rows(state_g, state_n, need)
+            lm_lp, state = lp_g, state_g
+            if (it & 15) == 15 and bool(done.all()):           # every 16 launches: stop early when every search has ended
+                break
+        toks, lens, n = i32(U, K, Tp), i32(U, K), i32(U)
+        score, ctc_score = torch.empty((U, K), dtype=torch.float32, device=dev), torch.empty((U, K), dtype=torch.float32, device=dev)
+        H.call('asr_ctc_beam_lm_readout', U, Tp, K, Tp, H.ptr(toks), H.ptr(lens), H.ptr(score), H.ptr(ctc_score), H.ptr(n), H.ptr(ws),
+               nbytes, st)
+        n_c, len_c, tok_c, sc_c, cs_c = n.cpu(), lens.cpu(), toks.cpu(), score.cpu(), ctc_score.cpu()
+        out = [[CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(sc_c[u, i]), float(cs_c[u, i])) for i in range(int(n_c[u]))]
+               for u in range(U)]
         return out[0] if U == 1 else out
 
     @torch.no_grad()

@@ -109,6 +109,7 @@ SIGNATURES = {
     'asr_ctc_prefix_score': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'asr_lstm_cell': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     'asr_gather_rows': [_vp, _vp, _vp, _i, _i, _l, _l, _i, _vp],
+    'asr_masked_copy_rows': [_vp, _vp, _vp, _i, _i, _l, _l, _vp],
     'asr_masked_softmax_fwd': [_vp, _vp, _i, _i, _i, _f, _vp, _vp],
     'asr_masked_softmax_bwd': [_vp, _vp, _i, _i, _f, _vp, _vp],
     'asr_loc_energy_fwd': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
@@ -138,6 +139,9 @@ SIGNATURES = {
     'asr_ctc_prefix_init_batched': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'asr_ctc_prefix_score_batched': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'asr_ctc_beam_search': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    'asr_ctc_beam_lm_init': [_i, _i, _i, _vp, _sz, _vp],
+    'asr_ctc_beam_lm_advance': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    'asr_ctc_beam_lm_readout': [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_ctc_align': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_ragged_align': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'asr_ragged_unalign': [_vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -172,6 +176,7 @@ _RESTYPES = {
     'asr_lstm16_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_ctc_loss_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_beam_search_workspace_bytes': (_sz, [_i, _i, _i]),
+    'asr_ctc_beam_lm_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_align_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_fbank_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_att_decoder_bwd_workspace_bytes': (_sz, [_P(DecDims)]),

@@ -551,6 +551,8 @@ int asr_gru_rec_bwd(const float* dy, const float* y, const float* saved, const f
  *   asr_lstm_cell        : pointwise LSTM cell on gate pre-activations (N,4D) + both biases (RNNLM step, src/lm.py:27-37;
  *                          the projections are asr_gemm);  c_prev may be NULL (zero state).
  *   asr_gather_rows      : dst[r,:] = src[idx[r],:]  (embedding lookup, state re-ordering after pruning).
+ *   asr_masked_copy_rows : dst[r,:] = src[r,:] for the rows with mask[r] != 0 (mask (rows) int32), the others untouched;
+ *                          src_ld, dst_ld >= width.  The CTC-only search keeps the new LM rows of the extended slots with it.
  */
 int asr_att_decoder_keys(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const float* enc,
                          float* key, int prec, asr_stream_t stream);
@@ -565,6 +567,8 @@ int asr_lstm_cell(const float* gates_pre, const float* bias_ih, const float* bia
                   float* h, float* c, int N, int D, asr_stream_t stream);
 int asr_gather_rows(const float* src, const int64_t* idx, float* dst, int rows, int width, long src_ld, long dst_ld,
                     int nsrc, asr_stream_t stream);
+int asr_masked_copy_rows(const float* src, const int* mask, float* dst, int rows, int width, long src_ld, long dst_ld,
+                         asr_stream_t stream);
 
 /* Device-side beam bookkeeping: one output position of BeamDecoder.forward (src/decode.py:104-177) for U utterances x
  * `beam` hypothesis rows (row = u*beam + i) with NO device-to-host copy.
@@ -614,12 +618,43 @@ int asr_ctc_prefix_score_batched(const float* logp, const int* tlen, const float
  * out_score (U,K) = log-probability of the token sequence under the pruned search (-inf in unused rows), out_n (U) = number of
  * hypotheses (tlen[u] = 0: the empty one, score 0).  Lcap >= Tmax.  workspace: asr_ctc_beam_search_workspace_bytes(U,Tmax,K)
  * (the prefix trie, 1 + K*Tmax nodes per utterance; need not be cleared).  Any V > 1, any Tmax > 0,
- * 1 <= K <= ASR_CTC_BEAM_MAX; anything else returns ASR_E_ARG and launches nothing.  No language-model fusion. */
+ * 1 <= K <= ASR_CTC_BEAM_MAX; anything else returns ASR_E_ARG and launches nothing.  No language-model fusion: that is the
+ * resumable search below. */
 #define ASR_CTC_BEAM_MAX 16
 size_t asr_ctc_beam_search_workspace_bytes(int U, int Tmax, int K);
 int asr_ctc_beam_search(const float* logp, const int* tlen, int U, int Tmax, int V, int K, int cand, int Lcap,
                         int* out_tokens, int* out_len, float* out_score, int* out_n,
                         void* workspace, size_t workspace_bytes, asr_stream_t stream);
+
+/* The same search with RNN-LM shallow fusion, resumable (csrc/ctc_decode.hip; the frame body is the one of asr_ctc_beam_search).
+ * A prefix l_1..l_n is ranked, at every frame and in the result, by
+ *   log P_ctc(l | frames so far) + lm_weight * sum_j log P_lm(l_j | <sos>, l_1..l_{j-1}) + len_bonus * n
+ * where log P_ctc = logaddexp(p_blank, p_nonblank) stays pure CTC and the LM part is one additive value per beam entry: a stay
+ * inherits it, the extension of slot i by c gets lms_i + lm_weight * lm_logp[row_i, c] + len_bonus, an extension that is a beam
+ * member keeps the member's value.  The allowed tokens stay the `cand` largest CTC log-probs of the frame; ties, the never-keep
+ * -inf rule and the slot order are those of asr_ctc_beam_search; with lm_weight = len_bonus = 0 and a finite table the result
+ * equals it bit for bit.  A new prefix needs an LM step (GEMMs) before it can be extended, so the beam and the trie live in the
+ * workspace between launches (asr_ctc_beam_lm_workspace_bytes; need not be cleared, _init fills what is read):
+ *   _init    : every utterance at the empty prefix, score 0.
+ *   _advance : per utterance, loads the beam and runs frames until the first frame whose survivors include an extension
+ *              (c != 0: some slot needs a new LM row), the utterance's last frame, or max_frames frames (max_frames > 0); at
+ *              least one frame of every unfinished utterance.  lm_logp (U*K,V): row u*K + r = the LM's log-probs after the
+ *              prefix of slot r.  Writes per slot src_row (U*K) int64 = the global row the slot inherits its LM state and
+ *              distribution from (stays permute the slots by rank; identity for dead slots and finished utterances), step_tok
+ *              (U*K) int64 = the slot's last token, need (U*K) int32 = 1 where the slot is an extension: the caller gathers
+ *              state and table rows by src_row, steps the LM with step_tok and keeps the stepped rows where need.  Per
+ *              utterance frame (U) = frames consumed so far, done (U) = 1 once all tlen[u] frames are.  A finished utterance
+ *              is a no-op.
+ *   _readout : out_tokens / out_len / out_n as asr_ctc_beam_search (same layout and padding), out_score (U,K) the fused score,
+ *              out_ctc_score (U,K) its CTC part; -inf in unused rows.  May be called after any launch.
+ * Null pointers, bad dims, K outside 1..ASR_CTC_BEAM_MAX and a short workspace return ASR_E_ARG and launch nothing. */
+size_t asr_ctc_beam_lm_workspace_bytes(int U, int Tmax, int K);
+int asr_ctc_beam_lm_init(int U, int Tmax, int K, void* workspace, size_t workspace_bytes, asr_stream_t stream);
+int asr_ctc_beam_lm_advance(const float* logp, const int* tlen, const float* lm_logp, int U, int Tmax, int V, int K, int cand,
+                            float lm_weight, float len_bonus, int max_frames, int64_t* src_row, int64_t* step_tok, int* need,
+                            int* frame, int* done, void* workspace, size_t workspace_bytes, asr_stream_t stream);
+int asr_ctc_beam_lm_readout(int U, int Tmax, int K, int Lcap, int* out_tokens, int* out_len, float* out_score,
+                            float* out_ctc_score, int* out_n, const void* workspace, size_t workspace_bytes, asr_stream_t stream);
 
 /* CTC forced alignment (csrc/ctc_align.hip): the most probable alignment (Viterbi) of a KNOWN transcript to the CTC
  * log-probabilities - token and word timestamps, cutting long recordings, finding bad transcripts by their score.  No reference

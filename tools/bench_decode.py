@@ -3,11 +3,15 @@ RNN-LM of config/librispeech_lm.yaml (4 x LSTM-1024, tied, random weights) with 
 U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Prints one JSON line.
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
        [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
-       [--ctc-only] [--batch-encode] [--lengths equal|librispeech] [--vgg N]
+       [--ctc-only] [--ctc-lm] [--batch-encode] [--lengths equal|librispeech] [--vgg N]
 The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one; --lm-module GRU
 fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one.  --ctc-only decodes the config's
 model built with ctc_weight = 1 (no attention decoder, no LM) by the CTC prefix beam search (csrc/ctc_decode.hip) and also
-times the search launch alone on the encoded batch.  --batch-encode measures, in the same process, the encoder pass alone and
+times the search launch alone on the encoded batch.  --ctc-only --ctc-lm fuses the RNN-LM into that search (shallow fusion, the
+resumable search asr_ctc_beam_lm_advance) and measures, in one process and alternating, one warm-up each, then the median of
+--reps runs: the whole decode without and with the LM, the search loop alone on the encoded batch (every launch of the LM and
+of the search between init and read-out), and the advance launches per batch when a launch runs ahead until a slot needs a new
+LM row against one frame per launch (max_frames = 1).  --batch-encode measures, in the same process, the encoder pass alone and
 the whole decode with the per-utterance encoder pass (the default) and with the length-aware batched one
 (BeamDecoder(batch_encode=True), src/ragged.py): one warm-up each, then the median of --reps runs.  --lengths librispeech
 draws the U lengths from SURVEY 8d's length model clip(N(1270,480),150,2450) instead of --frames for every utterance.  --vgg N
@@ -29,7 +33,7 @@ ap.add_argument('--beam', type=int, default=8); ap.add_argument('--host', action
 ap.add_argument('--model-yaml', default=os.path.join(PKG, 'config', 'librispeech_asr.yaml'))
 ap.add_argument('--attention-mode'); ap.add_argument('--num-head', type=int); ap.add_argument('--decoder-module')
 ap.add_argument('--lm-module', choices=('LSTM', 'GRU'), default='LSTM')
-ap.add_argument('--ctc-only', action='store_true')
+ap.add_argument('--ctc-only', action='store_true'); ap.add_argument('--ctc-lm', action='store_true')
 ap.add_argument('--batch-encode', action='store_true'); ap.add_argument('--lengths', choices=('equal', 'librispeech'), default='equal')
 ap.add_argument('--vgg', type=int, choices=range(8))
 a = ap.parse_args()
@@ -57,6 +61,31 @@ if a.lengths == 'librispeech':
     for u in range(U):
         feat[u, int(ln[u]):] = 0
 steps = int(-(-T * a.max_len_ratio // 1))
+if a.ctc_lm:
+    import statistics
+    assert a.ctc_only, '--ctc-lm measures the CTC-only search: give --ctc-only too'
+    dec_lm = BeamDecoder(model, None, beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio)
+    dec_lm.set_lm(lm, 0.3)
+    _, _, tlen, lp = dec._encode(feat, flen)
+    runs = {'no_lm': lambda: dec(feat, flen), 'lm': lambda: dec_lm(feat, flen), 'search_loop': lambda: dec_lm._forward_ctc_lm(lp, tlen),
+            'search_loop_one_frame': lambda: dec_lm._forward_ctc_lm(lp, tlen, max_frames=1)}
+    ts, launches = {k: [] for k in runs}, {}
+    for rep in range(1 + a.reps):                      # rep 0 = warm-up: workspaces, packed weights, plans
+        for name, fn in runs.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter(); out = fn(); torch.cuda.synchronize()
+            if rep: ts[name].append((time.perf_counter() - t0) * 1e3)
+            if name.startswith('search_loop'): launches[name] = dec_lm.launches
+    H.raise_if_aborted()
+    med = {k: statistics.median(v) for k, v in ts.items()}
+    print(json.dumps({'metric': 'CTC prefix beam search with RNN-LM shallow fusion, CTC-only model of config 4', 'batch_utterances': U, 'frames': T,
+                      'encoder_frames': int(lp.shape[1]), 'beam': a.beam, 'tokens_extended_per_frame': dec.ctc_cand, 'prec': a.prec,
+                      'lm': '4x1024 tied, %s' % a.lm_module, 'lm_weight': 0.3, 'reps': a.reps, 'weights': 'random',
+                      'decode_ms_no_lm': med['no_lm'], 'decode_ms_lm': med['lm'], 'utterances_per_s_no_lm': U * 1e3 / med['no_lm'],
+                      'utterances_per_s_lm': U * 1e3 / med['lm'], 'search_loop_ms': med['search_loop'],
+                      'search_loop_ms_one_frame_per_launch': med['search_loop_one_frame'], 'advance_launches': launches['search_loop'],
+                      'advance_launches_one_frame_per_launch': launches['search_loop_one_frame'],
+                      'search_loop_ms_per_advance': med['search_loop'] / launches['search_loop']}))
+    sys.exit(0)
 if a.batch_encode:
     import statistics
     dec_b = BeamDecoder(model, None, beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio, ctc_weight=0.3, batch_encode=True)
