@@ -11,6 +11,7 @@
 // Step kernels are bandwidth/latency bound: key (B,T',A) and enc (B,T',E) are re-read every step and
 // stay resident in the 256 MB Infinity Cache between steps; one launch covers the whole batch.
 #include "common.h"
+#include "gemm_plan.h"
 #include "decoder_internal.h"
 #include <stdlib.h>
 
@@ -1263,8 +1264,9 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
     if (state->work && state->work_bytes >= 256) hipMemsetAsync(state->work, 0, 256, st);
 
     // key = tanh(enc W_k^T + b_k), once per batch (src/asr.py:345)
-    rc = asr_gemm(enc, weights->Wk, state->key, weights->bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A, 1, 1, ASR_ACT_TANH, 0, 1,
-                  1, 0, 0, 0, 0, 0, prec, stream);
+    GemmCall key{enc, weights->Wk, state->key, weights->bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A};
+    key.act = ASR_ACT_TANH; key.prec = prec;
+    rc = gemm_run(key, st);
     if (rc != ASR_OK) return rc;
     // bf16 working copies of the two tensors every step re-reads (bf16 contraction mode only; the caller provides the
     // buffers): they halve the loop's HBM traffic and bring its per-XCD working set under the 4 MB L2
@@ -1306,8 +1308,10 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
     ASR_LAUNCH_CHECK("asr_att_decoder_fwd");
     if (teacher) {
         // logits[b,t,:] = W_c h_top[b,t] + b_c for all steps in one contraction
-        rc = asr_gemm(state->hs + (size_t)(d.NL - 1) * d.Dd, weights->Wc, state->logits, weights->bc, d.B * d.L, d.V, d.Dd,
-                      (long)d.NL * d.Dd, d.Dd, d.V, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0, 0, 0, prec, stream);
+        GemmCall logits{state->hs + (size_t)(d.NL - 1) * d.Dd, weights->Wc, state->logits, weights->bc, d.B * d.L, d.V, d.Dd,
+                        (long)d.NL * d.Dd, d.Dd, d.V};
+        logits.prec = prec;
+        rc = gemm_run(logits, st);
         if (rc != ASR_OK) return rc;
     }
     return ASR_OK;
@@ -1321,8 +1325,9 @@ extern "C" int asr_att_decoder_keys(const asr_dec_dims_t* dims, const asr_dec_we
                                     float* key, int prec, asr_stream_t stream) {
     ASR_REQUIRE(dims && weights && enc && key, ASR_E_ARG, "asr_att_decoder_keys: null pointer");
     const asr_dec_dims_t& d = *dims;
-    return asr_gemm(enc, weights->Wk, key, weights->bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A, 1, 1, ASR_ACT_TANH, 0, 1, 1, 0, 0, 0, 0, 0,
-                    prec, stream);
+    GemmCall c{enc, weights->Wk, key, weights->bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A};
+    c.act = ASR_ACT_TANH; c.prec = prec;
+    return gemm_run(c, (hipStream_t)stream);
 }
 
 extern "C" int asr_att_decoder_step(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights,
@@ -1434,8 +1439,9 @@ extern "C" int asr_att_decoder_bwd_ex(const asr_dec_dims_t* dims, const asr_dec_
     hipLaunchKernelGGL(transpose_kernel, dim3(256), dim3(256), 0, st, weights->Wq, p.wqT, d.A, d.Q, (long)d.A, 0L);
 
     // output layer: dh_top = dlogits W_c ; dW_c += dlogits^T h_top ; db_c += colsum(dlogits)
-    rc = asr_gemm(dlogits, weights->Wc, p.dhs + (size_t)(d.NL - 1) * d.Dd, nullptr, BL, d.Dd, d.V, d.V, d.Dd, SW, 1, 0,
-                  ASR_ACT_NONE, 0, 1, 1, 0, 0, 0, 0, 0, prec, stream);
+    GemmCall dh_top{dlogits, weights->Wc, p.dhs + (size_t)(d.NL - 1) * d.Dd, nullptr, BL, d.Dd, d.V, d.V, d.Dd, SW};
+    dh_top.b_kc = 0; dh_top.prec = prec;
+    rc = gemm_run(dh_top, st);
     if (rc != ASR_OK) return rc;
 
     const int taps = 2 * d.Ks + 1;
@@ -1505,13 +1511,17 @@ extern "C" int asr_att_decoder_bwd_ex(const asr_dec_dims_t* dims, const asr_dec_
 
     // ---- the rest of the critical path: gradient wrt the encoder output ----------------------------------------
     // context: denc[b] += attn[b]^T (T' x L) dctx[b] (L x E)
-    rc = asr_gemm(state->att, p.dxin + d.Dd, denc, nullptr, d.Tp, d.E, d.L, d.Tp, XW, d.E, 0, 0, ASR_ACT_NONE, 1, 1, d.B,
-                  (long)d.L * d.Tp, (long)d.L * XW, (long)d.Tp * d.E, 0, 0, prec, stream);
+    GemmCall dctx = gemm_wgrad_call(state->att, p.dxin + d.Dd, denc, d.Tp, d.E, d.L, d.Tp, XW, d.E, 1);
+    dctx.batch = d.B; dctx.sA = (long)d.L * d.Tp; dctx.sB = (long)d.L * XW; dctx.sC = (long)d.Tp * d.E;
+    dctx.prec = prec;
+    rc = gemm_run(dctx, st);
     if (rc != ASR_OK) return rc;
     // key projection backward
     rc = asr_act_bwd(p.dkey, state->key, dkeypre, (long)d.B * d.Tp * d.A, ASR_ACT_TANH, stream);
     if (rc != ASR_OK) return rc;
-    rc = asr_gemm(dkeypre, weights->Wk, denc, nullptr, d.B * d.Tp, d.E, d.A, d.A, d.E, d.E, 1, 0, ASR_ACT_NONE, 1, 1, 1, 0, 0, 0, 0, 0, prec, stream);
+    GemmCall dkey{dkeypre, weights->Wk, denc, nullptr, d.B * d.Tp, d.E, d.A, d.A, d.E, d.E};
+    dkey.b_kc = 0; dkey.accum = 1; dkey.prec = prec;
+    rc = gemm_run(dkey, st);
     if (rc != ASR_OK) return rc;
     ASR_LAUNCH_CHECK("asr_att_decoder_bwd(tail)");
     if (looped_out) *looped_out = looped ? 1 : 0;
@@ -1554,8 +1564,9 @@ extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_
     const float* pdg = looped ? dec_bwd_dgates(d, ws + lay.pwork) : nullptr;
     const int nslots_used = d.B * (looped ? lay.ntp : lay.nte);
     // output layer: dW_c += dlogits^T h_top ; db_c += colsum(dlogits)
-    rc = asr_gemm(dlogits, state->hs + (size_t)(d.NL - 1) * d.Dd, grads->Wc, nullptr, d.V, d.Dd, BL, d.V, SW, d.Dd, 0, 0,
-                  ASR_ACT_NONE, 1, wgrad_slices(d.V, d.Dd, BL), 1, 0, 0, 0, 0, 0, prec, stream);
+    GemmCall gWc = gemm_wgrad_call(dlogits, state->hs + (size_t)(d.NL - 1) * d.Dd, grads->Wc, d.V, d.Dd, BL, d.V, SW, d.Dd, wgrad_slices(d.V, d.Dd, BL));
+    gWc.prec = prec;
+    rc = gemm_run(gWc, st);
     if (rc != ASR_OK) return rc;
     rc = asr_colsum(dlogits, d.V, BL, d.V, grads->bc, stream);
     if (rc != ASR_OK) return rc;
@@ -1566,26 +1577,31 @@ extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_
         const int Kx = (l == 0) ? XW : d.Dd;
         const float* xl = (l == 0) ? state->xin : state->hs + (size_t)(l - 1) * d.Dd;
         const long ldx = (l == 0) ? XW : SW;
-        rc = asr_gemm(dg, xl, grads->Wih[l], nullptr, 4 * d.Dd, Kx, BL, ldg, ldx, Kx, 0, 0, ASR_ACT_NONE, 1, wgrad_slices(4 * d.Dd, Kx, BL), 1, 0, 0, 0, 0,
-                      0, prec, stream);
+        GemmCall gWih = gemm_wgrad_call(dg, xl, grads->Wih[l], 4 * d.Dd, Kx, BL, ldg, ldx, Kx, wgrad_slices(4 * d.Dd, Kx, BL));
+        gWih.prec = prec;
+        rc = gemm_run(gWih, st);
         if (rc != ASR_OK) return rc;
-        rc = asr_gemm(dg, state->hs + (size_t)l * d.Dd, grads->Whh[l], nullptr, 4 * d.Dd, d.Dd, BL, ldg, SW, d.Dd, 0, 0, ASR_ACT_NONE,
-                      1, wgrad_slices(4 * d.Dd, d.Dd, BL), 1, 0, 0, 0, d.L, -1, prec, stream);
+        // against h_{t-1}: row (b,t) of hs is read at (b, t - 1), zero at t = 0
+        GemmCall gWhh = gemm_wgrad_call(dg, state->hs + (size_t)l * d.Dd, grads->Whh[l], 4 * d.Dd, d.Dd, BL, ldg, SW, d.Dd, wgrad_slices(4 * d.Dd, d.Dd, BL));
+        gWhh.seqT = d.L; gWhh.bshift = -1; gWhh.prec = prec;
+        rc = gemm_run(gWhh, st);
         if (rc != ASR_OK) return rc;
         rc = asr_colsum2(dg, ldg, BL, 4 * d.Dd, grads->bih[l], grads->bhh[l], stream);
         if (rc != ASR_OK) return rc;
     }
     // query projection: dW_q += dqpre^T hcat_{t-1}, db_q += colsum(dqpre)
-    rc = asr_gemm(p.dq, state->hs, grads->Wq, nullptr, d.A, d.Q, BL, d.A, d.Q, d.Q, 0, 0, ASR_ACT_NONE, 1, wgrad_slices(d.A, d.Q, BL), 1, 0, 0, 0, d.L, -1,
-                  prec, stream);
+    GemmCall gWq = gemm_wgrad_call(p.dq, state->hs, grads->Wq, d.A, d.Q, BL, d.A, d.Q, d.Q, wgrad_slices(d.A, d.Q, BL));
+    gWq.seqT = d.L; gWq.bshift = -1; gWq.prec = prec;
+    rc = gemm_run(gWq, st);
     if (rc != ASR_OK) return rc;
     rc = asr_colsum(p.dq, d.A, BL, d.A, grads->bq, stream);
     if (rc != ASR_OK) return rc;
     // embedding.  After the persistent backward the embedding part of dxin is still to be formed:
     // dgates (B*L x 4Dd) . W_ih[:, :Dd]
     if (looped) {
-        rc = asr_gemm(pdg, weights->Wih[0], p.dxin, nullptr, BL, d.Dd, 4 * d.Dd, 4 * d.Dd, XW, XW, 1, 0, ASR_ACT_NONE, 0, 1, 1,
-                      0, 0, 0, 0, 0, prec, stream);
+        GemmCall demb{pdg, weights->Wih[0], p.dxin, nullptr, BL, d.Dd, 4 * d.Dd, 4 * d.Dd, XW, XW};
+        demb.b_kc = 0; demb.prec = prec;
+        rc = gemm_run(demb, st);
         if (rc != ASR_OK) return rc;
     }
     hipLaunchKernelGGL(embed_bwd_kernel, dim3(d.V, cdiv(d.Dd, 64)), dim3(256), (size_t)4 * std::min(cdiv(BL, 4), EMB_LIST_MAX) * sizeof(int), st,
@@ -1593,7 +1609,9 @@ extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_
     // key projection
     const int M = d.B * d.Tp;
     const int splits = wgrad_slices(d.A, d.E, M);
-    rc = asr_gemm(dkeypre, enc, grads->Wk, nullptr, d.A, d.E, M, d.A, d.E, d.E, 0, 0, ASR_ACT_NONE, 1, splits, 1, 0, 0, 0, 0, 0, prec, stream);
+    GemmCall gWk = gemm_wgrad_call(dkeypre, enc, grads->Wk, d.A, d.E, M, d.A, d.E, d.E, splits);
+    gWk.prec = prec;
+    rc = gemm_run(gWk, st);
     if (rc != ASR_OK) return rc;
     rc = asr_colsum(dkeypre, d.A, M, d.A, grads->bk, stream);
     if (rc != ASR_OK) return rc;

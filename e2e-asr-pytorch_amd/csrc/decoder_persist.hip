@@ -19,6 +19,7 @@
 // synchronise among themselves through an LDS counter where the polling waves are busy; s_barrier is used where
 // the polled data is handed over.
 #include "decoder_plan.h"
+#include "gemm_plan.h"
 #include "decoder_fwd_common.h"
 
 static int g_persist_fwd = -1, g_persist_bwd = -1;   // -1: from env ASR_DEC_PERSIST / ASR_DEC_PERSIST_BWD (default on)
@@ -358,8 +359,9 @@ int dec_fwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, cons
     clear_work(work, wk.xbuf_bytes, st);
     hipLaunchKernelGGL(build_wcat16_kernel, dim3(512), dim3(256), 0, st, w.Wih[0], w.Whh[0], wk.wcat16, 4 * d.Dd, d.Dd, d.E, pl.KCP);
     const int XW = d.Dd + d.E;
-    int rc = asr_gemm(s.xin, w.Wih[0], wk.embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0,
-                      0, 0, ASR_BF16, (asr_stream_t)st);
+    GemmCall embproj{s.xin, w.Wih[0], wk.embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd};
+    embproj.prec = ASR_BF16;
+    int rc = gemm_run(embproj, st);
     if (rc != ASR_OK) return rc;
     const PD p{d, w, s, enc, enc_len, wk.wcat16, wk.embproj, wk.xbuf, wk.status, pl.NT, pl.TE, pl.UPW, pl.QPW, pl.CPW, pl.HG2, pl.QG2, pl.SG2, pl.KC,
                pl.KCP, xcd_local_allowed()};

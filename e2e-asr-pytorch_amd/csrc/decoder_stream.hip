@@ -15,6 +15,7 @@
 //     (energies -> (m, s) -> weights in LDS -> weighted sum of the streamed enc rows), so nothing scales with TEB but LDS rows.
 // Exchange records, tags, epochs, XCD-local consensus, poll / compute wave roles: decoder_cluster.h, as in decoder_persist.hip.
 #include "decoder_fwd_common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -1043,8 +1044,9 @@ int dec_fwd_streamed(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const 
     hipLaunchKernelGGL(build_wcat16_kernel, dim3(512), dim3(256), 0, st, w.Wih[0], w.Whh[0], wk.wcat16, 4 * d.Dd, d.Dd, d.E, pl.KCP);
     hipLaunchKernelGGL(build_key16p_kernel, dim3(1024), dim3(256), 0, st, s.key, wk.key16t, d.B, d.Tp, d.A, pl.NT, pl.TE);
     const int XW = d.Dd + d.E;
-    int rc = asr_gemm(s.xin, w.Wih[0], wk.embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0,
-                      0, 0, ASR_BF16, (asr_stream_t)st);
+    GemmCall embproj{s.xin, w.Wih[0], wk.embproj, nullptr, d.B * d.L, 4 * d.Dd, d.Dd, XW, XW, 4 * d.Dd};
+    embproj.prec = ASR_BF16;
+    int rc = gemm_run(embproj, st);
     if (rc != ASR_OK) return rc;
     const PSF p{d, w, s, enc, enc_len, wk.wcat16, wk.embproj, wk.key16t, wk.xbuf, wk.status, pl.NT, pl.TE, pl.UPW, pl.QPW, pl.CPW, pl.HG2, pl.QG2,
                 pl.SG2, pl.KC, pl.KCP, xcd_local_allowed()};

@@ -9,6 +9,7 @@
 //   asr_specaug     : Augment (src/audio.py:364-406): one time mask and one frequency mask per utterance,
 //                     filled with the mean (recomputed after the time mask), in place on the padded batch.
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -251,11 +252,14 @@ extern "C" int asr_fbank(const float* wav, const int64_t* wav_len, float* out, c
     float* mag = spec + rows * 2 * nb;
     hipLaunchKernelGGL(frame_kernel, dim3(grid_for(rows * win)), dim3(256), 0, st, wav, wav_len, frames, window, B, N, T, win, hop, n_fft, preemph);
     // spec (rows, 2*nb) = frames (rows, win) x table^T, table (2*nb, win): exact fp32 MFMA
-    int rc = asr_gemm(frames, dft_table, spec, nullptr, (int)rows, 2 * nb, win, win, win, 2 * nb, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0, 0, 0,
-                      ASR_F32, stream);
+    GemmCall dft{frames, dft_table, spec, nullptr, (int)rows, 2 * nb, win, win, win, 2 * nb};
+    dft.prec = ASR_F32;
+    int rc = gemm_run(dft, st);
     if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL(magnitude_kernel, dim3(grid_for(rows * nb)), dim3(256), 0, st, spec, mag, rows, nb);
-    rc = asr_gemm(mag, mel_fb, out, nullptr, (int)rows, nmel, nb, nb, nb, nmel, 1, 1, ASR_ACT_NONE, 0, 1, 1, 0, 0, 0, 0, 0, ASR_F32, stream);
+    GemmCall mel{mag, mel_fb, out, nullptr, (int)rows, nmel, nb, nb, nb, nmel};
+    mel.prec = ASR_F32;
+    rc = gemm_run(mel, st);
     if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL(logmel_kernel, dim3(grid_for(rows * nmel)), dim3(256), 0, st, out, wav_len, rows, T, nmel, hop, ref_db, min_db);
     ASR_LAUNCH_CHECK("asr_fbank");

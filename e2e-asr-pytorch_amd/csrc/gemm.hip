@@ -8,35 +8,13 @@
 // Operands live in HBM as fp32; PREC selects the MFMA: bf16 inputs (converted while staging into LDS,
 // f32 accumulate) or exact f32-input MFMA (parity mode).
 // Tile: 128x128x32 per 256-thread workgroup, 4 waves as 2x2, each wave 4x4 tiles of 16x16.
-#include "common.h"
+#include "gemm_plan.h"
 #include <stdlib.h>
 
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int NT = 256;
-
-struct GemmP {
-    const float* A; const float* B; float* C; const float* bias;
-    int M, N, K;
-    long lda, ldb, ldc;
-    long sA, sB, sC;
-    int batch, splits;
-    int act, accum;
-    int seqT, bshift;
-    int vecA, vecB;
-    // implicit 3x3 convolution over a channel-last image (rows = (b,t,f), cT x cF pixels, cC channels):
-    // the conv operand's reduction/column index k = tap*cC + ci addresses pixel (t+dt, f+df), zero outside.
-    int convA, convB, cT, cF, cC;
-    // XCD-aware tile order (see gemm_kernel): column tiles, row tiles, z slices, rows per XCD band, column group width
-    int nx, ny, nz, rpb, gx, ngx, plain_order;
-    int fastA, fastB;      // operand qualifies for fetch_tile_fast
-    // bf16-storage variant (IO16 kernels): A and B are bf16 in HBM (element strides as above), C is bf16 (c16 = 1) or fp32;
-    // permH > 0: output row i of a (ND*4H)-row weight gradient computed in gate-minor order [unit][gate] is stored at the
-    // reference's row (i / 4H)*4H + (i & 3)*H + (i % 4H >> 2);  bpadT = 1: the shifted B operand lives in a time-padded
-    // buffer (B,seqT+2,.) - reduction row r = (b,t) is read at padded row b*(seqT+2) + t + 1 + bshift, always valid
-    int c16, permH, bpadT;
-};
 
 // source row offset and validity of tap (dt,df) for pixel row m
 __device__ __forceinline__ bool conv_tap(int m, int tap, int cT, int cF, long& src_row) {
@@ -420,9 +398,32 @@ int gemm_plain_order_forced() {
     if (plain < 0) { const char* e = getenv("ASR_GEMM_PLAIN_ORDER"); plain = (e && e[0] == '1') ? 1 : 0; }
     return plain;
 }
-// Host plan of a launch: tile counts, XCD band geometry, loader qualification, tile order and the number of workgroups.
-// Pure arithmetic on the arguments (no device call): launch_gemm and the plan queries all take it from here.
-int gemm_plan(GemmP& p, int a_kc, int b_kc, bool io16, long& nblk) {
+
+// The 20 instantiations, by [BF16][a_kc][b_kc][FAST][IO16]: bf16 storage exists for the bf16 MFMA and the fast loaders only
+typedef void (*GemmKernel)(GemmP);
+#define IO16_false(A, B) nullptr
+#define IO16_true(A, B) gemm_kernel<true, A, B, true, true>
+#define LOADERS(BF, A, B) {{gemm_kernel<BF, A, B, false>, nullptr}, {gemm_kernel<BF, A, B, true>, IO16_##BF(A, B)}}
+#define LAYOUTS(BF) {{LOADERS(BF, false, false), LOADERS(BF, false, true)}, {LOADERS(BF, true, false), LOADERS(BF, true, true)}}
+const GemmKernel gemm_kernels[2][2][2][2][2] = {LAYOUTS(false), LAYOUTS(true)};
+
+}  // namespace
+
+// Launch parameters of gemm_kernel for a checked call, then the plan of the launch: tile counts, XCD band geometry, loader
+// qualification, tile order and the number of workgroups.
+int gemm_plan(const GemmCall& c, bool io16, KernelPlan<GemmP>& pl) {
+    GemmP& p = pl.p;
+    p = GemmP{};
+    p.A = (const float*)c.A; p.B = (const float*)c.B; p.C = (float*)c.C; p.bias = c.bias;
+    p.M = c.M; p.N = c.N; p.K = c.K; p.lda = c.lda; p.ldb = c.ldb; p.ldc = c.ldc;
+    p.sA = c.sA; p.sB = c.sB; p.sC = c.sC; p.batch = c.batch; p.splits = c.splits;
+    p.act = c.act; p.accum = c.accum; p.seqT = c.seqT; p.bshift = c.bshift;
+    p.c16 = c.c_bf16; p.permH = c.perm_h; p.bpadT = c.b_time_padded;
+    if (c.conv_F > 0) { p.convA = c.a_kc ? 1 : 0; p.convB = 1 - p.convA; p.cT = c.conv_T; p.cF = c.conv_F; p.cC = c.conv_C; }
+    // float4 loads: 16-byte aligned rows (a convolution operand is read by pixel: only its base counts).  vecB also covers the
+    // shifted operand: its rows are read at an offset and stay 16-byte aligned because ldb % 4 == 0
+    p.vecA = (io16 || (((uintptr_t)c.A & 15) == 0 && (p.convA || ((c.lda % 4) == 0 && (c.sA % 4) == 0)))) ? 1 : 0;
+    p.vecB = (io16 || (((uintptr_t)c.B & 15) == 0 && (p.convB || ((c.ldb % 4) == 0 && (c.sB % 4) == 0)))) ? 1 : 0;
     p.nx = cdiv(p.N, BN); p.ny = cdiv(p.M, BM); p.nz = p.batch * p.splits;
     p.rpb = cdiv((long)p.ny * p.nz, 8);
     const long b_slice = (long)BN * cdiv(p.K, p.splits) * (long)(io16 ? 2 : sizeof(float));      // B operand bytes of one column tile
@@ -430,76 +431,38 @@ int gemm_plan(GemmP& p, int a_kc, int b_kc, bool io16, long& nblk) {
     p.gx = (int)(gx < 1 ? 1 : (gx > p.nx ? p.nx : gx));
     p.ngx = cdiv(p.nx, p.gx);
     // fast loader: no convolution operand, 16-byte aligned rows, contiguous extent a multiple of 4 and at least one float4
-    p.fastA = (!p.convA && p.vecA && (a_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.M % 4 == 0 && p.M >= 4))) ? 1 : 0;
-    p.fastB = (!p.convB && p.vecB && (b_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.N % 4 == 0 && p.N >= 4))) ? 1 : 0;
+    p.fastA = (!p.convA && p.vecA && (c.a_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.M % 4 == 0 && p.M >= 4))) ? 1 : 0;
+    p.fastB = (!p.convB && p.vecB && (c.b_kc ? (p.K % 4 == 0 && p.K >= 4) : (p.N % 4 == 0 && p.N >= 4))) ? 1 : 0;
     // measured (tools/bench_gemm.py): the banded order wins when a row of tiles is short (N <= 1024: projection and input-
     // gradient shapes, 1.15-1.2x) and loses for wide outputs and split reductions, which keep the natural order
     p.plain_order = (gemm_plain_order_forced() || p.nz > 1 || p.nx > 8) ? 1 : 0;
-    nblk = p.plain_order ? (long)p.nx * p.ny * p.nz : 8L * p.rpb * p.ngx * p.gx;
+    const long nblk = p.plain_order ? (long)p.nx * p.ny * p.nz : 8L * p.rpb * p.ngx * p.gx;
     ASR_REQUIRE(nblk < (1L << 31), ASR_E_UNSUPPORTED, "asr_gemm: %ld tiles", nblk);
+    pl.kernel = gemm_kernels[io16 || c.prec == ASR_BF16][c.a_kc != 0][c.b_kc != 0][io16 || (p.fastA && p.fastB)][io16];
+    pl.grid = (unsigned)nblk; pl.block = NT; pl.lds = 0;
+    pl.who = io16 ? "asr_gemm16" : "asr_gemm";
+    const int out[8] = {p.fastA, p.fastB, p.plain_order, p.nx, p.ny, p.nz, p.gx, p.ngx};
+    for (int i = 0; i < 8; ++i) pl.out[i] = out[i];
     return ASR_OK;
 }
-void gemm_plan_out(const GemmP& p, int out[8]) {
-    out[0] = p.fastA; out[1] = p.fastB; out[2] = p.plain_order; out[3] = p.nx; out[4] = p.ny; out[5] = p.nz; out[6] = p.gx; out[7] = p.ngx;
-}
+int gemm_launch(const KernelPlan<GemmP>& pl, hipStream_t st) { return launch_plan(pl, st); }
 
-template <bool BF16>
-int launch_gemm(const GemmP& p0, int a_kc, int b_kc, hipStream_t st, bool io16 = false) {
-    GemmP p = p0;
-    long nblk = 0;
-    const int prc = gemm_plan(p, a_kc, b_kc, io16, nblk);
-    if (prc != ASR_OK) return prc;
-    dim3 grid((unsigned)nblk);
-    dim3 block(NT);
-    if (io16) {
-        if (!BF16) return ASR_E_ARG;
-        if (a_kc && b_kc)        hipLaunchKernelGGL((gemm_kernel<true, true, true, true, true>), grid, block, 0, st, p);
-        else if (a_kc && !b_kc)  hipLaunchKernelGGL((gemm_kernel<true, true, false, true, true>), grid, block, 0, st, p);
-        else if (!a_kc && !b_kc) hipLaunchKernelGGL((gemm_kernel<true, false, false, true, true>), grid, block, 0, st, p);
-        else                     hipLaunchKernelGGL((gemm_kernel<true, false, true, true, true>), grid, block, 0, st, p);
-        ASR_LAUNCH_CHECK("asr_gemm16");
-        return ASR_OK;
-    }
-    if (p.fastA && p.fastB) {
-        if (a_kc && b_kc)        hipLaunchKernelGGL((gemm_kernel<BF16, true, true, true>), grid, block, 0, st, p);
-        else if (a_kc && !b_kc)  hipLaunchKernelGGL((gemm_kernel<BF16, true, false, true>), grid, block, 0, st, p);
-        else if (!a_kc && !b_kc) hipLaunchKernelGGL((gemm_kernel<BF16, false, false, true>), grid, block, 0, st, p);
-        else                     hipLaunchKernelGGL((gemm_kernel<BF16, false, true, true>), grid, block, 0, st, p);
-    } else {
-        if (a_kc && b_kc)        hipLaunchKernelGGL((gemm_kernel<BF16, true, true, false>), grid, block, 0, st, p);
-        else if (a_kc && !b_kc)  hipLaunchKernelGGL((gemm_kernel<BF16, true, false, false>), grid, block, 0, st, p);
-        else if (!a_kc && !b_kc) hipLaunchKernelGGL((gemm_kernel<BF16, false, false, false>), grid, block, 0, st, p);
-        else                     hipLaunchKernelGGL((gemm_kernel<BF16, false, true, false>), grid, block, 0, st, p);
-    }
-    ASR_LAUNCH_CHECK("asr_gemm");
-    return ASR_OK;
-}
-
-}  // namespace
-
-// Argument checks of asr_gemm and the launch parameters they give (shared by the launch and the asr_gemm_plan query).
-static int gemm_args(const float* A, const float* B, float* C, const float* bias,
-                     int M, int N, int K, long lda, long ldb, long ldc,
-                     int a_kc, int b_kc, int act, int accum, int splits,
-                     int batch, long sA, long sB, long sC, int seqT, int bshift, int prec, GemmP& p) {
-    ASR_REQUIRE(A && B && C, ASR_E_ARG, "asr_gemm: null operand");
-    ASR_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, ASR_E_ARG, "asr_gemm: bad dims M=%d N=%d K=%d batch=%d", M, N, K, batch);
-    ASR_REQUIRE(splits >= 1, ASR_E_ARG, "asr_gemm: splits must be >= 1");
-    ASR_REQUIRE(!(splits > 1 && (act != ASR_ACT_NONE || !accum)), ASR_E_ARG,
+// Argument checks of asr_gemm, then its plan (shared by the launch and the asr_gemm_plan query).
+static int gemm32_plan(const GemmCall& c, KernelPlan<GemmP>& pl) {
+    ASR_REQUIRE(c.A && c.B && c.C, ASR_E_ARG, "asr_gemm: null operand");
+    ASR_REQUIRE(c.M > 0 && c.N > 0 && c.K > 0 && c.batch > 0, ASR_E_ARG, "asr_gemm: bad dims M=%d N=%d K=%d batch=%d", c.M, c.N, c.K, c.batch);
+    ASR_REQUIRE(c.splits >= 1, ASR_E_ARG, "asr_gemm: splits must be >= 1");
+    ASR_REQUIRE(!(c.splits > 1 && (c.act != ASR_ACT_NONE || !c.accum)), ASR_E_ARG,
                 "asr_gemm: split reduction requires accum=1 and no activation");
-    ASR_REQUIRE(!(seqT > 0 && b_kc), ASR_E_ARG, "asr_gemm: shifted reduction rows need b_kc=0");
-    ASR_REQUIRE(prec == ASR_F32 || prec == ASR_BF16, ASR_E_ARG, "asr_gemm: bad prec %d", prec);
-    ASR_REQUIRE(ldc >= N, ASR_E_ARG, "asr_gemm: ldc < N");
-    p.A = A; p.B = B; p.C = C; p.bias = bias;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.sA = sA; p.sB = sB; p.sC = sC; p.batch = batch; p.splits = splits;
-    p.act = act; p.accum = accum; p.seqT = seqT; p.bshift = bshift;
-    p.convA = p.convB = p.cT = p.cF = p.cC = 0;
-    p.c16 = p.permH = p.bpadT = 0;
-    p.vecA = (((uintptr_t)A & 15) == 0 && (lda % 4) == 0 && (sA % 4) == 0) ? 1 : 0;
-    // vecB also covers the shifted operand: its rows are read at an offset and stay 16-byte aligned because ldb % 4 == 0
-    p.vecB = (((uintptr_t)B & 15) == 0 && (ldb % 4) == 0 && (sB % 4) == 0) ? 1 : 0;
-    return ASR_OK;
+    ASR_REQUIRE(!(c.seqT > 0 && c.b_kc), ASR_E_ARG, "asr_gemm: shifted reduction rows need b_kc=0");
+    ASR_REQUIRE(c.prec == ASR_F32 || c.prec == ASR_BF16, ASR_E_ARG, "asr_gemm: bad prec %d", c.prec);
+    ASR_REQUIRE(c.ldc >= c.N, ASR_E_ARG, "asr_gemm: ldc < N");
+    return gemm_plan(c, false, pl);
+}
+int gemm_run(const GemmCall& c, hipStream_t st) {
+    KernelPlan<GemmP> pl;
+    const int rc = gemm32_plan(c, pl);
+    return rc != ASR_OK ? rc : gemm_launch(pl, st);
 }
 
 extern "C" int asr_gemm(const float* A, const float* B, float* C, const float* bias,
@@ -507,11 +470,9 @@ extern "C" int asr_gemm(const float* A, const float* B, float* C, const float* b
                         int a_kc, int b_kc, int act, int accum, int splits,
                         int batch, long sA, long sB, long sC, int seqT, int bshift,
                         int prec, asr_stream_t stream) {
-    GemmP p;
-    const int rc = gemm_args(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, batch, sA, sB, sC, seqT, bshift, prec, p);
-    if (rc != ASR_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return prec == ASR_BF16 ? launch_gemm<true>(p, a_kc, b_kc, st) : launch_gemm<false>(p, a_kc, b_kc, st);
+    GemmCall c{A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, seqT, bshift, batch, sA, sB, sC};
+    c.prec = prec;
+    return gemm_run(c, (hipStream_t)stream);
 }
 
 // The plan asr_gemm launches with for these arguments (host arithmetic only: nothing is launched, no pointer is followed).
@@ -521,68 +482,54 @@ extern "C" int asr_gemm_plan(const float* A, const float* B, float* C, const flo
                              int batch, long sA, long sB, long sC, int seqT, int bshift,
                              int prec, int out[8]) {
     ASR_REQUIRE(out, ASR_E_ARG, "asr_gemm_plan: null out");
-    GemmP p;
-    const int rc = gemm_args(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, batch, sA, sB, sC, seqT, bshift, prec, p);
+    GemmCall c{A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, seqT, bshift, batch, sA, sB, sC};
+    c.prec = prec;
+    KernelPlan<GemmP> pl;
+    const int rc = gemm32_plan(c, pl);
     if (rc != ASR_OK) return rc;
-    long nblk = 0;
-    const int prc = gemm_plan(p, a_kc, b_kc, false, nblk);
-    if (prc != ASR_OK) return prc;
-    gemm_plan_out(p, out);
+    for (int i = 0; i < 8; ++i) out[i] = pl.out[i];
     return ASR_OK;
 }
 
-int gemm16_nt(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc,
-              int act, hipStream_t st);       // gemm16.hip
-int gemm16_tn(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-              int seqT, int bshift, int padded, hipStream_t st);
-int gemm16_nt_route(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc);
-int gemm16_tn_route(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                    int seqT, int bshift, int padded);
-void gemm16_nt_info(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc, int out[8]);
-void gemm16_tn_info(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                    int seqT, int bshift, int padded, int out[8]);
 static int nt_fast_enabled() {
     static const int on = [] { const char* e = getenv("ASR_GEMM16_NT"); return (e && e[0] == '0') ? 0 : 1; }();
     return on;
 }
 
+// The plan of one asr_gemm16 call: the route and that kernel's plan.
+struct Gemm16Plan {
+    KernelPlan<GemmP> generic; KernelPlan<G16P> nt; KernelPlan<T16P> tn;
+    int generic_rc = ASR_OK;         // route 0: what gemm_plan answered
+    const int* out(int route) const { return route == 0 ? generic.out : (route == 2 ? tn.out : nt.out); }
+};
 // Argument checks of asr_gemm16 and the kernel the call takes: 0 = the generic bf16-storage kernel (gemm_kernel IO16),
 // 1 / 3 = gemm16_nt_kernel at 128 x 128 / 256 x 256, 2 = gemm16_tn_kernel; negative = refused.  Host arithmetic only.
-extern "C" int asr_gemm16_route(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
-                                int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
-                                int seqT, int bshift, int b_time_padded) {
-    ASR_REQUIRE(A && B && C, ASR_E_ARG, "asr_gemm16: null operand");
-    ASR_REQUIRE(M > 0 && N > 0 && K > 0 && splits >= 1, ASR_E_ARG, "asr_gemm16: bad dims M=%d N=%d K=%d", M, N, K);
-    ASR_REQUIRE(!(splits > 1 && (act != ASR_ACT_NONE || !accum || c_bf16)), ASR_E_ARG, "asr_gemm16: split reduction needs an fp32 accumulating output");
-    ASR_REQUIRE(!(c_bf16 && (accum || perm_h)), ASR_E_ARG, "asr_gemm16: a bf16 output is written, not accumulated or permuted");
-    ASR_REQUIRE(!(seqT > 0 && b_kc), ASR_E_ARG, "asr_gemm16: shifted reduction rows need b_kc=0");
-    ASR_REQUIRE(ldc >= N, ASR_E_ARG, "asr_gemm16: ldc < N");
+static int gemm16_plan(const GemmCall& c, Gemm16Plan& pl) {
+    ASR_REQUIRE(c.A && c.B && c.C, ASR_E_ARG, "asr_gemm16: null operand");
+    ASR_REQUIRE(c.M > 0 && c.N > 0 && c.K > 0 && c.splits >= 1, ASR_E_ARG, "asr_gemm16: bad dims M=%d N=%d K=%d", c.M, c.N, c.K);
+    ASR_REQUIRE(!(c.splits > 1 && (c.act != ASR_ACT_NONE || !c.accum || c.c_bf16)), ASR_E_ARG, "asr_gemm16: split reduction needs an fp32 accumulating output");
+    ASR_REQUIRE(!(c.c_bf16 && (c.accum || c.perm_h)), ASR_E_ARG, "asr_gemm16: a bf16 output is written, not accumulated or permuted");
+    ASR_REQUIRE(!(c.seqT > 0 && c.b_kc), ASR_E_ARG, "asr_gemm16: shifted reduction rows need b_kc=0");
+    ASR_REQUIRE(c.ldc >= c.N, ASR_E_ARG, "asr_gemm16: ldc < N");
     // 16-byte loads of 8 bf16 along the contiguous index of each operand
-    ASR_REQUIRE((((uintptr_t)A | (uintptr_t)B) & 15) == 0 && lda % 8 == 0 && ldb % 8 == 0, ASR_E_UNSUPPORTED, "asr_gemm16: operands must be 16-byte aligned with row strides that are multiples of 8");
-    ASR_REQUIRE((a_kc ? K : M) % 8 == 0 && (b_kc ? K : N) % 8 == 0, ASR_E_UNSUPPORTED, "asr_gemm16: contiguous extents must be multiples of 8");
-    ASR_REQUIRE(perm_h == 0 || M % (4 * perm_h) == 0, ASR_E_ARG, "asr_gemm16: perm_h does not divide M");
-    if (a_kc && b_kc && c_bf16 && splits == 1 && nt_fast_enabled()) {
-        // direct-to-LDS 128x128x64 kernel (gemm16.hip); 0 = shape does not qualify, fall through to the generic kernel
-        const int r = gemm16_nt_route(A, B, C, bias, M, N, K, lda, ldb, ldc);
-        if (r) return r;
-    }
-    if (!a_kc && !b_kc && !c_bf16 && accum && act == ASR_ACT_NONE && bias == nullptr && nt_fast_enabled()) {
-        const int r = gemm16_tn_route(A, B, (float*)C, M, N, K, lda, ldb, ldc, splits, perm_h, seqT, bshift, b_time_padded);
-        if (r) return r;
-    }
+    ASR_REQUIRE((((uintptr_t)c.A | (uintptr_t)c.B) & 15) == 0 && c.lda % 8 == 0 && c.ldb % 8 == 0, ASR_E_UNSUPPORTED, "asr_gemm16: operands must be 16-byte aligned with row strides that are multiples of 8");
+    ASR_REQUIRE((c.a_kc ? c.K : c.M) % 8 == 0 && (c.b_kc ? c.K : c.N) % 8 == 0, ASR_E_UNSUPPORTED, "asr_gemm16: contiguous extents must be multiples of 8");
+    ASR_REQUIRE(c.perm_h == 0 || c.M % (4 * c.perm_h) == 0, ASR_E_ARG, "asr_gemm16: perm_h does not divide M");
+    // the direct-to-LDS kernels of gemm16.hip where the call has their form and its shape qualifies, else the generic kernel
+    if (c.a_kc && c.b_kc && c.c_bf16 && c.splits == 1 && nt_fast_enabled() && gemm16_nt_plan(c, pl.nt)) return pl.nt.route;
+    if (!c.a_kc && !c.b_kc && !c.c_bf16 && c.accum && c.act == ASR_ACT_NONE && c.bias == nullptr && nt_fast_enabled() &&
+        gemm16_tn_plan(c, pl.tn)) return pl.tn.route;
+    pl.generic_rc = gemm_plan(c, true, pl.generic);
     return 0;
 }
 
-// Launch parameters of the generic kernel for an asr_gemm16 call (shared by the launch and the asr_gemm16_plan query)
-static void gemm16_generic_args(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
-                                int act, int accum, int splits, int c_bf16, int perm_h, int seqT, int bshift, int b_time_padded, GemmP& p) {
-    p.A = (const float*)A; p.B = (const float*)B; p.C = (float*)C; p.bias = bias;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.sA = p.sB = p.sC = 0; p.batch = 1; p.splits = splits;
-    p.act = act; p.accum = accum; p.seqT = seqT; p.bshift = bshift;
-    p.convA = p.convB = p.cT = p.cF = p.cC = 0;
-    p.c16 = c_bf16; p.permH = perm_h; p.bpadT = b_time_padded;
-    p.vecA = p.vecB = 1;
+extern "C" int asr_gemm16_route(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
+                                int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
+                                int seqT, int bshift, int b_time_padded) {
+    GemmCall c{A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, seqT, bshift};
+    c.c_bf16 = c_bf16; c.perm_h = perm_h; c.b_time_padded = b_time_padded;
+    Gemm16Plan pl;
+    return gemm16_plan(c, pl);
 }
 
 // Contraction on bf16 operands in HBM (the encoder stack's activations, gate gradients and the bf16 weight copies):
@@ -591,19 +538,14 @@ static void gemm16_generic_args(const void* A, const void* B, void* C, const flo
 extern "C" int asr_gemm16(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc,
                           int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
                           int seqT, int bshift, int b_time_padded, asr_stream_t stream) {
-    const int route = asr_gemm16_route(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded);
+    GemmCall c{A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, seqT, bshift};
+    c.c_bf16 = c_bf16; c.perm_h = perm_h; c.b_time_padded = b_time_padded;
+    Gemm16Plan pl;
+    const int route = gemm16_plan(c, pl);
     if (route < 0) return route;
-    if (route == 1 || route == 3) {
-        const int rc = gemm16_nt(A, B, C, bias, M, N, K, lda, ldb, ldc, act, (hipStream_t)stream);
-        if (rc <= 0) return rc;
-    }
-    if (route == 2) {
-        const int rc = gemm16_tn(A, B, (float*)C, M, N, K, lda, ldb, ldc, splits, perm_h, seqT, bshift, b_time_padded, (hipStream_t)stream);
-        if (rc <= 0) return rc;
-    }
-    GemmP p;
-    gemm16_generic_args(A, B, C, bias, M, N, K, lda, ldb, ldc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded, p);
-    return launch_gemm<true>(p, a_kc, b_kc, (hipStream_t)stream, true);
+    if (route == 2) return gemm16_tn_launch(pl.tn, (hipStream_t)stream);
+    if (route != 0) return gemm16_nt_launch(pl.nt, (hipStream_t)stream);
+    return pl.generic_rc != ASR_OK ? pl.generic_rc : gemm_launch(pl.generic, (hipStream_t)stream);
 }
 
 // The plan behind asr_gemm16_route's answer (host arithmetic only).  Returns the route and fills out[8]:
@@ -615,21 +557,14 @@ extern "C" int asr_gemm16_plan(const void* A, const void* B, void* C, const floa
                                int a_kc, int b_kc, int act, int accum, int splits, int c_bf16, int perm_h,
                                int seqT, int bshift, int b_time_padded, int out[8]) {
     ASR_REQUIRE(out, ASR_E_ARG, "asr_gemm16_plan: null out");
-    const int route = asr_gemm16_route(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded);
+    GemmCall c{A, B, C, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, act, accum, splits, seqT, bshift};
+    c.c_bf16 = c_bf16; c.perm_h = perm_h; c.b_time_padded = b_time_padded;
+    Gemm16Plan pl;
+    const int route = gemm16_plan(c, pl);
     if (route < 0) return route;
     for (int i = 0; i < 8; ++i) out[i] = 0;
-    if (route == 1 || route == 3) {
-        gemm16_nt_info(A, B, C, bias, M, N, K, lda, ldb, ldc, out);
-    } else if (route == 2) {
-        gemm16_tn_info(A, B, (float*)C, M, N, K, lda, ldb, ldc, splits, perm_h, seqT, bshift, b_time_padded, out);
-    } else {
-        GemmP p;
-        gemm16_generic_args(A, B, C, bias, M, N, K, lda, ldb, ldc, act, accum, splits, c_bf16, perm_h, seqT, bshift, b_time_padded, p);
-        long nblk = 0;
-        const int prc = gemm_plan(p, a_kc, b_kc, true, nblk);
-        if (prc != ASR_OK) return prc;
-        gemm_plan_out(p, out);
-    }
+    if (route == 0 && pl.generic_rc != ASR_OK) return pl.generic_rc;
+    for (int i = 0; i < 8; ++i) out[i] = pl.out(route)[i];
     return route;
 }
 
@@ -641,25 +576,16 @@ extern "C" int asr_conv3x3(const float* img, const float* w_or_dout, float* out,
     ASR_REQUIRE(img && w_or_dout && out, ASR_E_ARG, "asr_conv3x3: null pointer");
     ASR_REQUIRE(B > 0 && T > 0 && F > 0 && C > 0 && N > 0, ASR_E_ARG, "asr_conv3x3: bad dims");
     ASR_REQUIRE((long)B * T * F < (1L << 31), ASR_E_UNSUPPORTED, "asr_conv3x3: more than 2^31 pixels");
-    GemmP p;
     const int rows = B * T * F, K9 = 9 * C;
-    p.bias = bias; p.act = act; p.accum = accum; p.seqT = 0; p.bshift = 0; p.batch = 1; p.sA = p.sB = p.sC = 0;
-    p.c16 = p.permH = p.bpadT = 0;
-    p.cT = T; p.cF = F; p.cC = C;
-    hipStream_t st = (hipStream_t)stream;
-    if (mode == 0) {
-        p.A = img; p.B = w_or_dout; p.C = out; p.M = rows; p.N = N; p.K = K9; p.lda = C; p.ldb = K9; p.ldc = N;
-        p.convA = 1; p.convB = 0; p.splits = 1;
-        p.vecA = (((uintptr_t)img & 15) == 0) ? 1 : 0;
-        p.vecB = (((uintptr_t)w_or_dout & 15) == 0 && (K9 % 4) == 0) ? 1 : 0;
-        return prec == ASR_BF16 ? launch_gemm<true>(p, 1, 1, st) : launch_gemm<false>(p, 1, 1, st);
+    GemmCall c{img, w_or_dout, out, bias, rows, N, K9, C, K9, N};
+    if (mode != 0) {
+        // wgrad: C[i = n, j = (tap,ci)] += sum_r dout[r, i] * conv(img)[r, j]
+        ASR_REQUIRE(accum == 1 && act == ASR_ACT_NONE && bias == nullptr, ASR_E_ARG, "asr_conv3x3: wgrad accumulates without epilogue");
+        c = gemm_wgrad_call(w_or_dout, img, out, N, K9, rows, N, C, K9, rows >= 65536 ? 32 : (rows >= 4096 ? 8 : 1));
     }
-    // wgrad: C[i = n, j = (tap,ci)] += sum_r dout[r, i] * conv(img)[r, j]
-    ASR_REQUIRE(accum == 1 && act == ASR_ACT_NONE && bias == nullptr, ASR_E_ARG, "asr_conv3x3: wgrad accumulates without epilogue");
-    p.A = w_or_dout; p.B = img; p.C = out; p.M = N; p.N = K9; p.K = rows; p.lda = N; p.ldb = C; p.ldc = K9;
-    p.convA = 0; p.convB = 1;
-    p.splits = rows >= 65536 ? 32 : (rows >= 4096 ? 8 : 1);
-    p.vecA = (((uintptr_t)w_or_dout & 15) == 0 && (N % 4) == 0) ? 1 : 0;
-    p.vecB = (((uintptr_t)img & 15) == 0) ? 1 : 0;
-    return prec == ASR_BF16 ? launch_gemm<true>(p, 0, 0, st) : launch_gemm<false>(p, 0, 0, st);
+    c.act = act; c.accum = accum; c.prec = prec;
+    c.conv_T = T; c.conv_F = F; c.conv_C = C;
+    KernelPlan<GemmP> pl;
+    const int rc = gemm_plan(c, false, pl);
+    return rc != ASR_OK ? rc : gemm_launch(pl, (hipStream_t)stream);
 }

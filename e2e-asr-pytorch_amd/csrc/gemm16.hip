@@ -15,26 +15,13 @@
 //    this model - 160 .. 2560 - so a deep per-workgroup pipeline would spend its time in prologue and epilogue);
 //  * tile order: each XCD gets a contiguous run of tiles, N fastest, so the X rows of a run stay in that XCD's L2 and the
 //    weight matrix (<= 3.3 MB) is shared by all of its workgroups.
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64, NTH = 256;
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;     // one k-step of both operands in LDS (32 KB)
 constexpr unsigned OOB = 0x80000000u;        // byte offset beyond any operand (num_records < 2^31): the load returns zeros
-
-struct G16P {
-    const unsigned short* X; const unsigned short* W; unsigned short* C; const float* bias;
-    int M, N, K;
-    long ldx, ldw, ldc;
-    int act;
-    unsigned xbytes, wbytes;
-    int ntx, nty;            // tiles along N, along M
-    // CONV instantiation only: rows are the pixels of a zero-bordered channel-last image (B, T2, F2, C) and k-step kt of the
-    // 9*C-deep reduction reads the rows shifted by its tap (convC > 0), border rows are stored as zeros (maskF2 > 0)
-    int convC, maskF2, maskT2;
-    float* C32;              // CONV only: when set, the result goes here as fp32 (pre-activations that a LayerNorm normalises next)
-};
 
 typedef __attribute__((address_space(3))) void lds_void;
 // tanh through one exp and one reciprocal (relative error ~1e-6, far below the bf16 rounding of the stored result)
@@ -205,86 +192,46 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN > 4) ? 1 : 2) void gemm1
 
 }  // namespace
 
-// Qualification and launch parameters of the NT kernel: 0 = qualifies (p and big filled), 1 = the shape does not.  Host
-// arithmetic only; the launch (gemm16_nt) and the route query (gemm16_nt_route) both decide here.
-static int gemm16_nt_plan(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc,
-                          int act, G16P& p, bool& big_out) {
-    if (K % 8 != 0 || N % 8 != 0 || ldx % 8 != 0 || ldw % 8 != 0 || ldc % 8 != 0) return 1;
-    if ((((uintptr_t)X | (uintptr_t)W | (uintptr_t)C) & 15) != 0 || (bias && ((uintptr_t)bias & 15) != 0)) return 1;
-    const long xb = ((long)(M - 1) * ldx + K) * 2, wb = ((long)(N - 1) * ldw + K) * 2;
-    if (xb >= (1L << 31) || wb >= (1L << 31)) return 1;
-    if (xb + 2L * K >= (long)OOB || wb + 2L * K >= (long)OOB) return 1;   // a valid byte offset never equals the OOB marker
+// Plan of the NT kernel for a call of the form x W^T -> bf16 (a_kc = b_kc = 1, splits = 1): X = A (M,K), W = B (N,K).
+// conv_F > 0: a 3x3 convolution (stride 1, zero padding 1) as an implicit GEMM, nn.Conv2d of the VGG front-ends (reference
+// src/module.py:599-614,670-681).  X: zero-bordered channel-last bf16 image (B, T+2, F+2, C) of M pixel rows, conv_T = T+2,
+// conv_F = F+2, conv_C = C with C % 64 == 0; W: (N, 9*C) bf16 with k = tap*C + ci; out: (B, T+2, F+2, N) bf16, borders written
+// as zeros (ready to be the next layer's input), or fp32 without activation where c_bf16 = 0 (the input of a CNNLayerNorm).
+// conv_C == 0: X is an explicit (rows, K) patch matrix over the same zero-bordered pixel grid (first layer: C = 4), only the
+// border mask applies.
+bool gemm16_nt_plan(const GemmCall& c, KernelPlan<G16P>& pl) {
+    const bool conv = c.conv_F > 0;
+    if (c.K % 8 != 0 || c.N % 8 != 0) return false;
+    if (!conv && (c.lda % 8 != 0 || c.ldb % 8 != 0 || c.ldc % 8 != 0)) return false;
+    if (conv && c.conv_C > 0 && (c.conv_C % 64 != 0 || c.K != 9 * c.conv_C)) return false;
+    if (conv && !c.c_bf16 && c.act != ASR_ACT_NONE) return false;
+    if ((((uintptr_t)c.A | (uintptr_t)c.B | (uintptr_t)c.C) & 15) != 0 || (c.bias && ((uintptr_t)c.bias & 15) != 0)) return false;
+    // buffer extents: up to the last element read, or the whole bordered image (its taps reach rows before and after any row)
+    const long xb = conv ? (long)c.M * c.lda * 2 : ((long)(c.M - 1) * c.lda + c.K) * 2, wb = ((long)(c.N - 1) * c.ldb + c.K) * 2;
+    if (!conv && (xb >= (1L << 31) || wb >= (1L << 31))) return false;
+    if (xb + 2L * c.K >= (long)OOB || wb + 2L * c.K >= (long)OOB) return false;   // a valid byte offset never equals the OOB marker
     // The 256 x 256 tiling is selected by ASR_GEMM16_BIG=1 only: measured on MI355X it is no faster on any shape of the
     // encoder (78.7 vs 80.1 us on 19200 x 2560 x 640, slower wherever the tile count drops under two rounds) - the main
     // loop, not the fragment traffic, holds both tilings near 0.3 of the MFMA peak.
-    static const bool big = [] { const char* e = getenv("ASR_GEMM16_BIG"); return e && atoi(e) > 0; }();
+    static const bool big_on = [] { const char* e = getenv("ASR_GEMM16_BIG"); return e && atoi(e) > 0; }();
+    const bool big = big_on && !conv;
     const int bm = big ? 256 : BM, bn = big ? 256 : BN;
-    p = G16P{(const unsigned short*)X, (const unsigned short*)W, (unsigned short*)C, bias, M, N, K, ldx, ldw, ldc, act,
-             (unsigned)xb, (unsigned)wb, cdiv(N, bn), cdiv(M, bm), 0, 0, 0, nullptr};
-    if ((long)p.ntx * p.nty >= (1L << 31)) return 1;
-    big_out = big;
-    return 0;
+    pl.p = G16P{(const unsigned short*)c.A, (const unsigned short*)c.B, (unsigned short*)c.C, c.bias, c.M, c.N, c.K, c.lda, c.ldb, c.ldc, c.act,
+                (unsigned)xb, (unsigned)wb, cdiv(c.N, bn), cdiv(c.M, bm), c.conv_C, c.conv_F, c.conv_T, (conv && !c.c_bf16) ? (float*)c.C : nullptr};
+    const long ntiles = (long)pl.p.ntx * pl.p.nty;
+    if (ntiles >= (1L << 31)) return false;
+    pl.kernel = conv ? gemm16_nt_kernel<2, 2, 4, true> : (big ? gemm16_nt_kernel<2, 4, 8> : gemm16_nt_kernel<2, 2, 4>);
+    pl.grid = (unsigned)ntiles; pl.block = big ? 512 : NTH; pl.lds = big ? 128 * 1024 : 2 * STAGE_BYTES;
+    pl.route = big ? 3 : 1;
+    pl.who = conv ? "asr_conv3x3_16" : "asr_gemm16(nt)";
+    pl.out[0] = pl.p.ntx; pl.out[1] = pl.p.nty; pl.out[2] = bm; pl.out[3] = bn;
+    return true;
 }
 
-// 0 = the generic kernel, 1 = this kernel's 128 x 128 tiling, 3 = its 256 x 256 tiling
-int gemm16_nt_route(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc) {
-    G16P p; bool big = false;
-    if (gemm16_nt_plan(X, W, C, bias, M, N, K, ldx, ldw, ldc, ASR_ACT_NONE, p, big)) return 0;
-    return big ? 3 : 1;
-}
-
-void gemm16_nt_info(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc, int out[8]) {
-    G16P p; bool big = false;
-    if (gemm16_nt_plan(X, W, C, bias, M, N, K, ldx, ldw, ldc, ASR_ACT_NONE, p, big)) return;
-    out[0] = p.ntx; out[1] = p.nty; out[2] = big ? 256 : BM; out[3] = big ? 256 : BN;
-}
-
-// Returns ASR_OK when launched, 1 when the shape does not qualify (the caller uses the generic kernel).
-int gemm16_nt(const void* X, const void* W, void* C, const float* bias, int M, int N, int K, long ldx, long ldw, long ldc,
-              int act, hipStream_t st) {
-    G16P p; bool big = false;
-    if (gemm16_nt_plan(X, W, C, bias, M, N, K, ldx, ldw, ldc, act, p, big)) return 1;
-    const long ntiles = (long)p.ntx * p.nty;
-    if (big) {
-        static const bool once = [] {
-            hipFuncSetAttribute((const void*)gemm16_nt_kernel<2, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            return true;
-        }();
-        (void)once;
-        hipLaunchKernelGGL((gemm16_nt_kernel<2, 4, 8>), dim3((unsigned)ntiles), dim3(512), 128 * 1024, st, p);
-    } else {
-        hipLaunchKernelGGL((gemm16_nt_kernel<2, 2, 4>), dim3((unsigned)ntiles), dim3(NTH), 2 * STAGE_BYTES, st, p);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("asr_gemm16(nt): launch failed: %s", hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
-}
-
-// 3x3 convolution (stride 1, zero padding 1) as an implicit GEMM on the NT kernel, nn.Conv2d of the VGG front-ends (reference
-// src/module.py:599-614,670-681).  img: zero-bordered channel-last bf16 image (B, T+2, F+2, C); W: (N, 9*C) bf16 with
-// k = tap*C + ci; out: (B, T+2, F+2, N) bf16, borders written as zeros (ready to be the next layer's input).  C % 64 == 0.
-// out_f32: the result is stored as fp32 (B, T+2, F+2, N) without activation (the input of a CNNLayerNorm).
-// convC == 0: `img` is an explicit (rows, K) patch matrix over the same zero-bordered pixel grid (first layer: C = 4), only the
-// border mask applies.  Returns 1 when the shape does not qualify.
-int gemm16_conv3x3(const void* img, const void* W, void* out, const float* bias, int B, int T, int F, int C, int N, int K, int implicit, int act,
-                   int out_f32, hipStream_t st) {
-    const int T2 = T + 2, F2 = F + 2;
-    const long M = (long)B * T2 * F2;
-    const long ldx = implicit ? C : K;
-    if (implicit && (C % 64 != 0 || K != 9 * C)) return 1;
-    if (K % 8 != 0 || N % 8 != 0 || M >= (1L << 31)) return 1;
-    if ((((uintptr_t)img | (uintptr_t)W | (uintptr_t)out) & 15) != 0 || (bias && ((uintptr_t)bias & 15) != 0)) return 1;
-    const long xb = M * ldx * 2, wb = (long)N * K * 2;
-    if (xb + 2L * K >= (long)OOB || wb + 2L * K >= (long)OOB) return 1;
-    G16P p{(const unsigned short*)img, (const unsigned short*)W, (unsigned short*)out, bias, (int)M, N, K, ldx, (long)K, (long)N, act,
-           (unsigned)xb, (unsigned)wb, cdiv(N, BN), cdiv(M, BM), implicit ? C : 0, F2, T2, out_f32 ? (float*)out : nullptr};
-    if (out_f32 && act != ASR_ACT_NONE) return 1;
-    const long ntiles = (long)p.ntx * p.nty;
-    if (ntiles >= (1L << 31)) return 1;
-    hipLaunchKernelGGL((gemm16_nt_kernel<2, 2, 4, true>), dim3((unsigned)ntiles), dim3(NTH), 2 * STAGE_BYTES, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("asr_conv3x3_16: launch failed: %s", hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
+int gemm16_nt_launch(const KernelPlan<G16P>& pl, hipStream_t st) {
+    static unsigned char big_lds_[32];        // only the 256 x 256 tiling goes beyond the 64 KB a kernel may use unasked
+    if (pl.lds > 64 * 1024 && first_on_device(big_lds_)) hipFuncSetAttribute((const void*)pl.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    return launch_plan(pl, st);
 }
 
 // =================================================================================================================
@@ -300,18 +247,6 @@ int gemm16_conv3x3(const void* img, const void* W, void* out, const float* bias,
 // direct-to-LDS load and again on the read).
 //   bshift / seqT / padded: row r = (b,t) of B is read at padded row b*(seqT+2) + t + 1 + bshift (h_{t-1} / h_{t+1} of the
 //   time-padded y16) - per-lane source addresses make that free;   permH: gate-minor -> reference row order of C.
-struct T16P {
-    const unsigned short* A; const unsigned short* B; float* C;
-    int I, J, R;                 // C is (I,J); reduction over R rows
-    long lda, ldb, ldc;
-    unsigned abytes, bbytes;
-    int nti, ntj, splits, per;   // tiles along I and J, reduction slices, k-steps per slice
-    int seqT, bshift, permH;
-    float inv_seqT;
-    int tapF2;                   // > 0: NINE contractions in one launch, the taps of a 3x3 convolution's weight gradient: tap
-                                 // (dt, df) reads B at row r + dt*tapF2 + df (rows outside [0, R) are zeros) and writes C at column tap*J
-};
-
 __device__ __forceinline__ int swz_f(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
 
 template <int STAGES>
@@ -457,40 +392,6 @@ __global__ __launch_bounds__(NTH, STAGES == 1 ? 3 : (STAGES == 2 ? 2 : 1)) void 
     }
 }
 
-// Returns ASR_OK when launched, 1 when the shape does not qualify.
-int gemm16_tn_taps(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                   int seqT, int bshift, int padded, int tapF2, hipStream_t st);
-int gemm16_tn(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-              int seqT, int bshift, int padded, hipStream_t st) {
-    return gemm16_tn_taps(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, 0, st);
-}
-// Qualification and launch parameters of the TN kernel: 0 = qualifies (p and the workgroup count filled), 1 = the shape does
-// not.  Host arithmetic only; the launch (gemm16_tn_taps) and the route query (gemm16_tn_route) both decide here.
-static int gemm16_tn_plan(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                          int seqT, int bshift, int padded, int tapF2, T16P& p, long& total) {
-    if (I % 8 != 0 || J % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0) return 1;
-    if ((((uintptr_t)A | (uintptr_t)B) & 15) != 0) return 1;
-    if (seqT > 0 && !padded) return 1;                        // unpadded shifted rows need masking: generic kernel
-    const long rows_b = seqT > 0 ? (long)(R / seqT) * (seqT + 2) : R;
-    const long ab = ((long)(R - 1) * lda + I) * 2, bb = ((rows_b - 1) * ldb + J) * 2;
-    if (ab >= (1L << 31) || bb >= (1L << 31) || (seqT > 0 && R % seqT != 0)) return 1;
-    const int nk = cdiv(R, BK);
-    if (splits < 1) splits = 1;
-    if (splits > nk) splits = nk;
-    p = T16P{(const unsigned short*)A, (const unsigned short*)B, C, I, J, R, lda, ldb, ldc, (unsigned)ab, (unsigned)bb,
-             cdiv(I, BM), cdiv(J, BN), splits, cdiv(nk, splits), seqT, bshift, perm_h, seqT > 0 ? 1.0f / (float)seqT : 0.f, tapF2};
-    total = (long)p.nti * p.ntj * p.splits * (tapF2 > 0 ? 9 : 1);
-    if (total >= (1L << 31)) return 1;
-    return 0;
-}
-
-// 0 = the generic kernel, 2 = this kernel
-int gemm16_tn_route(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                    int seqT, int bshift, int padded) {
-    T16P p; long total = 0;
-    return gemm16_tn_plan(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, 0, p, total) ? 0 : 2;
-}
-
 // LDS stages of the TN kernel: ASR_GEMM16_TN_STAGES=2 / 4 select the pipelined instantiations (two / one workgroup per CU);
 // default, and any other value, one stage at three per CU
 static int gemm16_tn_stages() {
@@ -498,30 +399,35 @@ static int gemm16_tn_stages() {
     return stages;
 }
 
-void gemm16_tn_info(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                    int seqT, int bshift, int padded, int out[8]) {
-    T16P p; long total = 0;
-    if (gemm16_tn_plan(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, 0, p, total)) return;
-    out[0] = p.nti; out[1] = p.ntj; out[2] = p.splits; out[3] = p.per; out[4] = gemm16_tn_stages(); out[5] = (int)total;
+// Plan of the TN kernel for a call of the form of a weight gradient (a_kc = b_kc = 0, fp32 C accumulated, no bias, no activation):
+// I = M, J = N, reduction over R = K rows.  conv_F > 0: the nine taps of a 3x3 convolution's weight gradient (T16P::tapF2).
+bool gemm16_tn_plan(const GemmCall& c, KernelPlan<T16P>& pl) {
+    const int I = c.M, J = c.N, R = c.K, seqT = c.seqT;
+    if (I % 8 != 0 || J % 8 != 0 || c.lda % 8 != 0 || c.ldb % 8 != 0) return false;
+    if ((((uintptr_t)c.A | (uintptr_t)c.B) & 15) != 0) return false;
+    if (seqT > 0 && !c.b_time_padded) return false;           // unpadded shifted rows need masking: generic kernel
+    const long rows_b = seqT > 0 ? (long)(R / seqT) * (seqT + 2) : R;
+    const long ab = ((long)(R - 1) * c.lda + I) * 2, bb = ((rows_b - 1) * c.ldb + J) * 2;
+    if (ab >= (1L << 31) || bb >= (1L << 31) || (seqT > 0 && R % seqT != 0)) return false;
+    const int nk = cdiv(R, BK), splits = c.splits < 1 ? 1 : (c.splits > nk ? nk : c.splits), ntap = c.conv_F > 0 ? 9 : 1;
+    T16P& p = pl.p;
+    p = T16P{(const unsigned short*)c.A, (const unsigned short*)c.B, (float*)c.C, I, J, R, c.lda, c.ldb, c.ldc, (unsigned)ab, (unsigned)bb,
+             cdiv(I, BM), cdiv(J, BN), splits, cdiv(nk, splits), seqT, c.bshift, c.perm_h, seqT > 0 ? 1.0f / (float)seqT : 0.f, c.conv_F};
+    const long total = (long)p.nti * p.ntj * p.splits * ntap;
+    if (total >= (1L << 31)) return false;
+    const int stages = gemm16_tn_stages();
+    pl.kernel = stages == 4 ? gemm16_tn_kernel<4> : (stages == 2 ? gemm16_tn_kernel<2> : gemm16_tn_kernel<1>);
+    pl.grid = (unsigned)total; pl.block = NTH; pl.lds = stages * STAGE_BYTES;
+    pl.route = 2;
+    pl.who = "asr_gemm16(tn)";
+    const int out[8] = {p.nti, p.ntj, p.splits, p.per, stages, (int)total, 0, 0};
+    for (int i = 0; i < 8; ++i) pl.out[i] = out[i];
+    return true;
 }
 
-int gemm16_tn_taps(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                   int seqT, int bshift, int padded, int tapF2, hipStream_t st) {
-    T16P p; long total = 0;
-    if (gemm16_tn_plan(A, B, C, I, J, R, lda, ldb, ldc, splits, perm_h, seqT, bshift, padded, tapF2, p, total)) return 1;
-    const int stages = gemm16_tn_stages();
-    if (stages == 4) {
-        static unsigned char attr4_[32];
-        if (first_on_device(attr4_)) hipFuncSetAttribute((const void*)gemm16_tn_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * STAGE_BYTES);
-        hipLaunchKernelGGL(gemm16_tn_kernel<4>, dim3((unsigned)total), dim3(NTH), 4 * STAGE_BYTES, st, p);
-    } else if (stages == 2) {
-        static const bool once = [] { hipFuncSetAttribute((const void*)gemm16_tn_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES); return true; }();
-        (void)once;
-        hipLaunchKernelGGL(gemm16_tn_kernel<2>, dim3((unsigned)total), dim3(NTH), 2 * STAGE_BYTES, st, p);
-    } else {
-        hipLaunchKernelGGL(gemm16_tn_kernel<1>, dim3((unsigned)total), dim3(NTH), STAGE_BYTES, st, p);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { asr_set_error("asr_gemm16(tn): launch failed: %s", hipGetErrorString(e)); return ASR_E_LAUNCH; }
-    return ASR_OK;
+int gemm16_tn_launch(const KernelPlan<T16P>& pl, hipStream_t st) {
+    static unsigned char lds_[2][32];         // the 2- and the 4-stage instantiation ask for their dynamic LDS, per device
+    const int stages = pl.lds / STAGE_BYTES;
+    if (stages > 1 && first_on_device(lds_[stages == 4])) hipFuncSetAttribute((const void*)pl.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    return launch_plan(pl, st);
 }

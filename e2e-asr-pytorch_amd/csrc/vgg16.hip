@@ -9,12 +9,7 @@
 //     (one launch of gemm16_tn_kernel, the tap as a grid dimension) over the same images;
 //   * the first layer (C = input channels = 4: K = 36) reads an explicit patch matrix over the same pixel grid (61 MB);
 //   * pooling, LayerNorm-over-frequency and the layout changes at both ends work on the bordered bf16 images, 16 bytes per lane.
-#include "common.h"
-
-int gemm16_conv3x3(const void* img, const void* W, void* out, const float* bias, int B, int T, int F, int C, int N, int K, int implicit, int act,
-                   int out_f32, hipStream_t st);
-int gemm16_tn_taps(const void* A, const void* B, float* C, int I, int J, int R, long lda, long ldb, long ldc, int splits, int perm_h,
-                   int seqT, int bshift, int padded, int tapF2, hipStream_t st);
+#include "gemm_plan.h"
 
 namespace {
 
@@ -276,9 +271,15 @@ extern "C" int asr_conv_weight_fold(const float* src, float* dst, int Co, int Ci
 extern "C" int asr_conv3x3_16(const void* img, const void* w, void* out, const float* bias, int B, int T, int F, int C, int N, int K, int implicit,
                               int act, int out_f32, asr_stream_t stream) {
     ASR_REQUIRE(img && w && out && B > 0 && T > 0 && F > 0 && N > 0 && K > 0, ASR_E_ARG, "asr_conv3x3_16: bad args");
-    const int rc = gemm16_conv3x3(img, w, out, bias, B, T, F, C, N, K, implicit, act, out_f32, (hipStream_t)stream);
-    ASR_REQUIRE(rc != 1, ASR_E_UNSUPPORTED, "asr_conv3x3_16: shape not covered (C %% 64, K %% 8, N %% 8, 16-byte alignment): C=%d N=%d K=%d", C, N, K);
-    return rc;
+    // the pixel rows of the bordered image (B, T+2, F+2, .) times W (N, K)^T on the NT kernel; implicit: rows of C channels, K = 9*C
+    const long M = (long)B * (T + 2) * (F + 2);
+    GemmCall c{img, w, out, bias, (int)M, N, K, implicit ? C : K, K, N};
+    c.act = act; c.c_bf16 = out_f32 ? 0 : 1;
+    c.conv_T = T + 2; c.conv_F = F + 2; c.conv_C = implicit ? C : 0;
+    KernelPlan<G16P> pl;
+    ASR_REQUIRE(M < (1L << 31) && (!implicit || C > 0) && gemm16_nt_plan(c, pl), ASR_E_UNSUPPORTED,
+                "asr_conv3x3_16: shape not covered (C %% 64, K %% 8, N %% 8, 16-byte alignment): C=%d N=%d K=%d", C, N, K);
+    return gemm16_nt_launch(pl, (hipStream_t)stream);
 }
 
 // dw (N, ldw)[n][tap*C + ci] += sum over the bordered pixel rows of dout[row, n] * img[row + shift(tap), ci]
@@ -289,9 +290,11 @@ extern "C" int asr_conv3x3_16_wgrad(const void* img, const void* dout, float* dw
     ASR_REQUIRE(M < (1L << 31), ASR_E_ARG, "asr_conv3x3_16_wgrad: image too large");
     // ONE launch for the nine taps (tap = a grid dimension of gemm16_tn_kernel): 9 x splits x tiles workgroups fill the chip with
     // a ninth of the split-K atomics nine separate launches would need; shifted rows outside the image read as zeros
-    const int rc = gemm16_tn_taps(dout, img, dw, N, C, (int)M, N, C, ldw, splits, 0, 0, 0, 0, F + 2, (hipStream_t)stream);
-    ASR_REQUIRE(rc != 1, ASR_E_UNSUPPORTED, "asr_conv3x3_16_wgrad: shape not covered by the bf16 TN contraction");
-    return rc;
+    GemmCall c = gemm_wgrad_call(dout, img, dw, N, C, (int)M, N, C, ldw, splits);
+    c.conv_F = F + 2;
+    KernelPlan<T16P> pl;
+    ASR_REQUIRE(gemm16_tn_plan(c, pl), ASR_E_UNSUPPORTED, "asr_conv3x3_16_wgrad: shape not covered by the bf16 TN contraction");
+    return gemm16_tn_launch(pl, (hipStream_t)stream);
 }
 
 extern "C" int asr_maxpool2x2_16_fwd(const void* x, void* y, unsigned char* idx, int B, int T, int F, int C, int T2, int F2, asr_stream_t stream) {

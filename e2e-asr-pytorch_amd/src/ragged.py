@@ -91,7 +91,7 @@ def max_batch(asr):
 
 # Byte budget of the largest single activation of a conv front-end over one chunk of the batch.  asr_conv3x3_16 addresses
 # its bf16 input image by 32-bit byte offsets that must stay below 2^31, one 2 K-byte read-ahead (K = 9 C <= 2304) included
-# (csrc/gemm16.hip: gemm16_conv3x3), and every image a convolution reads is at most as large as the largest activation of
+# (csrc/gemm16.hip: gemm16_nt_plan), and every image a convolution reads is at most as large as the largest activation of
 # the stack; 2^31 - 2^16 keeps them all addressable.  The fp32-operand path (asr_conv3x3: < 2^31 pixels) is inside the same
 # bound.  At most five such tensors are alive at once (input, pre-activation, activation, pooled, pooling index).
 FRONTEND_ACT_BYTES = (1 << 31) - (1 << 16)
