@@ -8,7 +8,9 @@ kernels do not cover (GRU, dot / multi-head attention, v_proj, deep LSTM) take t
 searches share the bookkeeping of _BeamBook.  A CTC-only model (ctc_weight = 1: no attention decoder) is decoded by a CTC
 prefix beam search instead, the whole search of all utterances in ONE launch (asr_ctc_beam_search, csrc/ctc_decode.hip); with
 an RNN-LM (shallow fusion) by the resumable form of that search, which stops whenever a new prefix needs an LM step
-(asr_ctc_beam_lm_advance).  The reference has no counterpart (`# ToDo : implement pure ctc decode`)."""
+(asr_ctc_beam_lm_advance).  The reference has no counterpart (`# ToDo : implement pure ctc decode`).  A joint model built
+with rescore=True is decoded in two passes: that CTC search proposes the n-best list, the attention decoder scores the
+hypotheses teacher-forced in one batched pass, and asr_rescore_nbest (csrc/rescore.hip) mixes the scores and re-ranks."""
 import ctypes
 import math
 
@@ -24,6 +26,13 @@ from src.lm import RNNLM
 
 CTC_BEAM_RATIO = 1.5
 LOG_ZERO = -10000000.0
+EOS = 1
+# Two-pass decoding runs the TRAINING forward of the decoder, which keeps its per-step state for a backward pass that never
+# comes; the largest piece is the location convolution's output, (rows, L, Kn, T') fp32.  A chunk of hypothesis rows keeps that
+# under RESCORE_STATE_BYTES (the sibling of ragged.FRONTEND_ACT_BYTES) and holds at most RESCORE_MAX_ROWS rows, the most the
+# streamed decoder plan takes at once (csrc/decoder_plan.h: B <= 64).
+RESCORE_STATE_BYTES = 1 << 30
+RESCORE_MAX_ROWS = 64
 
 
 def encode_unpadded(asr, audio_feature, feature_len, with_ctc):
@@ -151,11 +160,13 @@ class CTCHypothesis(object):
     """One result of the CTC prefix beam search: the collapsed token sequence (a trailing <eos> included when the model
     emits one) and its score.  CTC gives a sequence no per-token scores, so avgScore() IS the sequence score (not divided by
     the length) - the quantity the search ranks by: the sequence's CTC log-probability `ctc_score`, plus with an LM
-    lm_weight * its LM log-probability + len_bonus * its length."""
+    lm_weight * its LM log-probability + len_bonus * its length.  After two-pass decoding (rescore=True) `score` is the mixed
+    score the list was re-ranked by and `att_score` the attention decoder's log-probability of the sequence and its <eos>."""
 
-    def __init__(self, output_seq, score, ctc_score=None):
+    def __init__(self, output_seq, score, ctc_score=None, att_score=None):
         self.output_seq, self.score = output_seq, score
         self.ctc_score = score if ctc_score is None else ctc_score
+        self.att_score = att_score
 
     def avgScore(self):
         return self.score
@@ -167,24 +178,42 @@ class CTCHypothesis(object):
 
 class BeamDecoder(nn.Module):
     def __init__(self, asr, emb_decoder, beam_size, min_len_ratio, max_len_ratio, lm_path='', lm_config='', lm_weight=0.0,
-                 ctc_weight=0.0, batch_encode=False, len_bonus=0.0):
+                 ctc_weight=0.0, batch_encode=False, len_bonus=0.0, rescore=False, rescore_rows=None):
         super().__init__()
         assert emb_decoder is None, 'embedding-fusion decoding is outside the HIP path'
         self.batch_encode = bool(batch_encode)      # opt-in: the batched pass agrees with the per-utterance one to rounding only
         self.beam_size, self.min_len_ratio, self.max_len_ratio, self.asr = beam_size, min_len_ratio, max_len_ratio, asr
         self.ctc_only = not self.asr.enable_att
-        if self.ctc_only:
+        self.rescore = bool(rescore)
+        if self.rescore:
+            # two passes: the CTC search below proposes, the attention decoder rescores - the model needs both halves
+            if self.ctc_only:
+                raise ValueError('rescore=True needs an attention decoder to rescore with, and this model has none (CTC-only, '
+                                 'ctc_weight = 1): decode it without rescore, by the CTC prefix beam search alone')
+            if not self.asr.ctc_weight > 0:
+                raise ValueError('rescore=True needs a CTC head to propose the n-best list, and this model has none (ctc_weight = 0): '
+                                 'decode it without rescore, by the joint beam search')
+        if self.ctc_only or self.rescore:
             # no attention decoder to search with: CTC prefix beam search.  Nothing to mix the CTC score with (ctc_weight is
-            # ignored), and the frames bound the length (the length ratios are ignored)
+            # ignored), and the frames bound the length (the length ratios are ignored).  With rescore the same search is the
+            # first pass, and ctc_weight mixes its score with the attention decoder's in the second
             assert self.asr.ctc_weight > 0, 'ASR was not trained with CTC decoder'
             if lm_weight > 0 and not lm_config:
                 raise NotImplementedError('RNN-LM fusion for CTC-only decoding is not built into a decoder that names no LM: '
                                           'give lm_config (and lm_path), or construct with lm_weight = 0 and call set_lm(lm, weight)')
             if not 1 <= beam_size <= H.CTC_BEAM_MAX:
-                raise ValueError('CTC-only decoding takes a beam of 1..%d, got %d' % (H.CTC_BEAM_MAX, beam_size))
+                raise ValueError('the CTC prefix beam search (CTC-only decoding, first pass of rescore) takes a beam of 1..%d, got %d'
+                                 % (H.CTC_BEAM_MAX, beam_size))
             self.fast, self.apply_ctc, self.apply_lm = False, True, False
             self.ctc_cand = min(self.asr.vocab_size - 1, int(CTC_BEAM_RATIO * self.beam_size))
-            self.len_bonus = float(len_bonus)         # per-token insertion bonus of the fused score; the CTC-only search alone uses it
+            self.len_bonus = float(len_bonus)         # per-token insertion bonus of the fused score; the CTC search alone uses it
+            if self.rescore:
+                if not 0 <= ctc_weight <= 1:
+                    raise ValueError('rescore mixes (1 - ctc_weight) * attention + ctc_weight * CTC: ctc_weight %r is outside 0..1' % (ctc_weight,))
+                if rescore_rows is not None and rescore_rows < 1:
+                    raise ValueError('rescore_rows = %r: a chunk of the decoder pass holds at least one hypothesis row' % (rescore_rows,))
+                self.ctc_w, self.rescore_rows = float(ctc_weight), rescore_rows
+                self.phase_hook = None                # called with a phase's name when its launches are issued (tools/bench_decode.py)
             if lm_weight > 0:
                 self.set_lm(self._load_lm(lm_config, lm_path), lm_weight)
             return
@@ -217,6 +246,16 @@ class BeamDecoder(nn.Module):
         self.apply_lm, self.lm_w, self.lm = True, weight, lm
 
     def create_msg(self):
+        if self.rescore:
+            msg = ['Decode spec| Two-pass decoding: CTC prefix beam search, then attention rescoring of its n-best list\t| Beam size = {}'
+                   '\t| Tokens extended per frame = {}'.format(self.beam_size, self.ctc_cand),
+                   '           |Rescoring score = (1 - w) * attention + w * CTC \t| ctc_weight w = {:.2f}'.format(self.ctc_w),
+                   '           |Min/Max len ratio are ignored (the frames bound the length)']
+            if self.apply_lm:
+                msg.append('           |LM shallow fusion in the first pass, its terms added unweighted in the second \t| weight = {:.2f}'
+                           '\t| length bonus = {:.2f}'.format(self.lm_w, self.len_bonus))
+            msg.append(encoder_pass_msg(self.asr, self.batch_encode))
+            return msg
         if self.ctc_only:
             msg = ['Decode spec| CTC-only model: CTC prefix beam search\t| Beam size = {}\t| Tokens extended per frame = {}'.format(
                        self.beam_size, self.ctc_cand),
@@ -241,6 +280,8 @@ class BeamDecoder(nn.Module):
     def forward(self, audio_feature, feature_len):
         """audio_feature (U,T,D) zero-padded, feature_len (U).  U == 1: the reference's return value (list of <= beam
         Hypothesis, best first); U > 1: a list of such lists.  No device-to-host copy inside the search loop."""
+        if self.rescore:
+            return self._forward_rescore(audio_feature, feature_len)
         if self.ctc_only:
             return self._forward_ctc(audio_feature, feature_len)
         U = audio_feature.shape[0]
@@ -266,8 +307,24 @@ class BeamDecoder(nn.Module):
         """CTC-only model: one asr_ctc_beam_search launch runs every frame of every utterance; the results are read back
         once, after it.  Returns CTCHypothesis objects in the shape of forward's contract."""
         _, _, tlen, ctc_lp = self._encode(audio_feature, feature_len)
-        if self.apply_lm:
-            return self._forward_ctc_lm(ctc_lp, tlen)
+        return self._read_ctc(self._search_ctc_lm(ctc_lp, tlen) if self.apply_lm else self._search_ctc(ctc_lp, tlen))
+
+    def _forward_ctc_lm(self, ctc_lp, tlen, max_frames=0):
+        """The resumable search on an encoded batch, read back (tools/bench_decode.py times it)."""
+        return self._read_ctc(self._search_ctc_lm(ctc_lp, tlen, max_frames))
+
+    @staticmethod
+    def _read_ctc(res):
+        """The one read-back of a CTC search: CTCHypothesis objects in the shape of forward's contract."""
+        n_c, len_c, tok_c, sc_c = res['n'].cpu(), res['len'].cpu(), res['tokens'].cpu(), res['score'].cpu()
+        cs_c = sc_c if res['ctc_score'] is res['score'] else res['ctc_score'].cpu()
+        U = n_c.shape[0]
+        out = [[CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(sc_c[u, i]), float(cs_c[u, i])) for i in range(int(n_c[u]))]
+               for u in range(U)]
+        return out[0] if U == 1 else out
+
+    def _search_ctc(self, ctc_lp, tlen):
+        """The one-launch search; its result stays on the device: tokens (U,K,T') int32, len (U,K), n (U), score = ctc_score (U,K)."""
         U, Tp, V = ctc_lp.shape
         K, dev = self.beam_size, ctc_lp.device
         toks = torch.empty((U, K, Tp), dtype=torch.int32, device=dev)
@@ -277,12 +334,10 @@ class BeamDecoder(nn.Module):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         H.call('asr_ctc_beam_search', H.ptr(ctc_lp), H.ptr(tlen), U, Tp, V, K, self.ctc_cand, Tp, H.ptr(toks), H.ptr(lens), H.ptr(score),
                H.ptr(n), H.ptr(ws), nbytes, H.stream_ptr())
-        n_c, len_c, tok_c, sc_c = n.cpu(), lens.cpu(), toks.cpu(), score.cpu()
-        out = [[CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(sc_c[u, i])) for i in range(int(n_c[u]))] for u in range(U)]
-        return out[0] if U == 1 else out
+        return {'tokens': toks, 'len': lens, 'n': n, 'score': score, 'ctc_score': score}
 
-    def _forward_ctc_lm(self, ctc_lp, tlen, max_frames=0):
-        """CTC-only model with an LM: the resumable search.  Row u*K + r of the LM table and state belongs to beam slot r of
+    def _search_ctc_lm(self, ctc_lp, tlen, max_frames=0):
+        """The search with an LM: the resumable one.  Row u*K + r of the LM table and state belongs to beam slot r of
         utterance u.  Every asr_ctc_beam_lm_advance launch runs frames until some slot of an utterance is a new prefix (at least
         one frame of every unfinished utterance, so T' launches always suffice), then says per slot which row it inherits
         (src_row), with which token the LM has to step it (step_tok) and whether it is new (need); the glue gathers, steps all
@@ -320,10 +375,78 @@ class BeamDecoder(nn.Module):
         score, ctc_score = torch.empty((U, K), dtype=torch.float32, device=dev), torch.empty((U, K), dtype=torch.float32, device=dev)
         H.call('asr_ctc_beam_lm_readout', U, Tp, K, Tp, H.ptr(toks), H.ptr(lens), H.ptr(score), H.ptr(ctc_score), H.ptr(n), H.ptr(ws),
                nbytes, st)
-        n_c, len_c, tok_c, sc_c, cs_c = n.cpu(), lens.cpu(), toks.cpu(), score.cpu(), ctc_score.cpu()
-        out = [[CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(sc_c[u, i]), float(cs_c[u, i])) for i in range(int(n_c[u]))]
-               for u in range(U)]
+        return {'tokens': toks, 'len': lens, 'n': n, 'score': score, 'ctc_score': ctc_score}
+
+    def _forward_rescore(self, audio_feature, feature_len):
+        """Two passes.  First: the CTC search above on the joint model's CTC log-probs, its n-best list left on the device.
+        Second: asr_rescore_pack makes the teacher table, the encoder output is expanded to one row per hypothesis
+        (asr_gather_rows), the teacher-forced decoder forward ASR.forward uses runs over the rows in chunks, and ONE
+        asr_rescore_nbest launch scores, mixes and ranks.  Host reads: the 4-byte max_len (the decoder's step count is a host
+        integer) before the decoder pass, the results after the last launch.  Returns, per utterance, the first pass's
+        hypotheses (their sequences untouched: the <eos> the scoring appends is not output) in the new order, score = the mixed
+        score, ctc_score as the first pass gave it, att_score the decoder's."""
+        asr, K, st = self.asr, self.beam_size, H.stream_ptr()
+        phase = self.phase_hook or (lambda name: None)
+        enc, enc_len, tlen, ctc_lp = self._encode(audio_feature, feature_len)
+        phase('encoder')
+        first = self._search_ctc_lm(ctc_lp, tlen) if self.apply_lm else self._search_ctc(ctc_lp, tlen)
+        phase('first_pass')
+        U, Tp, E = enc.shape
+        V, dev, R, Lr = asr.vocab_size, enc.device, U * K, Tp + 1
+        i64 = lambda *s_: torch.empty(s_, dtype=torch.int64, device=dev)
+        teacher, row_utt, row_len = i64(R, Lr), i64(R), i64(R)
+        tgt_len, max_len = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        H.call('asr_rescore_pack', H.ptr(first['tokens']), H.ptr(first['len']), H.ptr(first['n']), H.ptr(enc_len), U, K, Tp, Lr, EOS,
+               H.ptr(teacher), H.ptr(tgt_len), H.ptr(row_utt), H.ptr(row_len), H.ptr(max_len), st)
+        L = max(1, int(max_len.item()))
+        rows = self._rescore_chunk_rows(L, Tp)
+        fast = asr.decoder.fast and asr.attention.fast and asr.emb_drop == 0.0        # the choice of ASR.forward
+        ctx = type('C', (), {'anchor': asr._anchor, 'prec': asr.prec, 'next_seed': lambda s: 0})()
+        enc2d = enc.reshape(U, Tp * E)
+        logits = None if rows >= R else torch.empty((R, L, V), dtype=torch.float32, device=dev)
+        was_training = asr.training
+        asr.eval()
+        try:
+            for r0 in range(0, R, rows):
+                r1 = min(R, r0 + rows)
+                enc_rows = torch.empty((r1 - r0, Tp, E), dtype=torch.float32, device=dev)
+                H.call('asr_gather_rows', H.ptr(enc2d), H.ptr(row_utt[r0:r1]), H.ptr(enc_rows), r1 - r0, Tp * E, Tp * E, Tp * E, U, st)
+                if fast:
+                    _, dst = F_hip.att_decoder_forward(asr, enc_rows, row_len[r0:r1], L, teacher[r0:r1], asr.prec)
+                    out = dst['logits']
+                else:
+                    from src.variants import variant_decoder
+                    out, _, _ = variant_decoder(asr, asr._anchor, enc_rows, row_len[r0:r1], L, teacher[r0:r1, :L].contiguous(), 1.0, ctx)
+                    out = out.contiguous()
+                if logits is None:
+                    logits = out
+                else:
+                    logits[r0:r1].copy_(out)
+        finally:
+            asr.train(was_training)
+        phase('decoder_pass')
+        att, total = torch.empty((U, K), dtype=torch.float32, device=dev), torch.empty((U, K), dtype=torch.float32, device=dev)
+        order = torch.empty((U, K), dtype=torch.int32, device=dev)
+        H.call('asr_rescore_nbest', H.ptr(logits), logits.stride(0), logits.stride(1), H.ptr(teacher), Lr, H.ptr(tgt_len),
+               H.ptr(first['ctc_score']), H.ptr(first['score']), H.ptr(first['n']), U, K, L, V, self.ctc_w, H.ptr(att), H.ptr(total),
+               H.ptr(order), st)
+        phase('rescore_launch')
+        n_c, len_c, tok_c = first['n'].cpu(), first['len'].cpu(), first['tokens'].cpu()
+        cs_c, att_c, tot_c, ord_c = first['ctc_score'].cpu(), att.cpu(), total.cpu(), order.cpu()
+        out = []
+        for u in range(U):
+            slots = [int(i) for i in ord_c[u, :int(n_c[u])]]
+            out.append([CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(tot_c[u, i]), float(cs_c[u, i]), float(att_c[u, i]))
+                        for i in slots])
+        phase('read_back')
         return out[0] if U == 1 else out
+
+    def _rescore_chunk_rows(self, L, Tp):
+        """Hypothesis rows one decoder pass of L steps takes: at most RESCORE_MAX_ROWS, its saved state under RESCORE_STATE_BYTES,
+        and no more than rescore_rows when the constructor gave one; never less than one row."""
+        kn = getattr(self.asr.attention.att_layer, 'kernel_num', 1)
+        rows = min(RESCORE_MAX_ROWS, max(1, RESCORE_STATE_BYTES // (4 * L * kn * Tp)))
+        return rows if self.rescore_rows is None else max(1, min(rows, int(self.rescore_rows)))
 
     @torch.no_grad()
     def forward_host(self, audio_feature, feature_len):

@@ -656,6 +656,33 @@ int asr_ctc_beam_lm_advance(const float* logp, const int* tlen, const float* lm_
 int asr_ctc_beam_lm_readout(int U, int Tmax, int K, int Lcap, int* out_tokens, int* out_len, float* out_score,
                             float* out_ctc_score, int* out_n, const void* workspace, size_t workspace_bytes, asr_stream_t stream);
 
+/* Two-pass decoding of a joint model (csrc/rescore.hip): the n-best list of the CTC prefix beam search above, scored by the
+ * attention decoder teacher-forced in one batched pass and re-ranked.  No reference counterpart (the reference has the joint
+ * search of src/decode.py:65-183 only).  Row r = u*K + i is beam slot i of utterance u.
+ *   asr_rescore_pack  : the first pass's result -> the decoder's teacher table.  tokens (U,K,Lcap), len (U,K), n (U) int32 as
+ *     asr_ctc_beam_search / asr_ctc_beam_lm_readout write them; enc_len (U) int64.  teacher (R,Lr) int64 = the hypothesis, `eos`
+ *     appended when its last token is not `eos` already, zero-padded to Lr; tgt_len (R) int32 = the tokens to score (an empty
+ *     hypothesis scores the one `eos`); row_utt (R) int64 = u (the index asr_gather_rows expands the encoder output with);
+ *     row_enc_len (R) int64 = enc_len[u]; max_len (1) int32 = the largest tgt_len.  A slot i >= n[u] is unused: tgt_len 0, an
+ *     all-zero teacher row, row_utt and row_enc_len as its utterance's (a valid row to read).  len is clamped to 0..Lcap.
+ *     Lr >= Lcap + 1 (so no tgt_len exceeds Lr); one workgroup per utterance, every one finds max_len for itself from len and n.
+ *   asr_rescore_nbest : logits fp32, element (r,t,v) at r*row_stride + t*pos_stride + v, both strides >= V (R,L,V of the decoder
+ *     pass); teacher (R,teacher_ld) int64, tgt_len (R) int32 (clamped to 0..L); ctc_score, first_score (U,K) fp32 = the pure CTC
+ *     log-probability and what the first pass ranked by (equal without an LM); n (U) int32.  Writes, all (U,K):
+ *       att_score = sum_{t < tgt_len} log_softmax(logits[r,t,:])[teacher[r,t]]      (fp32, max subtracted, added in order of t)
+ *       total     = (1 - ctc_weight) * att_score + ctc_weight * ctc_score + (first_score - ctc_score)
+ *       order     int32, rank -> slot: descending total, ties to the lower slot; unused slots last, their att_score = total = -inf.
+ *     A -inf logit is legal: a target at -inf (or outside 0..V-1) gives att_score = total = -inf, never NaN.  Nothing at or past
+ *     tgt_len along L or past V along a row is read.  One workgroup per utterance, one wave per slot; the result does not depend
+ *     on U, K or the launch shape.  Any V > 1, L >= 1, 1 <= K <= ASR_CTC_BEAM_MAX.
+ * Null pointers, bad dims, K outside 1..ASR_CTC_BEAM_MAX, Lr < Lcap + 1 and a stride below V return ASR_E_ARG and launch nothing. */
+int asr_rescore_pack(const int* tokens, const int* len, const int* n, const int64_t* enc_len, int U, int K, int Lcap, int Lr,
+                     int eos, int64_t* teacher, int* tgt_len, int64_t* row_utt, int64_t* row_enc_len, int* max_len,
+                     asr_stream_t stream);
+int asr_rescore_nbest(const float* logits, long row_stride, long pos_stride, const int64_t* teacher, long teacher_ld,
+                      const int* tgt_len, const float* ctc_score, const float* first_score, const int* n, int U, int K, int L,
+                      int V, float ctc_weight, float* att_score, float* total, int* order, asr_stream_t stream);
+
 /* CTC forced alignment (csrc/ctc_align.hip): the most probable alignment (Viterbi) of a KNOWN transcript to the CTC
  * log-probabilities - token and word timestamps, cutting long recordings, finding bad transcripts by their score.  No reference
  * counterpart.  ONE launch for all B utterances, one workgroup per utterance, one thread per lattice state; nothing is copied

@@ -3,7 +3,7 @@ RNN-LM of config/librispeech_lm.yaml (4 x LSTM-1024, tied, random weights) with 
 U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Prints one JSON line.
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
        [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
-       [--ctc-only] [--ctc-lm] [--batch-encode] [--lengths equal|librispeech] [--vgg N]
+       [--ctc-only] [--ctc-lm] [--batch-encode] [--lengths equal|librispeech] [--vgg N] [--rescore]
 The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one; --lm-module GRU
 fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one.  --ctc-only decodes the config's
 model built with ctc_weight = 1 (no attention decoder, no LM) by the CTC prefix beam search (csrc/ctc_decode.hip) and also
@@ -16,7 +16,12 @@ the whole decode with the per-utterance encoder pass (the default) and with the 
 (BeamDecoder(batch_encode=True), src/ragged.py): one warm-up each, then the median of --reps runs.  --lengths librispeech
 draws the U lengths from SURVEY 8d's length model clip(N(1270,480),150,2450) instead of --frames for every utterance.  --vgg N
 overrides the yaml's encoder.vgg (0..7: the front-ends of src/vgg.py / src/module.py), so that --batch-encode measures the
-batched pass of a front-end model."""
+batched pass of a front-end model.  --rescore measures, in one process, the joint CTC/attention/LM beam search and two-pass
+decoding of the same model (BeamDecoder(rescore=True): CTC prefix beam search, then attention rescoring of its n-best list,
+csrc/rescore.hip) without and with the LM in the first pass: one warm-up each, then the median of --reps runs, and for the two-pass
+modes one more run with a synchronisation after every phase, which splits the time into encoder, first pass, decoder pass (teacher
+table, the 4-byte read of the step count, row expansion, the teacher-forced decoder forward), rescoring launch and read-back.
+With --batch-encode all three use the length-aware batched encoder pass."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'e2e-asr-pytorch_amd')
@@ -35,7 +40,7 @@ ap.add_argument('--attention-mode'); ap.add_argument('--num-head', type=int); ap
 ap.add_argument('--lm-module', choices=('LSTM', 'GRU'), default='LSTM')
 ap.add_argument('--ctc-only', action='store_true'); ap.add_argument('--ctc-lm', action='store_true')
 ap.add_argument('--batch-encode', action='store_true'); ap.add_argument('--lengths', choices=('equal', 'librispeech'), default='equal')
-ap.add_argument('--vgg', type=int, choices=range(8))
+ap.add_argument('--vgg', type=int, choices=range(8)); ap.add_argument('--rescore', action='store_true')
 a = ap.parse_args()
 torch.manual_seed(0)
 mc = yaml.safe_load(open(a.model_yaml))['model']
@@ -85,6 +90,39 @@ if a.ctc_lm:
                       'search_loop_ms_one_frame_per_launch': med['search_loop_one_frame'], 'advance_launches': launches['search_loop'],
                       'advance_launches_one_frame_per_launch': launches['search_loop_one_frame'],
                       'search_loop_ms_per_advance': med['search_loop'] / launches['search_loop']}))
+    sys.exit(0)
+if a.rescore:
+    import statistics
+    assert not a.ctc_only, '--rescore decodes a joint model: drop --ctc-only'
+    kw = dict(beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio, ctc_weight=0.3, batch_encode=a.batch_encode)
+    dec_j = BeamDecoder(model, None, **kw); dec_j.set_lm(lm, 0.3)
+    dec_r = BeamDecoder(model, None, rescore=True, **kw)
+    dec_rl = BeamDecoder(model, None, rescore=True, **kw); dec_rl.set_lm(lm, 0.3)
+    runs = {'joint_lm': dec_j, 'rescore': dec_r, 'rescore_lm': dec_rl}
+    ts = {k: [] for k in runs}
+    for rep_ in range(1 + a.reps):                     # rep 0 = warm-up: workspaces, packed weights, plans
+        for name, d in runs.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter(); out = d(feat, flen); torch.cuda.synchronize()
+            if rep_: ts[name].append((time.perf_counter() - t0) * 1e3)
+    res = {'metric': 'joint beam search vs two-pass decoding (CTC n-best, attention rescoring), config 4', 'batch_utterances': U,
+           'lengths': a.lengths, 'frames': flen.tolist() if a.lengths != 'equal' else T, 'beam': a.beam, 'prec': a.prec, 'reps': a.reps,
+           'ctc_weight': 0.3, 'lm': '4x1024 tied, %s' % a.lm_module, 'lm_weight': 0.3, 'weights': 'random',
+           'encoder_pass': 'batched' if a.batch_encode else 'per utterance'}
+    for name in runs:
+        ms = statistics.median(ts[name])
+        res[name] = {'decode_ms': ms, 'utterances_per_s': U * 1e3 / ms}
+    for name in ('rescore', 'rescore_lm'):
+        stamps = []
+        def hook(phase):
+            torch.cuda.synchronize(); stamps.append((phase, time.perf_counter()))
+        runs[name].phase_hook = hook
+        torch.cuda.synchronize(); t0 = time.perf_counter(); out = runs[name](feat, flen)
+        runs[name].phase_hook = None
+        res[name]['split_ms'] = {ph: (t - tp) * 1e3 for (ph, t), tp in zip(stamps, [t0] + [t for _, t in stamps[:-1]])}
+        res[name]['hyps_first_utt'] = len(out[0]) if U > 1 else len(out)
+        res[name]['longest_hypothesis'] = max(len(h.outIndex) for hs in (out if U > 1 else [out]) for h in hs)
+    H.raise_if_aborted()
+    print(json.dumps(res))
     sys.exit(0)
 if a.batch_encode:
     import statistics
