@@ -43,7 +43,7 @@ __global__ void ctc_prefix_score_kernel(const float* __restrict__ x, const float
     const int start = max(1, plen);
     for (int t = 0; t < start && t < T; ++t) { ro[2 * t] = LOGZERO; ro[2 * t + 1] = LOGZERO; }
     if (plen == 0) ro[0] = x[tok];
-    float r0 = ro[2 * (start - 1)], r1 = ro[2 * (start - 1) + 1];
+    float r0 = ro[2 * (min(start, T) - 1)], r1 = ro[2 * (min(start, T) - 1) + 1];   // plen > T: stay inside the row, as the batched kernel does
     float psi = r0;
     const bool same = (plen > 0 && tok == last);
     for (int t = start; t < T; ++t) {
@@ -56,7 +56,12 @@ __global__ void ctc_prefix_score_kernel(const float* __restrict__ x, const float
         r0 = n0; r1 = n1;
         ro[2 * t] = r0; ro[2 * t + 1] = r1;
     }
-    if (tok == 1) psi = lae(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);   // <eos>: probability of the prefix itself
+    if (tok == 1) {                                                   // <eos>: probability of the prefix itself
+        psi = lae(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
+        // With no frame left to sweep (plen >= T, or T == 1) the reference's psi is still a view of r[start-1, 0, :], so
+        // its assignment lands in the state as well (src/ctc.py:85, 107); the next step reads it back through r_prev[T-1].
+        if (start >= T) ro[2 * (T - 1)] = psi;
+    }
     psi_out[i] = psi;
 }
 
@@ -367,7 +372,10 @@ __global__ void ctc_prefix_score_batched_kernel(const float* __restrict__ x, con
         r0 = n0; r1 = n1;
         ro[2 * t] = r0; ro[2 * t + 1] = r1;
     }
-    if (tok == 1) psi = lae(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
+    if (tok == 1) {
+        psi = lae(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
+        if (start >= T) ro[2 * (T - 1)] = psi;                           // as in ctc_prefix_score_kernel
+    }
     psi_out[i] = psi;
 }
 
@@ -397,12 +405,13 @@ extern "C" int asr_beam_candidates(const float* att_logp, int* candidates, int r
 }
 
 extern "C" int asr_beam_step(const asr_beam_step_t* a, asr_stream_t stream) {
-    ASR_REQUIRE(a && a->att_logp && a->alive_in && a->sum_in && a->len_in && a->seq_in && a->score_in && a->alive_out && a->sum_out &&
+    // ctcp_in / ctcp_out are read and written in every mode (0 without CTC), so they are required in every mode
+    ASR_REQUIRE(a && a->att_logp && a->alive_in && a->sum_in && a->ctcp_in && a->len_in && a->seq_in && a->score_in && a->alive_out && a->sum_out && a->ctcp_out &&
                 a->len_out && a->seq_out && a->score_out && a->last_token && a->parent && a->ctc_index && a->tokens && a->min_len &&
                 a->max_len && a->done && a->fin_n && a->fin_len && a->fin_avg && a->fin_seq && a->fin_score, ASR_E_ARG, "asr_beam_step: null pointer");
     ASR_REQUIRE(a->U > 0 && a->beam > 0 && a->beam <= BEAM_MAX && a->V > 1 && a->V <= 64 * VPL && a->Lmax > 0 && a->t >= 0, ASR_E_ARG,
                 "asr_beam_step: bad dims (beam <= %d, V <= %d)", BEAM_MAX, 64 * VPL);
-    ASR_REQUIRE((a->psi == nullptr) == (a->candidates == nullptr) && (!a->candidates || (a->C > 0 && a->ctcp_in && a->ctcp_out)), ASR_E_ARG,
+    ASR_REQUIRE((a->psi == nullptr) == (a->candidates == nullptr) && (!a->candidates || a->C > 0), ASR_E_ARG,
                 "asr_beam_step: CTC operands come together");
     BeamP p{a->att_logp, a->lm_logp, a->psi, a->candidates, a->alive_in, a->sum_in, a->ctcp_in, a->len_in, a->seq_in, a->score_in,
             a->alive_out, a->sum_out, a->ctcp_out, a->len_out, a->seq_out, a->score_out, a->last_token, (long long*)a->parent,

@@ -582,7 +582,9 @@ int asr_masked_copy_rows(const float* src, const int* mask, float* dst, int rows
  *       (:179-183, incl. the survivors when t+1 reaches max_len[u], and the beam-1 early return).  State is double
  *       buffered (in -> out); outputs for the next step: last_token (rows), parent (rows: source row of each new row),
  *       ctc_index (rows: parent*C + candidate slot, row index into r_out viewed (N*C, Tmax*2)), and column t+1 of the
- *       decoder's token table.  beam <= 16, V <= 2048, one wave per utterance. */
+ *       decoder's token table.  beam <= 16, V <= 2048, one wave per utterance.  Every pointer but lm_logp, psi and
+ *       candidates is required (ctcp_in / ctcp_out too without CTC: they are read and written as 0); psi and candidates come
+ *       together; anything else returns ASR_E_ARG and launches nothing. */
 typedef struct {
     const float *att_logp, *lm_logp, *psi;  /* (R,V); (R,V) or NULL; (R,C) or NULL */
     const int* candidates;                  /* (R,C) or NULL */

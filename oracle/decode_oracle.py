@@ -24,23 +24,26 @@ CTC_BEAM_RATIO = 1.5            # src/decode.py:10
 
 
 # ---- CTC prefix scores (src/ctc.py) ----------------------------------------------------------------------------------
-def ctc_prefix_init(x):
-    """x (T, V) log-probs -> r (T, 2): r[:, 0] = log zero (non-blank), r[t, 1] = cumulative blank log-prob."""
+def ctc_prefix_init(x, dtype=np.float32):
+    """x (T, V) log-probs -> r (T, 2): r[:, 0] = log zero (non-blank), r[t, 1] = cumulative blank log-prob.  `dtype`: the
+    arithmetic (float32 is the reference's; float64 serves tests/test_beam_step_reference.py as the yardstick)."""
+    x = np.asarray(x, dtype=dtype)
     T = x.shape[0]
-    r = np.full((T, 2), LOGZERO_CTC, dtype=np.float32)
+    r = np.full((T, 2), LOGZERO_CTC, dtype=dtype)
     r[0, 1] = x[0, 0]
     for i in range(1, T):
         r[i, 1] = r[i - 1, 1] + x[i, 0]
     return r
 
 
-def ctc_prefix_cheap(x, g, r_prev, candidates):
+def ctc_prefix_cheap(x, g, r_prev, candidates, dtype=np.float32):
     """Prefix g (list of ints), previous state r_prev (T, 2), candidate tokens -> (psi (C,), r (C, T, 2)).  float32 numpy as the
-    reference computes it (np.logaddexp on float32 arrays)."""
+    reference computes it (np.logaddexp on float32 arrays) unless another `dtype` is asked for."""
+    x, r_prev = np.asarray(x, dtype=dtype), np.asarray(r_prev, dtype=dtype)
     T = x.shape[0]
     C = len(candidates)
     last = g[-1] if len(g) > 0 else 0
-    r = np.full((T, 2, C), LOGZERO_CTC, dtype=np.float32)
+    r = np.full((T, 2, C), LOGZERO_CTC, dtype=dtype)
     start = max(1, len(g))
     if len(g) == 0:
         r[0, 0, :] = x[0, candidates]
@@ -85,8 +88,10 @@ class Hyp(object):
 
 
 def beam_search(feat, feat_len, P, cfg, beam_size, min_len_ratio, max_len_ratio, ctc_weight=0.0, lm=None, lm_weight=0.0,
-                eos_threshold=1.5):
-    """feat (1, T, D), feat_len (1,).  lm: None or (P_lm, lm_cfg).  Returns the reference's list: [(tokens, scores)] best first."""
+                eos_threshold=1.5, trace=None):
+    """feat (1, T, D), feat_len (1,).  lm: None or (P_lm, lm_cfg).  Returns the reference's list: [(tokens, scores)] best first.
+    trace: None, or a list that receives one (t, tuple(seq), att_prob, cand, ctc_prob, lm_logp) per hypothesis expansion - the
+    tables the bookkeeping of that expansion read (cand / ctc_prob / lm_logp are None where the mode has none)."""
     with torch.no_grad():
         enc, enc_len = O.encoder(feat, feat_len, P, cfg)
         Tp = enc.shape[1]
@@ -130,10 +135,13 @@ def beam_search(feat, feat_len, P, cfg, beam_size, min_len_ratio, max_len_ratio,
                         hack[0, ch] = ctc_char[i]
                     cur = (1 - ctc_weight) * cur + ctc_weight * hack
                     cur[0, 0] = LOG_ZERO
-                lm_state = None
+                lm_state, lm_logp = None, None
                 if lm is not None and lm_weight > 0:
                     lm_out, lm_state = rnnlm_step(lm[0], lm[1], tok, hyp.lm_state)
-                    cur = cur + lm_weight * F.log_softmax(lm_out, dim=-1)
+                    lm_logp = F.log_softmax(lm_out, dim=-1)
+                    cur = cur + lm_weight * lm_logp
+                if trace is not None:
+                    trace.append((t, tuple(hyp.seq), att_prob, cand, ctc_prob, lm_logp))
                 topv, topi = cur[0].topk(beam_size)
                 # Hypothesis.addTopk (src/decode.py:214-263)
                 new, term = [], None
