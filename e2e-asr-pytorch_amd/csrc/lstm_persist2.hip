@@ -20,6 +20,8 @@
 //    and move the bulk traffic (saved gates / c / y stores, operand prefetch three steps ahead).  vmcnt retires
 //    in issue order, so a poll that shares a wave with bulk stores is not seen before those have completed.
 // Hand-off, bounded spins and the abort word are as in lstm_persist.hip (guide form R2).
+// The phases this file shares with lstm_persist3.hip (forward gather, granule packing, coefficients and cell backward, partial
+// products, the NKS / NTO class lists) are stated once in lstm_persist_common.h.
 #include "common.h"
 #include <stdlib.h>
 #include "handoff.h"
@@ -87,31 +89,18 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
     if (tid >= 256) {
         // ---- gather role ----
         const int gt = tid - 256;
-        const int HG2 = HG >> 1, total2 = B * HG2;              // 16-byte pairs per row / in all
-        int slot_off[CH], cnt = 0;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int idx = gt + 256 * i;
-            slot_off[i] = (idx < total2) ? (idx / HG2) * LD + (idx % HG2) * 8 : -1;
-            if (idx < total2) cnt = i + 1;
-        }
+        int slot_off[CH];
+        const int cnt = fwd_gather_slots<CH>(slot_off, gt, B, HG >> 1, LD);
         LSTM_DIAG_DECL
         for (int s = 0; s < T; ++s) {
             __bf16* tile = tiles + (s & 1) * 16 * LD;
             if (s > 0 && cnt > 0) {
                 u64 glo[CH], ghi[CH];
-                for (int z = 0; z < p.poll_delay; ++z) __builtin_amdgcn_s_sleep(2);
                 const u64* src = p.xbuf + ((long)((s - 1) & 1) * ND + d) * xregion + 2 * gt;
-                const int sp = gather16<CH>(src, 512, cnt, FWD_MASK, fwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
+                const int sp = fwd_gather_poll<CH>(src, cnt, p.poll_delay, fwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
                 LSTM_DIAG_MARK(0)
                 LSTM_DIAG_COUNT(7, sp)
-#pragma unroll
-                for (int i = 0; i < CH; ++i)
-                    if (slot_off[i] >= 0) {
-                        u64* dst = reinterpret_cast<u64*>(tile + slot_off[i]);
-                        dst[0] = glo[i] & ~FWD_MASK;
-                        dst[1] = ghi[i] & ~FWD_MASK;
-                    }
+                fwd_gather_store<CH>(tile, slot_off, glo, ghi);
             }
             LSTM_DIAG_MARK(1)
             __syncthreads();
@@ -194,11 +183,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_p2(P2 p) {
             cst.z = gf.z * cst.z + gi.z * gg.z; cst.w = gf.w * cst.w + gi.w * gg.w;
             const float4 o_h = make_float4(go.x * tanh_f(cst.x), go.y * tanh_f(cst.y), go.z * tanh_f(cst.z), go.w * tanh_f(cst.w));
             if (s + 1 < T && bok) {
-                // bit 14 of a bf16 is clear for every |x| < 2; clearing it (only NaN/Inf are affected, and those
-                // still reach the loss through y) keeps the sequence bits (bits 14 and 30 of the granule) intact
-                const u64 b0 = f2bf_bits(o_h.x) & 0xBFFFu, b1 = f2bf_bits(o_h.y) & 0xBFFFu;
-                const u64 b2 = f2bf_bits(o_h.z) & 0xBFFFu, b3 = f2bf_bits(o_h.w) & 0xBFFFu;
-                const u64 v = b0 | (b1 << 16) | (b2 << 32) | (b3 << 48);
+                const u64 v = h_granule(h_bits(o_h.x), h_bits(o_h.y), h_bits(o_h.z), h_bits(o_h.w));
                 u64* dst = p.xbuf + ((long)(s & 1) * ND + d) * xregion + n * HG + (u0 >> 2) + q;
                 if (local) publish<true>(dst, v | fwd_want(seq_of(s), p.epoch));
                 else publish<false>(dst, v | fwd_want(seq_of(s), p.epoch));
@@ -260,23 +245,16 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
         LSTM_DIAG_DECL
         for (int s = 0; s < T; ++s) {
             if (s > 0) {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+                float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (gb < B && cntp > 0) {
                     for (int z = 0; z < p.poll_delay; ++z) __builtin_amdgcn_s_sleep(2);
                     const u64* src = p.xbuf + (long)((s - 1) & 1) * per_par + (((long)d * P + me) * P + pp_lo) * B * 8 + gb * 8 + 2 * g4;
                     u64 glo[NTO], ghi[NTO];
                     gather16<NTO>(src, (long)B * 8, cntp, BWD_MASK, bwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
-#pragma unroll
-                    for (int i = 0; i < NTO; ++i)
-                        if (i < cntp) {
-                            a0 += __uint_as_float((unsigned)glo[i] & ~7u);
-                            a1 += __uint_as_float((unsigned)(glo[i] >> 32) & ~7u);
-                            a2 += __uint_as_float((unsigned)ghi[i] & ~7u);
-                            a3 += __uint_as_float((unsigned)(ghi[i] >> 32) & ~7u);
-                        }
+                    a = bwd_sum_partials<NTO>(glo, ghi, cntp);
                 }
                 LSTM_DIAG_MARK(0)
-                *reinterpret_cast<float4*>(s_part + gq * 256 + gb * 16 + 4 * g4) = make_float4(a0, a1, a2, a3);
+                *reinterpret_cast<float4*>(s_part + gq * 256 + gb * 16 + 4 * g4) = a;
             }
             LSTM_DIAG_MARK(1)
             __syncthreads();
@@ -338,21 +316,9 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
         }
         return r;
     };
-    struct Coef { float dy, c1, c2, c3, c4, c5, f; };
-    auto make_coef = [&](const Raw& r) -> Coef {
-        const float tc = tanh_f(r.c);
-        Coef k;
-        k.dy = r.dy;
-        k.c1 = r.go * (1.f - tc * tc);          // d c / d h
-        k.c2 = r.gg * r.gi * (1.f - r.gi);      // d i_pre / d c
-        k.c3 = r.cp * r.gf * (1.f - r.gf);      // d f_pre / d c
-        k.c4 = r.gi * (1.f - r.gg * r.gg);      // d g_pre / d c
-        k.c5 = tc * r.go * (1.f - r.go);        // d o_pre / d h
-        k.f = r.gf;
-        return k;
-    };
+    auto coef_of = [&](const Raw& r) -> Coef { return make_coef(r.dy, r.gi, r.gf, r.gg, r.go, r.c, r.cp); };
 
-    Coef coef = make_coef(load_raw(0));
+    Coef coef = coef_of(load_raw(0));
     Raw rawB = load_raw(1);
     Raw rawC = load_raw(2);
     float carry = 0.f;
@@ -366,10 +332,10 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
         float dgv[4];
         {
             float dh = coef.dy;
-            if (s > 0) dh += (s_part[tid] + s_part[256 + tid]) + (s_part[512 + tid] + s_part[768 + tid]);
-            const float dc = dh * coef.c1 + carry;
-            dgv[0] = dc * coef.c2; dgv[1] = dc * coef.c3; dgv[2] = dc * coef.c4; dgv[3] = dh * coef.c5;
-            carry = dc * coef.f;
+            if (s > 0) dh += s_part_sum(s_part, tid);
+            const CellGrad cg = cell_bwd(coef, dh, carry);
+            dgv[0] = cg.d0; dgv[1] = cg.d1; dgv[2] = cg.d2; dgv[3] = cg.d3;
+            carry = cg.carry;
             if (eok) {
                 tile[eb * LD + ej] = (__bf16)dgv[0];
                 tile[eb * LD + 16 + ej] = (__bf16)dgv[1];
@@ -388,20 +354,16 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
             const u64 want = bwd_want(seq_of(s), p.epoch);
             f32x4 acc[NTO];
 #pragma unroll
-            for (int ot = 0; ot < NTO; ++ot) {
-                acc[ot] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                acc[ot] = mma16(w[ot][0], b0, acc[ot]);
-                acc[ot] = mma16(w[ot][1], b1, acc[ot]);
-            }
+            for (int ot = 0; ot < NTO; ++ot) acc[ot] = bwd_partial(w[ot][0], w[ot][1], b0, b1);
 #pragma unroll
             for (int ot = 0; ot < NTO; ++ot) {
                 const int tcol = wave + 4 * ot;
                 if (tcol < P && n < B) {
                     u64* o = dst + (((long)tcol * P + me) * B + n) * 8 + 2 * q;
-                    const u64 v0 = (u64)(__float_as_uint(acc[ot][0]) & ~7u) | ((u64)(__float_as_uint(acc[ot][1]) & ~7u) << 32);
-                    const u64 v1 = (u64)(__float_as_uint(acc[ot][2]) & ~7u) | ((u64)(__float_as_uint(acc[ot][3]) & ~7u) << 32);
-                    if (local) { publish<true>(o, v0 | want); publish<true>(o + 1, v1 | want); }
-                    else { publish<false>(o, v0 | want); publish<false>(o + 1, v1 | want); }
+                    u64 v0, v1;
+                    bwd_granules(acc[ot], want, v0, v1);
+                    if (local) { publish<true>(o, v0); publish<true>(o + 1, v1); }
+                    else { publish<false>(o, v0); publish<false>(o + 1, v1); }
                 }
             }
         }
@@ -411,7 +373,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
             float* gp = ge + (long)tix(s) * g_ts;
             gp[0] = dgv[0]; gp[H] = dgv[1]; gp[2 * (long)H] = dgv[2]; gp[3 * (long)H] = dgv[3];
         }
-        coef = make_coef(rawB);
+        coef = coef_of(rawB);
         rawB = rawC;
         rawC = load_raw(s + 3);
         LSTM_DIAG_MARK(4)
@@ -419,10 +381,6 @@ __global__ __launch_bounds__(512) void lstm_bwd_p2(P2 p) {
     LSTM_DIAG_DUMP(0, 2)
 }
 
-int poll_delay(bool bwd) {
-    static const int d[2] = {env_int("ASR_LSTM_POLL_DELAY_FWD", POLL_DELAY_FWD), env_int("ASR_LSTM_POLL_DELAY_BWD", POLL_DELAY_BWD)};
-    return d[bwd];
-}
 unsigned next_epoch() { static unsigned e = 1; return e++; }
 
 }  // namespace
@@ -444,9 +402,10 @@ int lstm_persistent2(float* gates, const float* whh, const float* bias2, float* 
                      int B, int T, int H, int ND, void* ws, hipStream_t st) {
     hipMemsetAsync(ws, 0, lstm_gen2_pass(B, H, ND, true, bwd).bytes, st);
     const P2 p{gates, whh, bwd ? nullptr : bias2, y, c, (u64*)((char*)ws + 256), (unsigned*)ws, B, T, H, ND, H / 16,
-               xcd_local_allowed(), poll_delay(bwd), next_epoch()};
+               xcd_local_allowed(),
+               poll_delays("ASR_LSTM_POLL_DELAY_FWD", "ASR_LSTM_POLL_DELAY_BWD", POLL_DELAY_FWD, POLL_DELAY_BWD, bwd), next_epoch()};
     const int nks = (H + 31) / 32, nto = (p.P + 3) / 4;
-    if (bwd) { BWD2_CASE(1) BWD2_CASE(2) BWD2_CASE(3) BWD2_CASE(4) BWD2_CASE(5) BWD2_CASE(6) BWD2_CASE(8) }
-    else { FWD2_CASE(1) FWD2_CASE(2) FWD2_CASE(4) FWD2_CASE(6) FWD2_CASE(8) FWD2_CASE(10) FWD2_CASE(12) FWD2_CASE(16) }
+    if (bwd) { LSTM_G23_NTO(BWD2_CASE) }
+    else { LSTM_G23_NKS(FWD2_CASE) }
     ASR_REQUIRE(false, ASR_E_UNSUPPORTED, "asr_lstm_%s(persistent v2): no kernel for H=%d", bwd ? "bwd" : "fwd", H);
 }

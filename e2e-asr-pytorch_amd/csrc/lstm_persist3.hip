@@ -20,6 +20,8 @@
 //  * the launch epoch of the tags is extended by rotating the exchange region of a caller-owned, persistent workspace
 //    (see asr_hip.h): a (region, tag) pair repeats only every 32 (forward) / 32 (backward) launches of that workspace.
 // Hand-off primitives, bounded spins and the abort word: handoff.h (guide form R2).
+// The phases this file shares with lstm_persist2.hip (forward gather, granule packing, coefficients and cell backward, partial
+// products, the NKS / NTO class lists) are stated once in lstm_persist_common.h.
 #include "common.h"
 #include <stdlib.h>
 #include "handoff.h"
@@ -104,30 +106,17 @@ __global__ __launch_bounds__(512) void lstm_fwd_p3(P3 p) {
     if (tid >= 256) {
         // ---- gather role ----
         const int gt = tid - 256;
-        const int HG2 = HG >> 1, total2 = nb * HG2;             // 16-byte pairs per row / in all (rows are contiguous)
-        int slot_off[CH], cnt = 0;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int idx = gt + 256 * i;
-            slot_off[i] = (idx < total2) ? (idx / HG2) * LD + (idx % HG2) * 8 : -1;
-            if (idx < total2) cnt = i + 1;
-        }
+        int slot_off[CH];
+        const int cnt = fwd_gather_slots<CH>(slot_off, gt, nb, HG >> 1, LD);       // the slice's rows are contiguous
         LSTM_DIAG_DECL
         for (int s = 0; s < T; ++s) {
             __bf16* tile = tiles + (s & 1) * 16 * LD;
             if (s > 0 && cnt > 0) {
                 u64 glo[CH], ghi[CH];
-                for (int z = 0; z < p.poll_delay; ++z) __builtin_amdgcn_s_sleep(2);
                 const u64* src = xg + (long)((s - 1) & 1) * 16 * HG + 2 * gt;
-                gather16<CH>(src, 512, cnt, FWD_MASK, fwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
+                fwd_gather_poll<CH>(src, cnt, p.poll_delay, fwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
                 LSTM_DIAG_MARK(0)
-#pragma unroll
-                for (int i = 0; i < CH; ++i)
-                    if (slot_off[i] >= 0) {
-                        u64* dst = reinterpret_cast<u64*>(tile + slot_off[i]);
-                        dst[0] = glo[i] & ~FWD_MASK;
-                        dst[1] = ghi[i] & ~FWD_MASK;
-                    }
+                fwd_gather_store<CH>(tile, slot_off, glo, ghi);
             }
             LSTM_DIAG_MARK(1)
             __syncthreads();
@@ -202,12 +191,11 @@ __global__ __launch_bounds__(512) void lstm_fwd_p3(P3 p) {
         cst = gf * cst + gi * gg;                                                                                           \
         const float hv = go * tanh_f(cst);                                                                                 \
         LSTM_DIAG_MARK(1)                                                                                                       \
-        /* the wave's four units of batch row n sit in lanes n, n+16, n+32, n+48: collect them in lane n                    \
-           (bit 14 of a bf16 is clear for |x| < 2; clearing it keeps the tag bits of the granule intact) */                 \
-        const unsigned hb16 = f2bf_bits(hv) & 0xBFFFu;                                                                      \
+        /* the wave's four units of batch row n sit in lanes n, n+16, n+32, n+48: collect them in lane n */                 \
+        const unsigned hb16 = h_bits(hv);                                                                                   \
         const unsigned h1 = __shfl(hb16, n + 16), h2 = __shfl(hb16, n + 32), h3 = __shfl(hb16, n + 48);                      \
         if (q == 0 && bok) {                                                                                                \
-            const u64 v = (u64)hb16 | ((u64)h1 << 16) | ((u64)h2 << 32) | ((u64)h3 << 48);                                   \
+            const u64 v = h_granule(hb16, h1, h2, h3);                                                                      \
             if (s + 1 < T) {                                                                                                \
                 u64* dst = xg + ((long)(s & 1) * 16 + n) * HG + (u0 >> 2) + w;                                              \
                 if (local) publish<true>(dst, v | fwd_want(seq_of(s), p.epoch));                                           \
@@ -277,23 +265,16 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
         LSTM_DIAG_DECL
         for (int s = 0; s < T; ++s) {
             if (s > 0) {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+                float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (gb < nb && cntp > 0) {
                     for (int z = 0; z < p.poll_delay; ++z) __builtin_amdgcn_s_sleep(2);
                     const u64* src = xg + (long)((s - 1) & 1) * per_par + (((long)me * P + pp_lo) * BS + gb) * 8 + 2 * g4;
                     u64 glo[NTO], ghi[NTO];
                     gather16<NTO>(src, (long)BS * 8, cntp, BWD_MASK, bwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
-#pragma unroll
-                    for (int i = 0; i < NTO; ++i)
-                        if (i < cntp) {
-                            a0 += __uint_as_float((unsigned)glo[i] & ~7u);
-                            a1 += __uint_as_float((unsigned)(glo[i] >> 32) & ~7u);
-                            a2 += __uint_as_float((unsigned)ghi[i] & ~7u);
-                            a3 += __uint_as_float((unsigned)(ghi[i] >> 32) & ~7u);
-                        }
+                    a = bwd_sum_partials<NTO>(glo, ghi, cntp);
                 }
                 LSTM_DIAG_MARK(0)
-                *reinterpret_cast<float4*>(s_part + gq * 256 + gb * 16 + 4 * g4) = make_float4(a0, a1, a2, a3);
+                *reinterpret_cast<float4*>(s_part + gq * 256 + gb * 16 + 4 * g4) = a;
             }
             LSTM_DIAG_MARK(1)
             __syncthreads();
@@ -362,26 +343,16 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
         }
         return r;
     };
-    struct Coef { float dy, c1, c2, c3, c4, c5, f; };
-    auto make_coef = [&](const Raw& r) -> Coef {
+    auto coef_of = [&](const Raw& r) -> Coef {
         const float gi = bf2f((unsigned short)(r.g.x & 0xFFFFu)), gf = bf2f((unsigned short)(r.g.x >> 16));
         const float gg = bf2f((unsigned short)(r.g.y & 0xFFFFu)), go = bf2f((unsigned short)(r.g.y >> 16));
-        const float tc = tanh_f(r.c);
-        Coef k;
-        k.dy = bf2f((unsigned short)r.dy);
-        k.c1 = go * (1.f - tc * tc);          // d c / d h
-        k.c2 = gg * gi * (1.f - gi);          // d i_pre / d c
-        k.c3 = (r.cp * r.cpm) * gf * (1.f - gf);   // d f_pre / d c
-        k.c4 = gi * (1.f - gg * gg);          // d g_pre / d c
-        k.c5 = tc * go * (1.f - go);          // d o_pre / d h
-        k.f = gf;
-        return k;
+        return make_coef(bf2f((unsigned short)r.dy), gi, gf, gg, go, r.c, r.cp * r.cpm);
     };
 
     // operands four steps ahead in FOUR NAMED register sets, time loop unrolled by four (no register rotation: see
     // lstm_fwd_p3); the coefficients of step s+1 are formed at the end of step s, off the hand-off's critical path
     Raw raw0 = load_raw(0), raw1 = load_raw(1), raw2 = load_raw(2), raw3 = load_raw(3);
-    Coef coef = make_coef(raw0);
+    Coef coef = coef_of(raw0);
     float carry = 0.f;
     LSTM_DIAG_DECL
     int s = 0;
@@ -395,12 +366,11 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
         uint2 dg16;                                                                                                         \
         {                                                                                                                   \
             float dh = coef.dy;                                                                                             \
-            if (s > 0) dh += (s_part[tid] + s_part[256 + tid]) + (s_part[512 + tid] + s_part[768 + tid]);                    \
-            const float dc = dh * coef.c1 + carry;                                                                          \
-            const float d0 = dc * coef.c2, d1 = dc * coef.c3, d2 = dc * coef.c4, d3 = dh * coef.c5;                          \
-            carry = dc * coef.f;                                                                                            \
-            dg16.x = (unsigned)f2bf_bits(d0) | ((unsigned)f2bf_bits(d1) << 16);                                             \
-            dg16.y = (unsigned)f2bf_bits(d2) | ((unsigned)f2bf_bits(d3) << 16);                                             \
+            if (s > 0) dh += s_part_sum(s_part, tid);                                                                       \
+            const CellGrad cg = cell_bwd(coef, dh, carry);                                                                  \
+            carry = cg.carry;                                                                                               \
+            dg16.x = (unsigned)f2bf_bits(cg.d0) | ((unsigned)f2bf_bits(cg.d1) << 16);                                       \
+            dg16.y = (unsigned)f2bf_bits(cg.d2) | ((unsigned)f2bf_bits(cg.d3) << 16);                                       \
             if (eok) *reinterpret_cast<uint2*>(tile + eb * LD + 4 * ej) = dg16;      /* LDS */                              \
         }                                                                                                                   \
         LSTM_DIAG_MARK(1)                                                                                                       \
@@ -413,25 +383,21 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
             u64* dst = xg + (long)(s & 1) * per_par;                                                                        \
             const u64 want = bwd_want(seq_of(s), p.epoch);                                                                 \
             f32x4 acc[NTO];                                                                                                 \
-            _Pragma("unroll") for (int ot = 0; ot < NTO; ++ot) {                                                            \
-                acc[ot] = (f32x4){0.f, 0.f, 0.f, 0.f};                                                                      \
-                acc[ot] = mma16(wreg[ot][0], bq0, acc[ot]);                                                                 \
-                acc[ot] = mma16(wreg[ot][1], bq1, acc[ot]);                                                                 \
-            }                                                                                                               \
+            _Pragma("unroll") for (int ot = 0; ot < NTO; ++ot) acc[ot] = bwd_partial(wreg[ot][0], wreg[ot][1], bq0, bq1);    \
             _Pragma("unroll") for (int ot = 0; ot < NTO; ++ot) {                                                            \
                 const int tcol = wave + 4 * ot;                                                                             \
                 const bool pok = tcol < P && n < nb && s + 1 < T;                                                           \
                 u64* o = dst + (((long)min(tcol, P - 1) * P + me) * BS + min(n, BS - 1)) * 8 + 2 * q;                         \
                 const unsigned off = pok ? (unsigned)(reinterpret_cast<unsigned char*>(o) - reinterpret_cast<unsigned char*>(p.xbuf)) : dump_off; \
-                const u64 v0 = ((u64)(__float_as_uint(acc[ot][0]) & ~7u) | ((u64)(__float_as_uint(acc[ot][1]) & ~7u) << 32)) | want; \
-                const u64 v1 = ((u64)(__float_as_uint(acc[ot][2]) & ~7u) | ((u64)(__float_as_uint(acc[ot][3]) & ~7u) << 32)) | want; \
+                u64 v0, v1;                                                                                                 \
+                bwd_granules(acc[ot], want, v0, v1);                                                                        \
                 publish_pair(xrsrc, off, v0, v1, local);                                                                    \
             }                                                                                                               \
         }                                                                                                                   \
         LSTM_DIAG_MARK(3)                                                                                                       \
         /* gradients wrt the gate pre-activations replace the saved gates; next coefficients; operands four steps ahead */  \
         *(eok ? reinterpret_cast<uint2*>(ge + (long)tix(s) * g_ts) : reinterpret_cast<uint2*>(dump_wg + tid * 16)) = dg16;    \
-        coef = make_coef(RNEXT);                                                                                            \
+        coef = coef_of(RNEXT);                                                                                              \
         RCUR = load_raw(s + 4);                                                                                             \
         LSTM_DIAG_MARK(4)                                                                                                       \
         if (++s >= T) break;                                                                                                \
@@ -440,11 +406,6 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
     for (;;) { BWD3_STEP(raw0, raw1) BWD3_STEP(raw1, raw2) BWD3_STEP(raw2, raw3) BWD3_STEP(raw3, raw0) }
 #undef BWD3_STEP
     LSTM_DIAG_DUMP(0, 64)
-}
-
-int poll_delay3(bool bwd) {
-    static const int d[2] = {env_int("ASR_LSTM3_POLL_DELAY_FWD", 6), env_int("ASR_LSTM3_POLL_DELAY_BWD", 4)};
-    return d[bwd];
 }
 
 size_t fwd3_region_bytes(int H) { return (size_t)8 * 2 * 16 * (H / 4) * sizeof(u64); }
@@ -479,7 +440,8 @@ bool make_p3(P3& p, unsigned short* gates, const float* whh, unsigned short* y, 
     unsigned* hdr = (unsigned*)((char*)ws + (size_t)(epoch & 1u) * HDR_BYTES);
     unsigned* hdr_next = (unsigned*)((char*)ws + (size_t)((epoch + 1u) & 1u) * HDR_BYTES);
     u64* region = (u64*)((char*)ws + HDR_SLOTS * HDR_BYTES + (size_t)rot * rbytes);
-    p = P3{gates, whh, y, c, region, hdr, hdr_next, B, T, H, ND, H / 16, 8 / ND, BS, xcd_local_allowed(), poll_delay3(bwd), epoch,
+    p = P3{gates, whh, y, c, region, hdr, hdr_next, B, T, H, ND, H / 16, 8 / ND, BS, xcd_local_allowed(),
+           poll_delays("ASR_LSTM3_POLL_DELAY_FWD", "ASR_LSTM3_POLL_DELAY_BWD", 6, 4, bwd), epoch,
            bwd ? (unsigned char*)region + rbytes - bwd3_dump_bytes(H) : nullptr, bwd ? (unsigned)rbytes : 0u};
     return true;
 }
@@ -517,7 +479,7 @@ int lstm_persistent3(unsigned short* gates, const float* whh, unsigned short* y,
     P3 p;
     if (!make_p3(p, gates, whh, y, c, B, T, H, ND, ws, ws_bytes, epoch, bwd)) return 1;
     const int nks = (H + 31) / 32, nto = (p.P + 3) / 4;
-    if (bwd) { BWD3_CASE(1) BWD3_CASE(2) BWD3_CASE(3) BWD3_CASE(4) BWD3_CASE(5) BWD3_CASE(6) BWD3_CASE(8) }
-    else { FWD3_CASE(1) FWD3_CASE(2) FWD3_CASE(4) FWD3_CASE(6) FWD3_CASE(8) FWD3_CASE(10) FWD3_CASE(12) FWD3_CASE(16) }
+    if (bwd) { LSTM_G23_NTO(BWD3_CASE) }
+    else { LSTM_G23_NKS(FWD3_CASE) }
     return 1;
 }

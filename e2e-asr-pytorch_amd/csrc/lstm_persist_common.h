@@ -1,5 +1,6 @@
 // What the persistent LSTM recurrence kernels share (lstm_persist.hip, lstm_persist2.hip, lstm_persist3.hip): granule tags,
-// the diagnostic / jitter macros of the time loops and the checked launch.  Include after handoff.h.
+// the diagnostic / jitter macros of the time loops, the checked launch, and the phases and class lists common to generations
+// 2 and 3.  Include after handoff.h.
 // Everything here is `static` per translation unit.
 #pragma once
 #include "handoff.h"
@@ -54,12 +55,115 @@ __device__ __forceinline__ u64 bwd_want(unsigned seq, unsigned epoch) {
     return (u64)(tag & 7u) | ((u64)(tag >> 3) << 32);
 }
 
+// ---- phases of generations 2 and 3 --------------------------------------------------------------------------------------
+// lstm_persist2.hip and lstm_persist3.hip differ in who owns which rows, in the order of the gate index and in the storage
+// type; the straight-line bodies between the marks and barriers of their time loops are the same and stand here once.  Marks,
+// barriers, the loops, the loads of the resident weights and of a step's operands and every bulk store stay in the kernels.
+// forward gather: thread gt of 256 takes the 16-byte granule pairs gt, gt + 256, ... of `rows` contiguous rows of HG2 pairs;
+// slot_off = where a pair lands in the operand tile (row stride LD bf16), -1 beyond the end.  Returns the number of pairs.
+template <int CH>
+__device__ __forceinline__ int fwd_gather_slots(int (&slot_off)[CH], int gt, int rows, int HG2, int LD) {
+    const int total2 = rows * HG2;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int idx = gt + 256 * i;
+        slot_off[i] = (idx < total2) ? (idx / HG2) * LD + (idx % HG2) * 8 : -1;
+        if (idx < total2) cnt = i + 1;
+    }
+    return cnt;
+}
+// one step's poll of this thread's pairs (src + 512 i) after the start-of-step sleep; returns the polling rounds it took
+template <int CH>
+__device__ __forceinline__ int fwd_gather_poll(const u64* src, int cnt, int poll_delay, u64 want, u64 (&glo)[CH], u64 (&ghi)[CH], unsigned* abort_flag) {
+    for (int z = 0; z < poll_delay; ++z) __builtin_amdgcn_s_sleep(2);
+    return gather16<CH>(src, 512, cnt, FWD_MASK, want, glo, ghi, abort_flag);
+}
+// ... and the polled pairs, tags stripped, into the operand tile
+template <int CH>
+__device__ __forceinline__ void fwd_gather_store(__bf16* tile, const int (&slot_off)[CH], const u64 (&glo)[CH], const u64 (&ghi)[CH]) {
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+        if (slot_off[i] >= 0) {
+            u64* dst = reinterpret_cast<u64*>(tile + slot_off[i]);
+            dst[0] = glo[i] & ~FWD_MASK;
+            dst[1] = ghi[i] & ~FWD_MASK;
+        }
+}
+
+// forward granule payload: bit 14 of a bf16 is clear for every |x| < 2; clearing it (only NaN/Inf are affected, and those
+// still reach the loss through y) keeps the tag bits of the granule intact.  The publisher ORs fwd_want() in.
+__device__ __forceinline__ unsigned h_bits(float h) { return f2bf_bits(h) & 0xBFFFu; }
+__device__ __forceinline__ u64 h_granule(unsigned b0, unsigned b1, unsigned b2, unsigned b3) {
+    return (u64)b0 | ((u64)b1 << 16) | ((u64)b2 << 32) | ((u64)b3 << 48);
+}
+
+// backward gather: the four partial sums of `cntp` polled producers' pairs, in producer order.  The sleep and the poll stay
+// in the kernels: moved in here, the polling loop of both generations came out longer (+0.05 us per step, measured).
+template <int NTO>
+__device__ __forceinline__ float4 bwd_sum_partials(const u64 (&glo)[NTO], const u64 (&ghi)[NTO], int cntp) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NTO; ++i)
+        if (i < cntp) {
+            a0 += __uint_as_float((unsigned)glo[i] & ~7u);
+            a1 += __uint_as_float((unsigned)(glo[i] >> 32) & ~7u);
+            a2 += __uint_as_float((unsigned)ghi[i] & ~7u);
+            a3 += __uint_as_float((unsigned)(ghi[i] >> 32) & ~7u);
+        }
+    return make_float4(a0, a1, a2, a3);
+}
+
+// backward: what one step's cell backward needs of the saved forward values, formed a step ahead of its use
+struct Coef { float dy, c1, c2, c3, c4, c5, f; };
+__device__ __forceinline__ Coef make_coef(float dy, float gi, float gf, float gg, float go, float c, float cp) {
+    const float tc = tanh_f(c);
+    return Coef{dy,
+                go * (1.f - tc * tc),     // d c / d h
+                gg * gi * (1.f - gi),     // d i_pre / d c
+                cp * gf * (1.f - gf),     // d f_pre / d c
+                gi * (1.f - gg * gg),     // d g_pre / d c
+                tc * go * (1.f - go),     // d o_pre / d h
+                gf};
+}
+// the recurrent part of dh: the four gather waves' partial sums of this thread's element, s_part[producer group][256]
+__device__ __forceinline__ float s_part_sum(const float* s_part, int tid) {
+    return (s_part[tid] + s_part[256 + tid]) + (s_part[512 + tid] + s_part[768 + tid]);
+}
+// cell backward of one element: the four gate pre-activation gradients and the new carry.  By value: written through an
+// array reference, gen 3's time loop came out with other vector-memory counts (the same holds for bwd_partial).
+struct CellGrad { float d0, d1, d2, d3, carry; };
+__device__ __forceinline__ CellGrad cell_bwd(Coef k, float dh, float carry) {
+    const float dc = dh * k.c1 + carry;
+    return CellGrad{dc * k.c2, dc * k.c3, dc * k.c4, dh * k.c5, dc * k.f};
+}
+// backward: the partial product of one output tile (two MFMAs over the 64 reduction indices) ...
+__device__ __forceinline__ f32x4 bwd_partial(bf16x8 w0, bf16x8 w1, bf16x8 b0, bf16x8 b1) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = mma16(w0, b0, acc);
+    return mma16(w1, b1, acc);
+}
+// ... and its four sums as two tagged granules (the tag replaces the three mantissa LSBs)
+__device__ __forceinline__ void bwd_granules(f32x4 acc, u64 want, u64& v0, u64& v1) {
+    v0 = ((u64)(__float_as_uint(acc[0]) & ~7u) | ((u64)(__float_as_uint(acc[1]) & ~7u) << 32)) | want;
+    v1 = ((u64)(__float_as_uint(acc[2]) & ~7u) | ((u64)(__float_as_uint(acc[3]) & ~7u) << 32)) | want;
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------
 // integer environment variable (poll delays: units of s_sleep(2) = 128 clocks; the callers read them once per process)
 inline int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
 }
+// poll delay of a pass from a generation's two variables, read on the first call (one call site per translation unit)
+inline int poll_delays(const char* env_fwd, const char* env_bwd, int dflt_fwd, int dflt_bwd, bool bwd) {
+    static const int d[2] = {env_int(env_fwd, dflt_fwd), env_int(env_bwd, dflt_bwd)};
+    return d[bwd];
+}
+// The instantiation classes of generations 2 and 3, ascending (a shape takes the first that holds it): NKS = 32-column
+// k-steps of the forward (H <= 32 NKS), NTO = output tiles per compute wave of the backward (H <= 64 NTO).
+#define LSTM_G23_NKS(X) X(1) X(2) X(4) X(6) X(8) X(10) X(12) X(16)
+#define LSTM_G23_NTO(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8)
 
 // Launches kernel<<<grid, block, lds, st>>>(p); ASR_OK, or ASR_E_LAUNCH with the runtime's message under `name`.
 template <typename KernelT, typename ParamT>

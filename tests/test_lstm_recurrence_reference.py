@@ -69,8 +69,9 @@ fourth step (a lost register at the unroll-by-four boundary) it is 2.3e-2 and pa
 one ulp, 2^-7 relative at the most, and the bound lies between half an ulp and one ulp, so a single element need not exceed it;
 over a whole gate plane some dropped fraction always does (2.0 here): kept, and caught.
 
-CASE TABLES, derived from the dispatch macros (FWD_CASE / BWD_CASE of lstm_persist.hip, FWD2_CASE / BWD2_CASE of
-lstm_persist2.hip, FWD3_CASE / BWD3_CASE of lstm_persist3.hip) by the plan arithmetic restated below; test_case_tables_cover
+CASE TABLES, derived from the dispatch macros (FWD_CASE / BWD_CASE of lstm_persist.hip; FWD2_CASE / BWD2_CASE of
+lstm_persist2.hip and FWD3_CASE / BWD3_CASE of lstm_persist3.hip, both expanded over the class lists LSTM_G23_NKS / LSTM_G23_NTO
+of lstm_persist_common.h) by the plan arithmetic restated below; test_case_tables_cover
 enumerates every (B, H, ND, precision) the plans accept and asserts that every instantiation any shape reaches is launched by
 a case, and that the lines below are the tables.  Shape -> instantiation:
   lstm16-bf16-B4-T4-H16-ND2                    fwd fwd3<NKS=1,CH=1>           bwd bwd3<NTO=1>
@@ -537,8 +538,8 @@ def passes_old(inp, st):
 # ---------------------------------------------------------------------------------------------------------------------
 G1_FWD_NKS = (1, 2, 3, 4, 5, 6, 8, 10)                                          # FWD_CASE, each x MT {1, 2, 4}
 G1_BWD = ((1, 1), (1, 2), (1, 4), (1, 8), (2, 8), (4, 4), (5, 4), (3, 4), (2, 4))   # BWD_CASE (NTO, NKS), each x NE {1, 2, 4, 8}
-G23_FWD_NKS = (1, 2, 4, 6, 8, 10, 12, 16)                                       # FWD2_CASE / FWD3_CASE
-G23_BWD_NTO = (1, 2, 3, 4, 5, 6, 8)                                             # BWD2_CASE / BWD3_CASE
+G23_FWD_NKS = (1, 2, 4, 6, 8, 10, 12, 16)                                       # LSTM_G23_NKS (FWD2_CASE / FWD3_CASE)
+G23_BWD_NTO = (1, 2, 3, 4, 5, 6, 8)                                             # LSTM_G23_NTO (BWD2_CASE / BWD3_CASE)
 
 
 def _cdiv(a, b):
