@@ -8,6 +8,8 @@
 //                     the order-k delta filters, zero padding at the utterance ends, channel-major stacking.
 //   asr_specaug     : Augment (src/audio.py:364-406): one time mask and one frequency mask per utterance,
 //                     filled with the mean (recomputed after the time mask), in place on the padded batch.
+// Every length is taken as min(length, padded extent).  An utterance shorter than the time-mask width, or a feature axis
+// narrower than the frequency-mask width, draws its mask width below its own extent (specaug_draws); the reference raises there.
 #include "common.h"
 #include "gemm_plan.h"
 
@@ -22,7 +24,7 @@ __global__ void frame_kernel(const float* __restrict__ wav, const int64_t* __res
         const int m = (int)(i % win);
         const int k = (int)((i / win) % T);
         const int b = (int)(i / ((long)win * T));
-        const int n = (int)wav_len[b];
+        const int n = (int)min(wav_len[b], (int64_t)N);
         float v = 0.f;
         if (n > 1 && k < 1 + (n - 1) / hop) {   // center padding n_fft/2 each side with odd n_fft: 1 + (n-1)/hop frames
             int p = k * hop + off + m;
@@ -48,14 +50,14 @@ __global__ void magnitude_kernel(const float* __restrict__ spec, float* __restri
     }
 }
 
-__global__ void logmel_kernel(float* __restrict__ mel, const int64_t* __restrict__ wav_len, long rows, int T, int nmel, int hop,
+__global__ void logmel_kernel(float* __restrict__ mel, const int64_t* __restrict__ wav_len, long rows, int N, int T, int nmel, int hop,
                               float ref_db, float min_db) {
     const long total = rows * nmel;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long r = i / nmel;
         const int b = (int)(r / T), k = (int)(r % T);
         float v = 0.f;
-        if (k < 1 + ((int)wav_len[b] - 1) / hop) {
+        if (k < 1 + ((int)min(wav_len[b], (int64_t)N) - 1) / hop) {
             const float db = 20.f * log10f(fmaxf(mel[i], 1e-5f)) - ref_db;
             v = fminf(fmaxf((db - min_db) / -min_db, 0.f), 1.f);
         }
@@ -73,7 +75,7 @@ __global__ void delta_stack_kernel(const float* __restrict__ x, const int64_t* _
         const int c = (int)((i / F) % C);
         const int t = (int)((i / ((long)F * C)) % T);
         const int b = (int)(i / ((long)F * C * T));
-        const int len = (int)lens[b];
+        const int len = (int)min(lens[b], (int64_t)T);
         float acc = 0.f;
         if (t < len) {
             for (int j = 0; j < taps; ++j) {
@@ -82,6 +84,33 @@ __global__ void delta_stack_kernel(const float* __restrict__ x, const int64_t* _
             }
         }
         out[i] = acc;
+    }
+}
+
+// SpecAugment draws of utterance b, stated once for the three kernels: dr = {t, t0, tend, f, f0, fend} (reference draw order),
+// 0 <= t0 <= tend <= len and 0 <= f0 <= fend <= D on return; t == 0 / f == 0 is an empty band (tend = t0 / fend = f0).
+//   device draws: t = r0 % min(Tmask, max(len, 1)), t0 = r1 % max(len - t, 1), tend = t0 + r2 % t; f = r3 % min(Fmask, D),
+//                 f0 = r4 % (D - f), fend = f0 + r5 % f - the reference's draws wherever it has any (len >= Tmask, D >= Fmask);
+//   draws_in    : t and f as given, the bands clamped into the utterance.
+__device__ __forceinline__ void specaug_draws(int b, int len, int D, int Tmask, int Fmask, uint64_t seed, const int* draws_in, int (&dr)[6]) {
+    len = max(len, 0);
+    if (draws_in) {
+        for (int i = 0; i < 6; ++i) dr[i] = draws_in[b * 6 + i];
+        dr[1] = min(max(dr[1], 0), len);
+        dr[2] = (dr[0] > 0) ? min(max(dr[2], dr[1]), len) : dr[1];
+        dr[4] = min(max(dr[4], 0), D);
+        dr[5] = (dr[3] > 0) ? min(max(dr[5], dr[4]), D) : dr[4];
+    } else {
+        uint32_t r[4], r2[4];
+        philox4x32((uint32_t)b, 0u, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+        philox4x32((uint32_t)b, 0u, 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r2);
+        const int t = (int)(r[0] % (uint32_t)min(Tmask, max(len, 1)));
+        const int t0 = (int)(r[1] % (uint32_t)max(len - t, 1));
+        const int tend = (t > 0) ? t0 + (int)(r[2] % (uint32_t)t) : t0;
+        const int f = (int)(r[3] % (uint32_t)min(Fmask, D));
+        const int f0 = (int)(r2[0] % (uint32_t)(D - f));
+        const int fend = (f > 0) ? f0 + (int)(r2[1] % (uint32_t)f) : f0;
+        dr[0] = t; dr[1] = t0; dr[2] = tend; dr[3] = f; dr[4] = f0; dr[5] = fend;
     }
 }
 
@@ -96,25 +125,11 @@ __global__ __launch_bounds__(1024) void specaug_kernel(float* __restrict__ x, co
     float* xb = x + (long)b * T * D;
     if (tid == 0) {
         int dr[6];
-        if (draws_in) {
-            for (int i = 0; i < 6; ++i) dr[i] = draws_in[b * 6 + i];
-        } else {
-            uint32_t r[4], r2[4];
-            philox4x32((uint32_t)b, 0u, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-            philox4x32((uint32_t)b, 0u, 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r2);
-            const int t = (int)(r[0] % (uint32_t)Tmask);
-            const int t0 = (len - t > 0) ? (int)(r[1] % (uint32_t)(len - t)) : 0;
-            const int tend = (t > 0) ? t0 + (int)(r[2] % (uint32_t)t) : t0;
-            const int f = (int)(r[3] % (uint32_t)Fmask);
-            const int f0 = (D - f > 0) ? (int)(r2[0] % (uint32_t)(D - f)) : 0;
-            const int fend = (f > 0) ? f0 + (int)(r2[1] % (uint32_t)f) : f0;
-            dr[0] = t; dr[1] = t0; dr[2] = tend; dr[3] = f; dr[4] = f0; dr[5] = fend;
-        }
+        specaug_draws(b, len, D, Tmask, Fmask, seed, draws_in, dr);
         for (int i = 0; i < 6; ++i) { s_draw[i] = dr[i]; if (draws_out) draws_out[b * 6 + i] = dr[i]; }
     }
     __syncthreads();
-    const int t0 = s_draw[1], tend = (s_draw[0] > 0) ? s_draw[2] : s_draw[1];
-    const int f0 = s_draw[4], fend = (s_draw[3] > 0) ? s_draw[5] : s_draw[4];
+    const int t0 = s_draw[1], tend = s_draw[2], f0 = s_draw[4], fend = s_draw[5];
     if (len <= 0) return;
     // sums over the valid region and over the rows of the time mask
     double sum = 0.0, srow = 0.0;
@@ -136,7 +151,7 @@ __global__ __launch_bounds__(1024) void specaug_kernel(float* __restrict__ x, co
     double rowtot = 0.0;
     for (int i = 0; i < 16; ++i) rowtot += s_red[i];
     const float mean1 = (float)(tot / (double)n);
-    const double nrow = (double)max(tend - t0, 0) * D;
+    const double nrow = (double)(tend - t0) * D;
     const float mean2 = (float)((tot - rowtot + (double)mean1 * nrow) / (double)n);   // mean after the time mask
     for (long i = tid; i < n; i += 1024) {
         const int t = (int)(i / D), f = (int)(i % D);
@@ -150,23 +165,6 @@ __global__ __launch_bounds__(1024) void specaug_kernel(float* __restrict__ x, co
 // masked rows / columns are written.
 constexpr int SA_SPLIT = 16;
 
-__device__ __forceinline__ void specaug_draws(int b, int len, int D, int Tmask, int Fmask, uint64_t seed, const int* draws_in, int (&dr)[6]) {
-    if (draws_in) {
-        for (int i = 0; i < 6; ++i) dr[i] = draws_in[b * 6 + i];
-    } else {
-        uint32_t r[4], r2[4];
-        philox4x32((uint32_t)b, 0u, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-        philox4x32((uint32_t)b, 0u, 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r2);
-        const int t = (int)(r[0] % (uint32_t)Tmask);
-        const int t0 = (len - t > 0) ? (int)(r[1] % (uint32_t)(len - t)) : 0;
-        const int tend = (t > 0) ? t0 + (int)(r[2] % (uint32_t)t) : t0;
-        const int f = (int)(r[3] % (uint32_t)Fmask);
-        const int f0 = (D - f > 0) ? (int)(r2[0] % (uint32_t)(D - f)) : 0;
-        const int fend = (f > 0) ? f0 + (int)(r2[1] % (uint32_t)f) : f0;
-        dr[0] = t; dr[1] = t0; dr[2] = tend; dr[3] = f; dr[4] = f0; dr[5] = fend;
-    }
-}
-
 __global__ __launch_bounds__(256) void specaug_sum_kernel(const float* __restrict__ x, const int64_t* __restrict__ lens,
                                                           const int* __restrict__ draws_in, int* __restrict__ draws_out,
                                                           double* __restrict__ part, int B, int T, int D, int Tmask, int Fmask, uint64_t seed) {
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(256) void specaug_sum_kernel(const float* __restric
     int dr[6];
     specaug_draws(b, len, D, Tmask, Fmask, seed, draws_in, dr);          // every workgroup derives the same draws
     if (sp == 0 && tid == 0 && draws_out) for (int i = 0; i < 6; ++i) draws_out[b * 6 + i] = dr[i];
-    const int t0 = dr[1], tend = (dr[0] > 0) ? dr[2] : dr[1];
+    const int t0 = dr[1], tend = dr[2];
     const float* xb = x + (long)b * T * D;
     const long n = (long)max(len, 0) * D;
     const long per = (n + SA_SPLIT - 1) / SA_SPLIT, i0 = sp * per, i1 = min(n, i0 + per);
@@ -204,16 +202,15 @@ __global__ __launch_bounds__(256) void specaug_apply_kernel(float* __restrict__ 
     if (len <= 0) return;
     int dr[6];
     specaug_draws(b, len, D, Tmask, Fmask, seed, draws_in, dr);
-    const int t0 = dr[1], tend = (dr[0] > 0) ? dr[2] : dr[1];
-    const int f0 = dr[4], fend = (dr[3] > 0) ? dr[5] : dr[4];
+    const int t0 = dr[1], tend = dr[2], f0 = dr[4], fend = dr[5];
     double tot = 0.0, rowtot = 0.0;
     for (int i = 0; i < SA_SPLIT; ++i) { tot += part[((long)b * SA_SPLIT + i) * 2]; rowtot += part[((long)b * SA_SPLIT + i) * 2 + 1]; }
     const long n = (long)len * D;
     const float mean1 = (float)(tot / (double)n);
-    const double nrow = (double)max(tend - t0, 0) * D;
+    const double nrow = (double)(tend - t0) * D;
     const float mean2 = (float)((tot - rowtot + (double)mean1 * nrow) / (double)n);   // mean after the time mask
     float* xb = x + (long)b * T * D;
-    const int fw = max(fend - f0, 0), tw = max(min(tend, len) - t0, 0);
+    const int fw = fend - f0, tw = tend - t0;
     // frequency band: columns f0..fend of every valid row; time band: rows t0..tend outside that band
     const long nf = (long)len * fw, nt = (long)tw * D;
     for (long i = blockIdx.x * 256L + tid; i < nf + nt; i += (long)gridDim.x * 256) {
@@ -243,6 +240,7 @@ extern "C" int asr_fbank(const float* wav, const int64_t* wav_len, float* out, c
                          void* workspace, size_t workspace_bytes, asr_stream_t stream) {
     ASR_REQUIRE(wav && wav_len && out && dft_table && mel_fb && window && workspace, ASR_E_ARG, "asr_fbank: null pointer");
     ASR_REQUIRE(B > 0 && N > 0 && T > 0 && win > 0 && hop > 0 && n_fft >= win && nmel > 0, ASR_E_ARG, "asr_fbank: bad dims");
+    ASR_REQUIRE(n_fft & 1, ASR_E_ARG, "asr_fbank: n_fft %d is even (the frame count 1 + (n-1)/hop holds for odd n_fft)", n_fft);
     ASR_REQUIRE(workspace_bytes >= asr_fbank_workspace_bytes(B, T, win, n_fft), ASR_E_ARG, "asr_fbank: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const long rows = (long)B * T;
@@ -261,7 +259,7 @@ extern "C" int asr_fbank(const float* wav, const int64_t* wav_len, float* out, c
     mel.prec = ASR_F32;
     rc = gemm_run(mel, st);
     if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL(logmel_kernel, dim3(grid_for(rows * nmel)), dim3(256), 0, st, out, wav_len, rows, T, nmel, hop, ref_db, min_db);
+    hipLaunchKernelGGL(logmel_kernel, dim3(grid_for(rows * nmel)), dim3(256), 0, st, out, wav_len, rows, N, T, nmel, hop, ref_db, min_db);
     ASR_LAUNCH_CHECK("asr_fbank");
     return ASR_OK;
 }

@@ -406,7 +406,21 @@ int asr_embedding_bwd(const float* dy, long dy_ld, const int64_t* idx, float* de
  *     filters (channels, taps) as Delta._create_filters builds them; out (B,T,channels*F) channel-major.
  *   asr_specaug: Augment (src/audio.py:364-406), in place on x (B,T,D) using lens.  draws_in (B,6) int32 =
  *     {t, t0, tend, f, f0, fend} in the reference's draw order, or NULL to draw on the device
- *     (Philox, seed); draws_out (B,6) optional.
+ *     (Philox, seed); draws_out (B,6) optional: the draws as applied.
+ * Edges, the same for all four entry points:
+ *   - a length is taken as min(length, padded extent): wav_len against N, lens against T; a length <= 0 is an empty utterance
+ *     (asr_fbank and asr_delta_stack write zero rows, SpecAugment leaves it alone);
+ *   - asr_fbank refuses an even n_fft (ASR_E_ARG, nothing launched): its frame count 1 + (n-1)/hop is that of centre padding
+ *     with an odd n_fft.  An utterance of n samples owns rows [0, 1 + (n-1)/hop), n <= 1 gives zeros;
+ *   - SpecAugment device draws, with r0..r5 the Philox words of (seed, utterance) and len = min(lens[b], T):
+ *       t = r0 % min(time_width, max(len, 1)),  t0 = r1 % max(len - t, 1),  tend = t0 + r2 % t   (t == 0: no time mask)
+ *       f = r3 % min(freq_width, D),            f0 = r4 % (D - f),          fend = f0 + r5 % f   (f == 0: no frequency mask)
+ *     so that 0 <= t0 <= tend <= len and 0 <= f0 <= fend <= D always.  For len >= time_width and D >= freq_width these are the
+ *     reference's draws; below, where the reference raises (randint over an empty range), the mask width is drawn below the
+ *     utterance's own extent.  The time band is filled with the mean of the valid len x D region, the frequency band with the
+ *     mean after that fill;
+ *   - caller-supplied draws_in are clamped into the utterance before use: t0 to [0, len], tend to [t0, len], f0 to [0, D],
+ *     fend to [f0, D]; t == 0 / f == 0 switch the band off as in the reference.  No draw can store outside len x D.
  */
 size_t asr_fbank_workspace_bytes(int B, int T, int win, int n_fft);
 int asr_fbank(const float* wav, const int64_t* wav_len, float* out, const float* dft_table, const float* mel_fb,

@@ -63,17 +63,25 @@ def test_hip_specaugment_matches_reference(g5):
     for i in range(nb):
         np.testing.assert_allclose(out[i, :T].numpy(), g5['aug_out%d' % i], atol=2e-6)
         assert float((out[i, T:] - 9.0).abs().max()) == 0.0
-    # device-side draws: masks must be legal (inside the utterance, widths below T / F) and mean-filled
-    y = torch.rand(4, 300, 160)
-    lens = torch.tensor([300, 250, 200, 41])
+    # device-side draws: masks must be legal (inside the utterance, widths below T / F) and mean-filled - and exactly the
+    # bands of the stated rule (tests/test_frontend_reference.py::specaug_draws), also on utterances shorter than the time mask
+    from test_frontend_reference import specaug_draws
+    y = torch.rand(6, 300, 160)
+    lens = torch.tensor([300, 250, 200, 41, 10, 1])
     yd = y.clone().cuda()
     aug(yd, lens.cuda())
+    seed = (aug.seed * 1000003 + aug.calls) & 0xFFFFFFFFFFFF
     changed = (yd.cpu() != y)
-    for b in range(4):
+    for b in range(6):
         assert not changed[b, lens[b]:].any()
         rows = changed[b].all(dim=1).nonzero().flatten()
         cols = changed[b, :lens[b]].all(dim=0).nonzero().flatten()
         assert len(rows) < 40 and len(cols) < 27
+        t, t0, tend, f, f0, fend = specaug_draws(b, int(lens[b]), 160, 40, 27, seed)
+        want = torch.zeros(300, 160, dtype=torch.bool)
+        want[t0:tend] = True
+        want[:lens[b], f0:fend] = True
+        assert torch.equal(changed[b], want), (b, (t, t0, tend, f, f0, fend))
 
 
 @pytest.mark.gpu
