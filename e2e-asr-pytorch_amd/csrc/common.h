@@ -32,6 +32,18 @@ void asr_set_error(const char* fmt, ...);
         }                                                                     \
     } while (0)
 
+// What every dropout + down-sampling entry point (elementwise.hip, elementwise16.hip) refuses beyond null pointers and
+// non-positive sizes (include/asr_hip.h):
+// p outside [0,1) (the scale 1 / (1 - p) must be finite), a style other than 0 / 1, and a T2 that asks for frames y does not
+// have - rows of z would stay unwritten and the backward would read past dz.  A smaller T2 is legal.
+#define ASR_DS_REQUIRE(name)                                                                                              \
+    do {                                                                                                                  \
+        ASR_REQUIRE(p >= 0.f && p < 1.f, ASR_E_ARG, name ": p must be in [0,1)");                                         \
+        ASR_REQUIRE(style == 0 || style == 1, ASR_E_ARG, name ": style must be 0 (drop) or 1 (concat)");                  \
+        ASR_REQUIRE(style == 0 ? (long)(T2 - 1) * rate < T : (long)T2 * rate <= T, ASR_E_ARG,                             \
+                    name ": T2 = %d asks for frames beyond T = %d at rate %d", T2, T, rate);                              \
+    } while (0)
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // true the first time it is called for the CURRENT device with this flag array: kernel attributes (dynamic-LDS limits) are

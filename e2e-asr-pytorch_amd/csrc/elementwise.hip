@@ -227,7 +227,7 @@ inline uint32_t drop_thresh(float p) {
 extern "C" int asr_dropout_downsample_fwd(const float* y, float* z, int B, int T, int D, int T2, int rate, int style,
                                           float p, uint64_t seed, asr_stream_t stream) {
     ASR_REQUIRE(y && z && B > 0 && T > 0 && D > 0 && T2 > 0 && rate >= 1, ASR_E_ARG, "asr_dropout_downsample_fwd: bad args");
-    ASR_REQUIRE(p >= 0.f && p < 1.f, ASR_E_ARG, "asr_dropout_downsample_fwd: p must be in [0,1)");
+    ASR_DS_REQUIRE("asr_dropout_downsample_fwd");
     DsP a{y, z, B, T, D, T2, rate, style, 1.f / (1.f - p), drop_thresh(p), seed};
     if ((D & 3) == 0 && (((uintptr_t)y | (uintptr_t)z) & 15) == 0)
         hipLaunchKernelGGL(dropout_downsample_vec4_kernel<false>, dim3(grid_for((long)B * T * (D / 4))), dim3(256), 0, (hipStream_t)stream, a);
@@ -240,6 +240,7 @@ extern "C" int asr_dropout_downsample_fwd(const float* y, float* z, int B, int T
 extern "C" int asr_dropout_downsample_bwd(const float* dz, float* dy, int B, int T, int D, int T2, int rate, int style,
                                           float p, uint64_t seed, asr_stream_t stream) {
     ASR_REQUIRE(dz && dy && B > 0 && T > 0 && D > 0 && T2 > 0 && rate >= 1, ASR_E_ARG, "asr_dropout_downsample_bwd: bad args");
+    ASR_DS_REQUIRE("asr_dropout_downsample_bwd");
     DsP a{dz, dy, B, T, D, T2, rate, style, 1.f / (1.f - p), drop_thresh(p), seed};
     if ((D & 3) == 0 && (((uintptr_t)dz | (uintptr_t)dy) & 15) == 0)
         hipLaunchKernelGGL(dropout_downsample_vec4_kernel<true>, dim3(grid_for((long)B * T * (D / 4))), dim3(256), 0, (hipStream_t)stream, a);
@@ -251,6 +252,7 @@ extern "C" int asr_dropout_downsample_bwd(const float* dz, float* dy, int B, int
 
 extern "C" int asr_dropout_mask(float* mask, long n, float p, uint64_t seed, asr_stream_t stream) {
     ASR_REQUIRE(mask && n > 0, ASR_E_ARG, "asr_dropout_mask: bad args");
+    ASR_REQUIRE(p >= 0.f && p < 1.f, ASR_E_ARG, "asr_dropout_mask: p must be in [0,1)");
     hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, mask, n, drop_thresh(p), seed);
     ASR_LAUNCH_CHECK("asr_dropout_mask");
     return ASR_OK;

@@ -53,7 +53,8 @@ __global__ void cast_to_f32_kernel(const unsigned short* __restrict__ src, float
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
         const long j = (n8 << 3) + threadIdx.x;
-        dst[j] = (accum ? dst[j] : 0.f) + bf2f(src[j]);
+        const float v = bf2f(src[j]);
+        dst[j] = accum ? dst[j] + v : v;                                 // not 0.f + v: that turns -0 into +0
     }
 }
 
@@ -232,7 +233,8 @@ extern "C" int asr_rnn_pack_weights(const float* w_ih, const float* b_ih, const 
 
 extern "C" int asr_dropout_downsample16_fwd(const void* y, long y_bstride, long y_off, void* z, int B, int T, int D, int T2, int rate,
                                             int style, float p, uint64_t seed, asr_stream_t stream) {
-    ASR_REQUIRE(y && z && B > 0 && T > 0 && D > 0 && T2 > 0 && rate >= 1 && p >= 0.f && p < 1.f, ASR_E_ARG, "asr_dropout_downsample16_fwd: bad args");
+    ASR_REQUIRE(y && z && B > 0 && T > 0 && D > 0 && T2 > 0 && rate >= 1, ASR_E_ARG, "asr_dropout_downsample16_fwd: bad args");
+    ASR_DS_REQUIRE("asr_dropout_downsample16_fwd");
     ASR_REQUIRE(D % 8 == 0 && y_bstride % 8 == 0 && y_off % 8 == 0 && (((uintptr_t)y | (uintptr_t)z) & 15) == 0, ASR_E_UNSUPPORTED,
                 "asr_dropout_downsample16_fwd: rows of 8 bf16, 16-byte aligned");
     Ds16P a{(const unsigned short*)y, (unsigned short*)z, y_bstride, y_off, B, T, D, T2, rate, style, 1.f / (1.f - p), drop_thresh(p), seed};
@@ -244,6 +246,7 @@ extern "C" int asr_dropout_downsample16_fwd(const void* y, long y_bstride, long 
 extern "C" int asr_dropout_downsample16_bwd(const void* dz, void* dy, int B, int T, int D, int T2, int rate, int style,
                                             float p, uint64_t seed, asr_stream_t stream) {
     ASR_REQUIRE(dz && dy && B > 0 && T > 0 && D > 0 && T2 > 0 && rate >= 1, ASR_E_ARG, "asr_dropout_downsample16_bwd: bad args");
+    ASR_DS_REQUIRE("asr_dropout_downsample16_bwd");
     ASR_REQUIRE(D % 8 == 0 && (((uintptr_t)dz | (uintptr_t)dy) & 15) == 0, ASR_E_UNSUPPORTED, "asr_dropout_downsample16_bwd: rows of 8 bf16, 16-byte aligned");
     Ds16P a{(const unsigned short*)dz, (unsigned short*)dy, (long)T * D, 0, B, T, D, T2, rate, style, 1.f / (1.f - p), drop_thresh(p), seed};
     hipLaunchKernelGGL(dropout_downsample16_kernel<true>, dim3(grid_for((long)B * T * (D / 8))), dim3(256), 0, (hipStream_t)stream, a);

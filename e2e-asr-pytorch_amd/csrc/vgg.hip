@@ -8,6 +8,12 @@ namespace {
 
 inline int grid_for(long n) { long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
 
+// a * b rounded to fp32 on its own, never contracted into a neighbouring add (__fmul_rn is a plain, contractable a * b here)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 // out[r, b, a] = in[r, a, b]   (rows r, inner dims A x Bd)
 __global__ void permute_last2_kernel(const float* __restrict__ in, float* __restrict__ out, long rows, int A, int Bd) {
     const long total = rows * A * Bd;
@@ -101,16 +107,22 @@ __global__ __launch_bounds__(256) void ln_f_fwd_kernel(const float* __restrict__
     }
 }
 
+// dw / db: wave reduction, one LDS atomic per wave, and ONE global atomic per workgroup and f at the end.  The global atomics are a
+// chain of fp32 roundings at the magnitude of the finished sum (a random walk of ulp(sum) / sqrt(12) per link), so the launch keeps
+// that chain short: at most LN_BWD_MAX_WG workgroups of LN_BWD_TPB threads - the thread slots of the 2048 x 256 launch it
+// replaces, a quarter of the links.  Measured on the MI355X against that launch: 174 vs 190 us at rows 16000 F 40 C 64, 76 vs 87 us at
+// rows 8000 F 20 C 128, 38 vs 36 us at rows 800 F 40 C 64; 256 workgroups of 1024 halve the chain again but cost 238 / 103 us.
+constexpr int LN_BWD_TPB = 1024, LN_BWD_MAX_WG = 512;
 template <int FMAX>
-__global__ __launch_bounds__(256) void ln_f_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ w,
+__global__ __launch_bounds__(LN_BWD_TPB) void ln_f_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ bia, const float* __restrict__ stats,
                                                        float* __restrict__ dx, float* __restrict__ dw, float* __restrict__ db,
                                                        long rows, int F, int C, int relu) {
     __shared__ float s_dw[FMAX], s_db[FMAX];
-    for (int f = threadIdx.x; f < F; f += 256) { s_dw[f] = 0.f; s_db[f] = 0.f; }
+    for (int f = threadIdx.x; f < F; f += LN_BWD_TPB) { s_dw[f] = 0.f; s_db[f] = 0.f; }
     __syncthreads();
     const long total = rows * C;
-    for (long i0 = blockIdx.x * 256L; i0 < total; i0 += (long)gridDim.x * 256) {
+    for (long i0 = blockIdx.x * (long)LN_BWD_TPB; i0 < total; i0 += (long)gridDim.x * LN_BWD_TPB) {
         const long i = i0 + threadIdx.x;
         const bool ok = i < total;
         const long r = ok ? i / C : 0;
@@ -126,8 +138,12 @@ __global__ __launch_bounds__(256) void ln_f_bwd_kernel(const float* __restrict__
                 g = gp[(long)f * C];
                 if (relu && (xh * w[f] + bia[f]) <= 0.f) g = 0.f;
             }
-            s1 += g * w[f];
-            s2 += g * w[f] * xh;
+            // g w is ROUNDED on its own, here and in the second loop: that loop must subtract the very product this one summed - at
+            // F = 1, where rstd = 1/sqrt(eps), a g w fused into `g w - s1` left rstd ulp(g w) where the gradient is exactly 0
+            // (tests/test_hip_vgg_kernels_vs_float64.py, as in asr_ln_freq16_bwd)
+            const float gwp = mul_rounded(g, w[f]);
+            s1 += gwp;
+            s2 += gwp * xh;
             // per-f parameter gradients: wave reduction, then one LDS atomic per wave
             const float gw = wave_sum(g * xh), gb = wave_sum(g);
             if ((threadIdx.x & 63) == 0) { atomicAdd(&s_dw[f], gw); atomicAdd(&s_db[f], gb); }
@@ -139,12 +155,12 @@ __global__ __launch_bounds__(256) void ln_f_bwd_kernel(const float* __restrict__
                 const float xh = (xp[(long)f * C] - mean) * rstd;
                 float g = gp[(long)f * C];
                 if (relu && (xh * w[f] + bia[f]) <= 0.f) g = 0.f;
-                dp[(long)f * C] = rstd * (g * w[f] - s1 - xh * s2);
+                dp[(long)f * C] = rstd * (mul_rounded(g, w[f]) - s1 - xh * s2);
             }
         }
     }
     __syncthreads();
-    for (int f = threadIdx.x; f < F; f += 256) { atomicAdd(dw + f, s_dw[f]); atomicAdd(db + f, s_db[f]); }
+    for (int f = threadIdx.x; f < F; f += LN_BWD_TPB) { atomicAdd(dw + f, s_dw[f]); atomicAdd(db + f, s_db[f]); }
 }
 
 }  // namespace
@@ -173,7 +189,8 @@ extern "C" int asr_maxpool2x2_fwd(const float* x, float* y, unsigned char* idx, 
 
 extern "C" int asr_maxpool2x2_bwd(const float* dy, const unsigned char* idx, float* dx, int B, int T, int F, int C, int T2, int F2,
                                   asr_stream_t stream) {
-    ASR_REQUIRE(dy && idx && dx && B > 0 && T > 0 && F > 0 && C > 0, ASR_E_ARG, "asr_maxpool2x2_bwd: bad args");
+    ASR_REQUIRE(dy && idx && dx && B > 0 && T > 0 && F > 0 && C > 0 && T2 > 0 && F2 > 0, ASR_E_ARG, "asr_maxpool2x2_bwd: bad args");
+    ASR_REQUIRE(2 * T2 - 1 <= T && 2 * F2 - 1 <= F, ASR_E_ARG, "asr_maxpool2x2_bwd: output larger than ceil(T/2) x ceil(F/2)");
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for((long)B * T * F * C)), dim3(256), 0, (hipStream_t)stream, dy, idx, dx, B, T, F, C, T2, F2);
     ASR_LAUNCH_CHECK("asr_maxpool2x2_bwd");
     return ASR_OK;
@@ -191,8 +208,8 @@ extern "C" int asr_ln_freq_bwd(const float* dy, const float* x, const float* w, 
                                float* dx, float* dw, float* db, long rows, int F, int C, int relu, asr_stream_t stream) {
     ASR_REQUIRE(dy && x && w && b && stats && dx && dw && db && rows > 0 && F > 0 && C > 0, ASR_E_ARG, "asr_ln_freq_bwd: bad args");
     ASR_REQUIRE(F <= 128, ASR_E_UNSUPPORTED, "asr_ln_freq_bwd: F=%d > 128", F);
-    long g = (rows * C + 255) / 256; if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(ln_f_bwd_kernel<128>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, dy, x, w, b, stats, dx, dw, db, rows, F, C, relu);
+    long g = (rows * C + LN_BWD_TPB - 1) / LN_BWD_TPB; if (g > LN_BWD_MAX_WG) g = LN_BWD_MAX_WG;
+    hipLaunchKernelGGL(ln_f_bwd_kernel<128>, dim3((int)g), dim3(LN_BWD_TPB), 0, (hipStream_t)stream, dy, x, w, b, stats, dx, dw, db, rows, F, C, relu);
     ASR_LAUNCH_CHECK("asr_ln_freq_bwd");
     return ASR_OK;
 }

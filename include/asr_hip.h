@@ -163,11 +163,20 @@ int asr_gemm16_plan(const void* A, const void* B, void* C, const float* bias, in
 int asr_rnn_pack_weights(const float* w_ih, const float* b_ih, const float* b_hh, const float* pj,
                          void* w_ih16, void* w_ihT16, float* bias, void* pj16, void* pjT16,
                          int H, int ND, int Din, int D, asr_stream_t stream);
-/* fp32 <-> bf16 (accum = 1: dst += src) */
+/* fp32 <-> bf16 (accum = 1: dst += src, one float32 add per element; accum = 0: dst = src with the sign of zero kept).
+ * asr_cast_bf16 rounds to nearest, ties to even: FLT_MAX and everything above the largest bf16 value's tie go to infinity,
+ * +-0 and +-infinity keep their sign, NaN stays NaN.  SUBNORMAL float32 inputs are rounded like every other value
+ * (nearest-even onto the bf16 subnormals, which share float32's exponent range); they are not flushed to zero.
+ * src and dst 16-byte aligned, n > 0; anything else returns ASR_E_ARG and launches nothing. */
 int asr_cast_bf16(const float* src, void* dst, long n, asr_stream_t stream);
 int asr_cast_f32(const void* src, float* dst, long n, int accum, asr_stream_t stream);
 /* the bf16 forms of asr_dropout_downsample_*, asr_act_bwd and asr_colsum2 (same Philox mask: flat index (b*T+t)*D+k);
- * y is addressed as y[y_off + b*y_bstride + t*D + k] (elements), which covers the time-padded y16 */
+ * y is addressed as y[y_off + b*y_bstride + t*D + k] (elements), which covers the time-padded y16; only those B*T rows of y
+ * are read.  Kept values are bf16(float32(y) * float32(1 / (1 - p))), one float32 product and one nearest-even rounding.
+ * D, y_bstride, y_off multiples of 8 and 16-byte aligned bases, else ASR_E_UNSUPPORTED; p, style and T2 are checked as for
+ * the fp32 entry points below (ASR_E_ARG).  asr_act_bwd16: n % 8 == 0 and act = ASR_ACT_TANH / ASR_ACT_RELU, else ASR_E_ARG.
+ * asr_colsum16: N % 8, lda % 8 or a misaligned A return ASR_E_UNSUPPORTED; lda < N or a perm_h > 0 with N % (4 perm_h) != 0
+ * return ASR_E_ARG.  A refused call launches nothing and touches no output. */
 int asr_dropout_downsample16_fwd(const void* y, long y_bstride, long y_off, void* z, int B, int T, int D, int T2, int rate,
                                  int style, float p, uint64_t seed, asr_stream_t stream);
 int asr_dropout_downsample16_bwd(const void* dz, void* dy, int B, int T, int D, int T2, int rate, int style,
@@ -182,6 +191,15 @@ int asr_colsum16(const void* A, long lda, int M, int N, float* out, float* out2,
  * keep(element) = Philox4x32-10(seed, flat index in y) >= p*2^32, kept values scaled by 1/(1-p);
  * asr_dropout_mask exports the same {0,1} mask (tests feed it to the oracle).  p = 0: no dropout.
  * Backward writes the full dy (B,T,D), zeros where nothing flowed.
+ * keep in full: element i of y draws word i & 3 of Philox block i >> 2 - counter (low, high word of the block index, 0, 0),
+ * key (low, high word of seed) - and is kept iff that word >= floor(float32(p) * 2^32), saturated at 2^32 - 1; the scale is
+ * the float32 quotient 1 / (1 - p) and a kept value the float32 product y * scale.
+ * Refused with ASR_E_ARG, nothing launched, by all four down-sampling entry points (fp32 and bf16):
+ *   - p outside [0, 1) (asr_dropout_mask refuses it too);
+ *   - style other than 0 or 1;
+ *   - a T2 that asks for frames y does not have: style 0 with (T2 - 1) * rate >= T, style 1 with T2 * rate > T.
+ * A SMALLER T2 than the caller's usual ceil(T / rate) resp. T / rate is legal: the forward drops the tail of y, the backward
+ * writes zeros there.
  */
 int asr_dropout_downsample_fwd(const float* y, float* z, int B, int T, int D, int T2, int rate, int style,
                                float p, uint64_t seed, asr_stream_t stream);
@@ -444,7 +462,10 @@ int asr_specaug_ws(float* x, const int64_t* lens, const int* draws_in, int* draw
  *   mode 1: dw[n][tap*C+ci] += sum_pixels dout[pixel, n] * img[pixel shifted by tap, ci]   (w_or_dout = dout)
  * asr_conv_weight_permute builds those copies from / folds the gradient back into the reference's
  * (Co,Ci,3,3) tensors (modes 0,1,2).  asr_maxpool2x2_* = nn.MaxPool2d(2, stride 2[, ceil_mode]); idx keeps
- * the arg-max (0..3).  asr_ln_freq_* = CNNLayerNorm (LayerNorm over F, affine per f) + optional ReLU;
+ * the arg-max (0..3 = 2 dt + df; of equal maxima the first in that order); T2 x F2 windows with 1 <= T2 <= ceil(T/2),
+ * 1 <= F2 <= ceil(F/2) - anything larger is refused by the forward AND the backward (ASR_E_ARG, nothing launched); the
+ * backward writes all of dx, zeros where no window reaches or the element was not the arg-max.
+ * asr_ln_freq_* = CNNLayerNorm (LayerNorm over F, affine per f) + optional ReLU; the backward takes F <= 128 (ASR_E_UNSUPPORTED);
  * stats (rows*C, 2).  asr_permute_last2: out[r,b,a] = in[r,a,b] (channel-major <-> channel-last).
  */
 int asr_conv3x3(const float* img, const float* w_or_dout, float* out, const float* bias,

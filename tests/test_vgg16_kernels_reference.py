@@ -150,6 +150,15 @@ def pack_ref(w, mode, Kp):
     return out
 
 
+def pack_unrounded(w, mode):
+    """The packing rule alone, values untouched (the fp32 asr_conv_weight_permute): mode 0 (Co, 9 Ci)[co][tap*Ci+ci], mode 1
+    (Ci, 9 Co)[ci][tap*Co+co] = w[co][ci][8-tap]."""
+    Co, Ci = w.shape[0], w.shape[1]
+    if mode == 0:
+        return w.permute(0, 2, 3, 1).reshape(Co, 9 * Ci)
+    return w.flip(2, 3).permute(1, 2, 3, 0).reshape(Ci, 9 * Co)
+
+
 def fold_ref(src, dst):
     """dst (Co,Ci,3,3) fp32 + src (Co, ld)[tap*Ci+ci] fp32: one float32 add per element."""
     Co, Ci = dst.shape[0], dst.shape[1]
@@ -324,7 +333,7 @@ def pool_inputs(case, kind):
     """post_relu: relu of bf16 normals, more than half of the elements exactly zero, so most windows hold ties;
     negative: every element below zero (a maximum that starts from 0 instead of -inf would show)."""
     B, T, Fq, C = case
-    g = gen(4400 + 7 * POOL_CASES.index(case) + POOL_KINDS.index(kind))
+    g = gen(4400 + 7 * (POOL_CASES + [POOL_CASE_STRIDE]).index(case) + POOL_KINDS.index(kind))
     x = bf16(torch.randn(B, T, Fq, C, generator=g))
     x = torch.relu(x - 0.25) if kind == 'post_relu' else -(x.abs() + 0.125)
     x = bf16(x)
@@ -332,7 +341,43 @@ def pool_inputs(case, kind):
     return dict(x=border(x), g=bf16(torch.randn(B, T2, F2, C, generator=g)))
 
 
-LN_SEEDS = {case: 4500 + 7 * i for i, case in enumerate(LN_CASES)}
+# further pooling inputs on one odd-sized image: 'tie0' .. 'tie3' - in every window the maximum stands at scan position k and at
+# every later one, smaller values before it, so the index byte must be k wherever position k lies inside the image; 'neg_inf' - a
+# third of the elements are -inf, whole windows among them (their index byte stays 0)
+POOL_EXTRA_CASE = (2, 5, 7, 8)
+POOL_EXTRA_KINDS = ['tie0', 'tie1', 'tie2', 'tie3', 'neg_inf']
+
+
+def pool_extra_inputs(kind):
+    B, T, Fq, C = POOL_EXTRA_CASE
+    g = gen(4450 + POOL_EXTRA_KINDS.index(kind))
+    T2, F2 = pool_sizes(T, Fq, True)
+    if kind == 'neg_inf':
+        x = bf16(torch.randn(B, T, Fq, C, generator=g))
+        x[torch.rand(B, T, Fq, C, generator=g) < 0.33] = float('-inf')
+        x[0, 0:2, 0:2, :] = float('-inf')
+        x[1, 4, 6, :] = float('-inf')                                 # the one-element corner window of the ceil sizes
+    else:
+        first = int(kind[3])
+        top = bf16(torch.randn(B, T2, F2, C, generator=g))
+        x = torch.zeros(B, 2 * T2, 2 * F2, C, dtype=F64)
+        for k, (dt, df) in enumerate(POOL_SCAN):
+            x[:, dt::2, df::2, :] = top if k >= first else top - 1.0 - k
+        x = bf16(x[:, :T, :Fq, :].contiguous())
+    return dict(x=border(x), g=bf16(torch.randn(B, T2, F2, C, generator=g)))
+
+
+# fp32 kernels only (tests/test_hip_vgg_kernels_vs_float64.py): their grids are capped, and these sizes run past the caps.
+#   LN_CASE_BWD_STRIDE  B T C = 527352 > 512 x 1024 thread slots of asr_ln_freq_bwd: a second pass of its loop by 3 workgroups, the
+#                       last of them with 1016 of its 1024 lanes in range.  F = 8, not 2: dw / db are sums of 527352 terms each,
+#                       torch's float32 error on ONE such sum varies 16-fold with the data (7e-5 .. 1.2e-3 seen on F = 2), and e32
+#                       is the maximum over the F outputs - with two of them the yardstick itself is a lottery
+#   LN_CASE_FWD_STRIDE  B T C = 4198400 > 16384 x 256 threads of asr_ln_freq_fwd (forward only)
+#   POOL_CASE_STRIDE    4259840 outputs and 17039360 inputs against the 16384 x 256 threads of the pooling forward / backward
+LN_CASE_BWD_STRIDE = (8, 129, 8, 511)
+LN_CASE_FWD_STRIDE = (8, 1025, 2, 512)
+POOL_CASE_STRIDE = (16, 130, 64, 128)
+LN_SEEDS = {case: 4500 + 7 * i for i, case in enumerate(LN_CASES + [LN_CASE_BWD_STRIDE, LN_CASE_FWD_STRIDE])}
 
 
 def ln_inputs(case):
@@ -496,7 +541,58 @@ def test_pool_ref(case, kind):
     assert int(interior(pool_ref(t, 1, 1)[1])) == 1
 
 
-@pytest.mark.parametrize('case', LN_CASES)
+def test_pool_extra_inputs():
+    B, T, Fq, C = POOL_EXTRA_CASE
+    assert T % 2 == 1 and Fq % 2 == 1
+    for kind in POOL_EXTRA_KINDS:
+        c = pool_extra_inputs(kind)
+        x = interior(c['x'])
+        assert torch.equal(bf16(x), x)
+        for ceil in (True, False):
+            T2, F2 = pool_sizes(T, Fq, ceil)
+            y, idx = pool_ref(c['x'], T2, F2)
+            yi, ii = interior(y), interior(idx)
+            if kind == 'neg_inf':
+                assert bool((x == float('-inf')).any()) and bool((yi == float('-inf')).any()) and bool((yi > float('-inf')).any())
+                assert bool((ii[yi == float('-inf')] == 0).all())
+                assert not bool(torch.isnan(interior(pool_bwd_ref(border(c['g'][:, :T2, :F2]), idx, T, Fq))).any())
+                continue
+            first = int(kind[3])
+            full = ii[:, :T // 2, :Fq // 2]                             # windows that lie inside the image
+            assert bool((full == first).all()), kind
+            dt, df = POOL_SCAN[first]
+            sub = x[:, dt:2 * T2:2, df:2 * F2:2, :]
+            assert torch.equal(yi[:, :sub.shape[1], :sub.shape[2]], sub)
+            # a scan from the last position down would name the last of the equal maxima instead
+            assert first == 3 or bool((x[:, 1:2 * (T // 2):2, 1:2 * (Fq // 2):2, :] == yi[:, :T // 2, :Fq // 2]).all())
+
+
+def test_pack_unrounded_is_pack_ref_before_rounding():
+    g = gen(5)
+    w = torch.randn(3, 2, 3, 3, generator=g).to(F64)
+    for mode in (0, 1):
+        u = pack_unrounded(w, mode)
+        assert torch.equal(bf16(u), pack_ref(w, mode, u.shape[1])) and not torch.equal(bf16(u), u)
+    assert pack_unrounded(w, 0)[2, 5 * 2 + 1] == w[2, 1, 1, 2] and pack_unrounded(w, 1)[1, 2 * 3 + 2] == w[2, 1, 2, 0]
+    wf = w.to(F32)
+    back = fold_ref(pack_unrounded(wf, 0), torch.zeros(3, 2, 3, 3))
+    assert torch.equal(back, wf)                                       # mode 2 undoes mode 0
+
+
+def test_stride_cases_pass_the_grid_caps():
+    B, T, Fq, C = LN_CASE_BWD_STRIDE
+    assert 512 * 1024 < B * T * C < 2 * 512 * 1024 and (B * T * C) % 1024 == 1016 and 8 <= Fq <= 128
+    B, T, Fq, C = LN_CASE_FWD_STRIDE
+    assert B * T * C > 16384 * 256
+    B, T, Fq, C = POOL_CASE_STRIDE
+    T2, F2 = pool_sizes(T, Fq, True)
+    assert B * T2 * F2 * C > 16384 * 256 and B * T * Fq * C > 16384 * 256
+    # the largest case of the common table stays below the fp32 backward's cap: it is the bordered bf16 form that passes it
+    B, T, Fq, C = LN_CASES[-1]
+    assert B * T * C < 512 * 1024 < B * (T + 2) * C
+
+
+@pytest.mark.parametrize('case', LN_CASES + [LN_CASE_BWD_STRIDE])
 def test_ln_ref_and_gate_band(case):
     """ln_ref against F.layer_norm + autograd in float64; the share of pre-activations within 1e-5 * scale of zero is at most
     0.1 % for the committed seed (elements whose ReLU gate fp32 arithmetic may decide either way), and float32 torch flips a gate
