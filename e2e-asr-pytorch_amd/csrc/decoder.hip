@@ -473,6 +473,9 @@ __global__ __launch_bounds__(256) void dec_greedy_kernel(DecP p, int t) {
     }
 }
 
+// The decode step's vocabulary projection, one workgroup per hypothesis row: every row walks all of Wc, which is the cheaper
+// way only while Wc is small.  Above this V asr_att_decoder_step computes the projection as one contraction over all rows.
+constexpr int DEC_LOGITS_ROW_MAX_V = 2048;
 __global__ __launch_bounds__(256) void dec_logits_kernel(DecP p, int t) {
     const asr_dec_dims_t& d = p.d;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1355,9 +1358,16 @@ extern "C" int asr_att_decoder_step(const asr_dec_dims_t* dims, const asr_dec_we
         if (bf) hipLaunchKernelGGL(dec_cell_fwd_kernel<true>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
         else    hipLaunchKernelGGL(dec_cell_fwd_kernel<false>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
     }
-    // logits only (the arg-max side effect is redirected to a scratch row: t+1 >= L never written)
-    DecP pl = p;
-    hipLaunchKernelGGL(dec_logits_kernel, dim3(d.B), dim3(256), sizeof(float) * d.V, st, pl, t);
+    ASR_LAUNCH_CHECK("asr_att_decoder_step");
+    if (d.V > DEC_LOGITS_ROW_MAX_V) {
+        // word and subword vocabularies: logits[:, t] = hs_top[:, t] Wc^T + bc as ONE contraction over all rows, which reads Wc
+        // once per row tile; the per-row kernel below reads it once per row
+        GemmCall logits{state->hs + ((size_t)t * d.NL + (d.NL - 1)) * d.Dd, weights->Wc, state->logits + (size_t)t * d.V, weights->bc,
+                        d.B, d.V, d.Dd, (long)d.L * d.NL * d.Dd, d.Dd, (long)d.L * d.V};
+        logits.prec = prec;
+        return gemm_run(logits, st);
+    }
+    hipLaunchKernelGGL(dec_logits_kernel, dim3(d.B), dim3(256), 0, st, p, t);
     ASR_LAUNCH_CHECK("asr_att_decoder_step");
     return ASR_OK;
 }

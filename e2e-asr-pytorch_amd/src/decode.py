@@ -220,6 +220,9 @@ class BeamDecoder(nn.Module):
         # the decode kernels of the shipped decoder (asr_att_decoder_step) cover an LSTM of <= MAX_DEC_LAYERS layers with
         # location-aware single-head attention and no value projection, whatever its dropout (inactive in eval); every other
         # model runs the variant search of src/decode_variants.py
+        if self.asr.vocab_size > H.BEAM_WIDE_MAX_V:
+            raise ValueError('the joint beam search takes a vocabulary of at most %d tokens (asr_beam_step_wide), this model has %d'
+                             % (H.BEAM_WIDE_MAX_V, self.asr.vocab_size))
         self.fast = self.asr.decoder.layers.module == 'LSTM' and self.asr.decoder.layer <= H.MAX_DEC_LAYERS and self.asr.attention.fast
         self.apply_ctc = ctc_weight > 0
         if self.apply_ctc:
@@ -609,6 +612,11 @@ class _BeamBook(object):
         self.fin_n, self.fin_len, self.fin_avg = i32(U), i32(U, beam), f32(U, beam)
         self.fin_seq, self.fin_sc = i32(U, beam, Lmax + 1), f32(U, beam, Lmax + 1)
         self.att_lp = f32(R, V)
+        # above the narrow kernels' vocabulary the row-per-workgroup forms do the same two steps; their shortlists live here
+        self.wide = V > H.BEAM_NARROW_MAX_V
+        self.wide_ws = None
+        if self.wide:
+            self.wide_ws = torch.zeros(H.lib().asr_beam_step_wide_workspace_bytes(U, beam), dtype=torch.uint8, device=dev)
 
     def step(self, t, logits):
         """logits (R,V) of output position t -> parent (R) int64: the source row of every surviving row."""
@@ -617,7 +625,7 @@ class _BeamBook(object):
         att_lp = self.att_lp
         H.call('asr_log_softmax', H.ptr(logits), H.ptr(att_lp), R, V, st)
         if bd.apply_ctc:
-            H.call('asr_beam_candidates', H.ptr(att_lp), H.ptr(self.cand), R, V, C, st)
+            H.call('asr_beam_candidates_wide' if self.wide else 'asr_beam_candidates', H.ptr(att_lp), H.ptr(self.cand), R, V, C, st)
             H.call('asr_ctc_prefix_score_batched', H.ptr(self.ctc_lp), H.ptr(self.tlen), H.ptr(self.ctc_r), H.ptr(self.cand), H.ptr(a['len']),
                    H.ptr(self.last_tok), H.ptr(self.psi), H.ptr(self.ctc_rn), R, C, Tp, V, self.beam, st)
         lm_lp = lm_new = None
@@ -637,7 +645,10 @@ class _BeamBook(object):
         args.ctc_weight = float(bd.ctc_w) if bd.apply_ctc else 0.0
         args.lm_weight = float(bd.lm_w) if bd.apply_lm else 0.0
         args.eos_threshold = 1.5
-        H.call('asr_beam_step', ctypes.byref(args), st)
+        if self.wide:
+            H.call('asr_beam_step_wide', ctypes.byref(args), H.ptr(self.wide_ws), self.wide_ws.numel(), st)
+        else:
+            H.call('asr_beam_step', ctypes.byref(args), st)
         if bd.apply_ctc:
             H.call('asr_gather_rows', H.ptr(self.ctc_rn), H.ptr(self.ctc_index), H.ptr(self.ctc_r), R, Tp * 2, Tp * 2, Tp * 2, R * C, st)
         if bd.apply_lm:

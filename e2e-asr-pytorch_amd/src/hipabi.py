@@ -49,6 +49,7 @@ class BeamStep(ctypes.Structure):
 ATT_DOT, ATT_LOC = 0, 1
 BEAM_ATTEND_MAX_ROWS, BEAM_ATTEND_MAX_T = 16, 8192
 CTC_BEAM_MAX = 16                  # ASR_CTC_BEAM_MAX: widest beam of asr_ctc_beam_search
+BEAM_NARROW_MAX_V, BEAM_WIDE_MAX_V = 2048, 65536    # largest vocabulary of asr_beam_step / asr_beam_candidates, and of their _wide forms
 
 
 class BeamAttend(ctypes.Structure):
@@ -135,6 +136,8 @@ SIGNATURES = {
     'asr_beam_candidates': [_vp, _vp, _i, _i, _i, _vp],
     'asr_sample_tokens': [_vp, _l, _vp, _l, _i, _i, _u64, _vp],
     'asr_beam_step': [ctypes.POINTER(BeamStep), _vp],
+    'asr_beam_candidates_wide': [_vp, _vp, _i, _i, _i, _vp],
+    'asr_beam_step_wide': [ctypes.POINTER(BeamStep), _vp, _sz, _vp],
     'asr_beam_attend': [ctypes.POINTER(BeamAttend), _vp],
     'asr_ctc_prefix_init_batched': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'asr_ctc_prefix_score_batched': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -177,6 +180,7 @@ _RESTYPES = {
     'asr_gemm16_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _P(_i)]),
     'asr_lstm16_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_ctc_loss_workspace_bytes': (_sz, [_i, _i, _i]),
+    'asr_beam_step_wide_workspace_bytes': (_sz, [_i, _i]),
     'asr_ctc_beam_search_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_beam_lm_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_align_workspace_bytes': (_sz, [_i, _i, _i]),

@@ -637,6 +637,19 @@ typedef struct {
 int asr_sample_tokens(const float* logits, long ld, int64_t* out, long out_ld, int rows, int V, uint64_t seed, asr_stream_t stream);
 int asr_beam_candidates(const float* att_logp, int* candidates, int rows, int V, int C, asr_stream_t stream);
 int asr_beam_step(const asr_beam_step_t* args, asr_stream_t stream);
+/* The same two steps for word and subword vocabularies, 2 <= V <= 65536 (csrc/decode.hip, "wide"): a multi-wave workgroup owns
+ * a row and strides over V.
+ *   asr_beam_candidates_wide : att_logp.topk(C) per row (src/decode.py:129), 1 <= C <= min(V, 32), in asr_beam_candidates' order
+ *       (descending, the lower token first among equals, token 0 where fewer than C entries are above -inf).
+ *   asr_beam_step_wide : asr_beam_step's argument block and rules (src/decode.py:131-183, Hypothesis.addTopk :214-263), the
+ *       fused score in the same fp32 operation order.  Phase A reduces every live row to its `beam` best (token, score) pairs,
+ *       att[<eos>] and max(att[2:]) in `workspace` (asr_beam_step_wide_workspace_bytes(U, beam) bytes, contents need not
+ *       survive between calls); phase B, one wave per utterance, is asr_beam_step behind its picks.  beam <= 16, C <= 32.
+ * V > 65536 returns ASR_E_UNSUPPORTED; null pointers, other bad dims, psi without candidates and a workspace that is too
+ * small return ASR_E_ARG; nothing is launched then. */
+int asr_beam_candidates_wide(const float* att_logp, int* candidates, int rows, int V, int C, asr_stream_t stream);
+size_t asr_beam_step_wide_workspace_bytes(int U, int beam);
+int asr_beam_step_wide(const asr_beam_step_t* args, void* workspace, size_t workspace_bytes, asr_stream_t stream);
 int asr_ctc_prefix_init_batched(const float* logp, const int* tlen, float* r, int rows, int rows_per_utt, int Tmax, int V,
                                 asr_stream_t stream);
 int asr_ctc_prefix_score_batched(const float* logp, const int* tlen, const float* r_prev, const int* candidates,

@@ -3,7 +3,10 @@ RNN-LM of config/librispeech_lm.yaml (4 x LSTM-1024, tied, random weights) with 
 U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Prints one JSON line.
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
        [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
-       [--ctc-only] [--ctc-lm] [--batch-encode] [--lengths equal|librispeech] [--vgg N] [--rescore]
+       [--ctc-only] [--ctc-lm] [--batch-encode] [--lengths equal|librispeech] [--vgg N] [--rescore] [--vocab N] [--no-lm]
+--vocab N builds the synthetic model and the LM with N tokens instead of the character table's 31 (above 2048 the joint search runs
+asr_beam_candidates_wide / asr_beam_step_wide and the decode step's projection is one contraction); --no-lm leaves the LM out of
+the joint search.
 The model options decode a variant of the config's model (src/decode_variants.py) instead of the shipped one; --lm-module GRU
 fuses a GRU language model of the same dims (csrc/gru_rec.hip) instead of the LSTM one.  --ctc-only decodes the config's
 model built with ctc_weight = 1 (no attention decoder, no LM) by the CTC prefix beam search (csrc/ctc_decode.hip) and also
@@ -41,6 +44,7 @@ ap.add_argument('--lm-module', choices=('LSTM', 'GRU'), default='LSTM')
 ap.add_argument('--ctc-only', action='store_true'); ap.add_argument('--ctc-lm', action='store_true')
 ap.add_argument('--batch-encode', action='store_true'); ap.add_argument('--lengths', choices=('equal', 'librispeech'), default='equal')
 ap.add_argument('--vgg', type=int, choices=range(8)); ap.add_argument('--rescore', action='store_true')
+ap.add_argument('--vocab', type=int, default=31); ap.add_argument('--no-lm', action='store_true')
 a = ap.parse_args()
 torch.manual_seed(0)
 mc = yaml.safe_load(open(a.model_yaml))['model']
@@ -49,12 +53,13 @@ if a.num_head: mc['attention']['num_head'] = a.num_head
 if a.decoder_module: mc['decoder']['module'] = a.decoder_module
 if a.ctc_only: mc['ctc_weight'] = 1
 if a.vgg is not None: mc['encoder']['vgg'] = a.vgg
-model = ASR(160, 31, 1, prec=a.prec, **mc).cuda().eval()
+model = ASR(160, a.vocab, 1, prec=a.prec, **mc).cuda().eval()
 lmc = yaml.safe_load(open(os.path.join(PKG, 'config', 'librispeech_lm.yaml')))['model']
 lmc['module'] = a.lm_module
-lm = RNNLM(31, **lmc).cuda().eval()
+lm = RNNLM(a.vocab, **lmc).cuda().eval()
 dec = BeamDecoder(model, None, beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio, ctc_weight=0.3)
-if not a.ctc_only: dec.set_lm(lm, 0.3)
+with_lm = not a.ctc_only and not a.no_lm
+if with_lm: dec.set_lm(lm, 0.3)
 U, T = a.utts, a.frames
 feat = torch.rand(U, T, 160, device='cuda')
 flen = torch.full((U,), T, dtype=torch.int64, device='cuda')
@@ -127,7 +132,7 @@ if a.rescore:
 if a.batch_encode:
     import statistics
     dec_b = BeamDecoder(model, None, beam_size=a.beam, min_len_ratio=0.01, max_len_ratio=a.max_len_ratio, ctc_weight=0.3, batch_encode=True)
-    if not a.ctc_only: dec_b.set_lm(lm, 0.3)
+    if with_lm: dec_b.set_lm(lm, 0.3)
     def median_ms(fn):
         fn(); torch.cuda.synchronize()                # warm-up: workspaces, packed weights, plans
         ts = []
@@ -136,7 +141,7 @@ if a.batch_encode:
         return statistics.median(ts)
     res = {'metric': 'encoder pass per utterance vs batched, %s' % ('CTC-only model of config 4' if a.ctc_only else 'config 4'),
            'batch_utterances': U, 'lengths': a.lengths, 'frames': flen.tolist() if a.lengths != 'equal' else T, 'beam': a.beam,
-           'prec': a.prec, 'reps': a.reps, 'vgg': mc['encoder']['vgg']}
+           'prec': a.prec, 'reps': a.reps, 'vgg': mc['encoder']['vgg'], 'vocab': a.vocab, 'lm': with_lm}
     for name, d in (('per_utterance', dec), ('batched', dec_b)):
         enc_ms = median_ms(lambda: d._encode(feat, flen))
         dec_ms = median_ms(lambda: d(feat, flen))
@@ -169,7 +174,7 @@ if a.ctc_only:
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     for i in range(1 + 10):
         if i == 1: ev[0].record()
-        H.call('asr_ctc_beam_search', H.ptr(lp), H.ptr(tlen), U, Tp, 31, K, dec.ctc_cand, Tp, H.ptr(toks), H.ptr(lens), H.ptr(score),
+        H.call('asr_ctc_beam_search', H.ptr(lp), H.ptr(tlen), U, Tp, a.vocab, K, dec.ctc_cand, Tp, H.ptr(toks), H.ptr(lens), H.ptr(score),
                H.ptr(n), H.ptr(ws), nb, H.stream_ptr())
     ev[1].record(); torch.cuda.synchronize()
     print(json.dumps({'metric': 'CTC prefix beam search, CTC-only model of config 4', 'utterances_per_s': U / dt, 'ms_per_utterance': dt * 1e3 / U,
@@ -179,7 +184,7 @@ if a.ctc_only:
     sys.exit(0)
 print(json.dumps({'metric': 'beam-search decode, config 4', 'utterances_per_s': U / dt, 'ms_per_utterance': dt * 1e3 / U,
                   'decode_positions_per_s': U * steps / dt, 'batch_utterances': U, 'frames': T, 'max_positions': steps, 'beam': a.beam,
-                  'ctc_weight': 0.3, 'lm': '4x1024 tied, %s' % a.lm_module, 'lm_weight': 0.3, 'path': 'host score table' if a.host else 'device beam step',
+                  'ctc_weight': 0.3, 'vocab': a.vocab, 'lm': ('4x1024 tied, %s' % a.lm_module) if with_lm else None, 'lm_weight': 0.3 if with_lm else 0.0, 'path': 'host score table' if a.host else 'device beam step',
                   'hyps_first_utt': n_hyp, 'prec': a.prec, 'decoder_path': 'fast' if dec.fast else 'variant',
                   'attention': '%s x%d' % (mc['attention']['mode'], mc['attention']['num_head']), 'decoder': mc['decoder']['module'],
                   'reference_cpu_note': 'BASELINE.md: ~1.0 s per T=400 utterance, reference on 8 CPU cores'}))
