@@ -52,7 +52,7 @@ __device__ __forceinline__ void fetch_tile(const float* __restrict__ base, long 
             const int mend = KC ? nrows : kend, kk_end = KC ? kend : nrows;
             if (m < mend && k < kk_end) {
                 float e[4] = {0.f, 0.f, 0.f, 0.f};
-                if ((cC & 3) == 0 && k + 3 < kk_end) {
+                if (vec && (cC & 3) == 0 && k + 3 < kk_end) {   // vec: the image base is 16-byte aligned (gemm_plan)
                     long src;
                     if (conv_tap(m, k / cC, cT, cF, src)) {
                         const float4 t4 = *reinterpret_cast<const float4*>(base + src * cC + (k % cC));
@@ -571,21 +571,45 @@ extern "C" int asr_gemm16_plan(const void* A, const void* B, void* C, const floa
 // 3x3 / stride 1 / pad 1 convolution over channel-last images as an implicit GEMM.
 //   mode 0 (forward / dgrad): out[(b,t,f), n] (+)= act( sum_{tap,ci} img[(b,t+dt,f+df), ci] * w[n][tap*C + ci] + bias[n] )
 //   mode 1 (wgrad)          : dw[n][tap*C + ci] += sum_{(b,t,f)} dout[(b,t,f), n] * img[(b,t+dt,f+df), ci]
-extern "C" int asr_conv3x3(const float* img, const float* w_or_dout, float* out, const float* bias,
-                           int B, int T, int F, int C, int N, int mode, int act, int accum, int prec, asr_stream_t stream) {
+// Argument checks of asr_conv3x3, then its plan (shared by the launch and the asr_conv3x3_plan query).
+static int conv3x3_plan(const float* img, const float* w_or_dout, float* out, const float* bias,
+                        int B, int T, int F, int C, int N, int mode, int act, int accum, int prec, KernelPlan<GemmP>& pl) {
     ASR_REQUIRE(img && w_or_dout && out, ASR_E_ARG, "asr_conv3x3: null pointer");
     ASR_REQUIRE(B > 0 && T > 0 && F > 0 && C > 0 && N > 0, ASR_E_ARG, "asr_conv3x3: bad dims");
+    ASR_REQUIRE(mode == 0 || mode == 1, ASR_E_ARG, "asr_conv3x3: bad mode %d", mode);
+    ASR_REQUIRE(prec == ASR_F32 || prec == ASR_BF16, ASR_E_ARG, "asr_conv3x3: bad prec %d", prec);
+    ASR_REQUIRE(act == ASR_ACT_NONE || act == ASR_ACT_TANH || act == ASR_ACT_RELU, ASR_E_ARG, "asr_conv3x3: bad act %d", act);
+    ASR_REQUIRE(accum == 0 || accum == 1, ASR_E_ARG, "asr_conv3x3: bad accum %d", accum);
     ASR_REQUIRE((long)B * T * F < (1L << 31), ASR_E_UNSUPPORTED, "asr_conv3x3: more than 2^31 pixels");
+    ASR_REQUIRE(9L * C < (1L << 31), ASR_E_UNSUPPORTED, "asr_conv3x3: more than 2^31 / 9 channels");
     const int rows = B * T * F, K9 = 9 * C;
     GemmCall c{img, w_or_dout, out, bias, rows, N, K9, C, K9, N};
-    if (mode != 0) {
+    if (mode == 1) {
         // wgrad: C[i = n, j = (tap,ci)] += sum_r dout[r, i] * conv(img)[r, j]
         ASR_REQUIRE(accum == 1 && act == ASR_ACT_NONE && bias == nullptr, ASR_E_ARG, "asr_conv3x3: wgrad accumulates without epilogue");
         c = gemm_wgrad_call(w_or_dout, img, out, N, K9, rows, N, C, K9, rows >= 65536 ? 32 : (rows >= 4096 ? 8 : 1));
     }
     c.act = act; c.accum = accum; c.prec = prec;
     c.conv_T = T; c.conv_F = F; c.conv_C = C;
-    KernelPlan<GemmP> pl;
     const int rc = gemm_plan(c, false, pl);
+    pl.who = "asr_conv3x3";
+    return rc;
+}
+
+extern "C" int asr_conv3x3(const float* img, const float* w_or_dout, float* out, const float* bias,
+                           int B, int T, int F, int C, int N, int mode, int act, int accum, int prec, asr_stream_t stream) {
+    KernelPlan<GemmP> pl;
+    const int rc = conv3x3_plan(img, w_or_dout, out, bias, B, T, F, C, N, mode, act, accum, prec, pl);
     return rc != ASR_OK ? rc : gemm_launch(pl, (hipStream_t)stream);
+}
+
+// The plan asr_conv3x3 launches with for these arguments (host arithmetic only: nothing is launched, no pointer is followed).
+extern "C" int asr_conv3x3_plan(const float* img, const float* w_or_dout, float* out, const float* bias,
+                                int B, int T, int F, int C, int N, int mode, int act, int accum, int prec, int plan[8]) {
+    ASR_REQUIRE(plan, ASR_E_ARG, "asr_conv3x3_plan: null out");
+    KernelPlan<GemmP> pl;
+    const int rc = conv3x3_plan(img, w_or_dout, out, bias, B, T, F, C, N, mode, act, accum, prec, pl);
+    if (rc != ASR_OK) return rc;
+    for (int i = 0; i < 8; ++i) plan[i] = pl.out[i];
+    return ASR_OK;
 }

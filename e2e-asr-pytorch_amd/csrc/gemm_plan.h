@@ -5,7 +5,8 @@
 //   asr_gemm, asr_gemm_plan, gemm_run (decoder*.hip, frontend.hip)   the fp32 entry's checks, then gemm_plan
 //   asr_gemm16, asr_gemm16_route, asr_gemm16_plan                    the bf16 entry's checks, then the first of gemm16_nt_plan,
 //                                                                    gemm16_tn_plan, gemm_plan (bf16 storage) that takes the call
-//   asr_conv3x3 / asr_conv3x3_16 / asr_conv3x3_16_wgrad (vgg16.hip)  gemm_plan / gemm16_nt_plan / gemm16_tn_plan on a call with conv_F > 0
+//   asr_conv3x3, asr_conv3x3_plan                                    the fp32 convolution entry's checks, then gemm_plan on a call with conv_F > 0
+//   asr_conv3x3_16 / asr_conv3x3_16_wgrad (vgg16.hip)                gemm16_nt_plan / gemm16_tn_plan on a call with conv_F > 0
 // Every entry plans once and launches, or reports, exactly that plan.
 #pragma once
 #include "common.h"

@@ -176,6 +176,7 @@ _RESTYPES = {
     'asr_lstm_set_persistent': (ctypes.c_int, [_i]),
     'asr_lstm_plan': (ctypes.c_int, [_i, _i, _i, _i, _i]),
     'asr_gemm_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _l, _l, _l, _i, _i, _i, _P(_i)]),
+    'asr_conv3x3_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _P(_i)]),
     'asr_gemm16_route': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     'asr_gemm16_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _P(_i)]),
     'asr_lstm16_workspace_bytes': (_sz, [_i, _i, _i, _i]),

@@ -467,9 +467,22 @@ int asr_specaug_ws(float* x, const int64_t* lens, const int* draws_in, int* draw
  * backward writes all of dx, zeros where no window reaches or the element was not the arg-max.
  * asr_ln_freq_* = CNNLayerNorm (LayerNorm over F, affine per f) + optional ReLU; the backward takes F <= 128 (ASR_E_UNSUPPORTED);
  * stats (rows*C, 2).  asr_permute_last2: out[r,b,a] = in[r,a,b] (channel-major <-> channel-last).
+ * asr_conv3x3 refuses, before anything is launched and with `out` untouched: a NULL img / w_or_dout / out or a dim <= 0
+ * (ASR_E_ARG); mode other than 0 or 1, prec other than ASR_F32 / ASR_BF16, act other than ASR_ACT_NONE / _TANH / _RELU, accum
+ * other than 0 or 1 (ASR_E_ARG); mode 1 without accum = 1, with an activation or with a bias (ASR_E_ARG: the weight gradient
+ * is added onto dw, in 8 reduction slices from 4096 pixels and 32 from 65536, by fp32 atomics); B*T*F >= 2^31 or 9*C >= 2^31
+ * (ASR_E_UNSUPPORTED).  The image is read with 16-byte loads where C % 4 == 0 and img is 16-byte aligned, element by
+ * element otherwise; w_or_dout, out and bias need 4-byte alignment only.
+ * asr_conv3x3_plan: the plan asr_conv3x3 launches with for the same arguments (without the stream), the eight entries of
+ * asr_gemm_plan {fastA, fastB, plain_order, nx, ny, nz, gx, ngx} - mode 0: A = the image (fastA = 0), nx = column tiles of
+ * N, ny = tiles of the B*T*F pixels, nz = 1; mode 1: B = the image (fastB = 0), nx = column tiles of 9*C, ny = row tiles of
+ * N, nz = reduction slices.  Host arithmetic from the function the launch itself plans with: no device call, the pointers are
+ * looked at for their alignment only.  Returns what asr_conv3x3 returns for refused arguments (plan untouched).
  */
 int asr_conv3x3(const float* img, const float* w_or_dout, float* out, const float* bias,
                 int B, int T, int F, int C, int N, int mode, int act, int accum, int prec, asr_stream_t stream);
+int asr_conv3x3_plan(const float* img, const float* w_or_dout, float* out, const float* bias,
+                     int B, int T, int F, int C, int N, int mode, int act, int accum, int prec, int plan[8]);
 
 /* ---- bf16 VGG front-end (bf16 contraction mode), csrc/vgg16.hip ----------------------------------------------------
  * The same layers - nn.Conv2d(k 3, stride 1, pad 1) + ReLU / CNNLayerNorm, nn.MaxPool2d(2, 2[, ceil_mode]) of
