@@ -449,26 +449,35 @@ __global__ __launch_bounds__(256) void dec_cell_fwd_kernel(DecP p, int t, int l)
 // ------------------------------------------------------------------------------------------------
 // K5 (greedy decoding only): logits of step t, argmax, next input token.  One block per utterance.
 // ------------------------------------------------------------------------------------------------
+// The arg-max is the LOWEST index among equal logits (torch.argmax on the reference's side): every wave keeps a running
+// (value, index) over the entries it computes - ascending v, strict `>` - and the four waves meet in eight LDS words, so the
+// kernel's LDS does not grow with V.
 __global__ __launch_bounds__(256) void dec_greedy_kernel(DecP p, int t) {
-    extern __shared__ __attribute__((aligned(16))) float smem_f[];  // [V]
+    __shared__ float s_val[4];
+    __shared__ int s_idx[4];
     const asr_dec_dims_t& d = p.d;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* h = p.s.hs + (((long)b * d.L + t) * d.NL + (d.NL - 1)) * d.Dd;
+    float bv = -INFINITY;
+    int bi = -1;                         // -1: the wave owns no entry (V < 4)
     for (int v = wave; v < d.V; v += 4) {
         float acc = 0.f;
         for (int k = lane; k < d.Dd; k += 64) acc += h[k] * p.w.Wc[(long)v * d.Dd + k];
-        acc = wave_sum(acc);
-        if (lane == 0) {
-            acc += p.w.bc[v];
-            smem_f[v] = acc;
-            p.s.logits[((long)b * d.L + t) * d.V + v] = acc;
-        }
+        acc = wave_sum(acc);             // every lane holds the sum
+        acc += p.w.bc[v];
+        if (lane == 0) p.s.logits[((long)b * d.L + t) * d.V + v] = acc;
+        if (bi < 0 || acc > bv) { bv = acc; bi = v; }
     }
+    if (lane == 0) { s_val[wave] = bv; s_idx[wave] = bi; }
     __syncthreads();
     if (threadIdx.x == 0 && t + 1 < d.L) {
-        int best = 0;
-        float bv = smem_f[0];
-        for (int v = 1; v < d.V; ++v) if (smem_f[v] > bv) { bv = smem_f[v]; best = v; }
+        float best_v = s_val[0];         // wave 0 owns entry 0
+        int best = s_idx[0];
+        for (int w = 1; w < 4; ++w) {
+            const float v = s_val[w];
+            const int i = s_idx[w];
+            if (i >= 0 && (v > best_v || (v == best_v && i < best))) { best_v = v; best = i; }
+        }
         p.s.tokens[(long)b * d.L + t + 1] = best;
     }
 }
@@ -1250,6 +1259,15 @@ extern "C" size_t asr_att_decoder_fwd_work_bytes(const asr_dec_dims_t* dims) {
 }
 extern "C" int asr_att_decoder_fwd_plan(const asr_dec_dims_t* dims) { return dims ? dec_fwd_plan_info(*dims).kind : 0; }
 extern "C" int asr_att_decoder_bwd_plan(const asr_dec_dims_t* dims) { return dims ? dec_bwd_plan_info(*dims).kind : 0; }
+// the (KNMAX, TPW) pair launch_energy picks for this shape
+extern "C" int asr_att_decoder_energy_plan(const asr_dec_dims_t* dims, int* knmax, int* tpw) {
+    ASR_REQUIRE(dims && knmax && tpw, ASR_E_ARG, "asr_att_decoder_energy_plan: null pointer");
+    const int rc = check_dims(*dims, "asr_att_decoder_energy_plan");
+    if (rc != ASR_OK) return rc;
+    *knmax = dims->Kn <= 4 ? 4 : (dims->Kn <= 10 ? 10 : 16);
+    *tpw = energy_plan(*dims).tpw;
+    return ASR_OK;
+}
 
 extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights,
                                    const float* enc, const int64_t* enc_len, const int64_t* teacher, int teacher_ld,
@@ -1306,7 +1324,7 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
             if (bf) hipLaunchKernelGGL(dec_cell_fwd_kernel<true>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
             else    hipLaunchKernelGGL(dec_cell_fwd_kernel<false>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
         }
-        if (!teacher) hipLaunchKernelGGL(dec_greedy_kernel, dim3(d.B), dim3(256), sizeof(float) * d.V, st, p, t);
+        if (!teacher) hipLaunchKernelGGL(dec_greedy_kernel, dim3(d.B), dim3(256), 0, st, p, t);
     }
     ASR_LAUNCH_CHECK("asr_att_decoder_fwd");
     if (teacher) {

@@ -106,6 +106,7 @@ SIGNATURES = {
     'asr_permute_last2': [_vp, _vp, _l, _i, _i, _vp],
     'asr_att_decoder_keys': [_P(DecDims), _P(DecWeights), _vp, _vp, _i, _vp],
     'asr_att_decoder_step': [_P(DecDims), _P(DecWeights), _vp, _vp, _P(DecState), _i, _i, _vp],
+    'asr_att_decoder_energy_plan': [_P(DecDims), _P(_i), _P(_i)],
     'asr_ctc_prefix_init': [_vp, _vp, _i, _i, _vp],
     'asr_ctc_prefix_score': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'asr_lstm_cell': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],

@@ -352,6 +352,10 @@ int asr_att_decoder_set_persistent(int flags);
  * 3 400 frames, src/collect_batch.py:21-24, and BASELINE config 5). */
 int asr_att_decoder_fwd_plan(const asr_dec_dims_t* dims);
 int asr_att_decoder_bwd_plan(const asr_dec_dims_t* dims);
+/* Which instantiation of the forward energy kernel the per-step path (asr_att_decoder_fwd without a persistent plan,
+ * asr_att_decoder_step) launches for this shape: *knmax in {4, 10, 16} is the location-filter count it is compiled for,
+ * *tpw in {2, 4, 5, 8} the encoder frames per wave.  Host code only; ASR_E_ARG on a null pointer or dims the step refuses. */
+int asr_att_decoder_energy_plan(const asr_dec_dims_t* dims, int* knmax, int* tpw);
 /* tiles per utterance when asr_att_decoder_bwd runs the whole loop as ONE persistent launch (0: no plan for this shape,
  * the per-step kernels run); offset of that launch's 4 KB status block (abort word first) inside the workspace. */
 int asr_att_decoder_bwd_persistent_tiles(const asr_dec_dims_t* dims);
