@@ -270,6 +270,10 @@ extern "C" int asr_colsum2(const float* A, long lda, int M, int N, float* out, f
     ASR_REQUIRE(A && out && M > 0 && N > 0 && lda >= N, ASR_E_ARG, "asr_colsum: bad args");
     int rows_per_block = 512;                               // small matrices: more, shorter row blocks (about one round of workgroups)
     while (rows_per_block > 32 && (long)cdiv(N, 64) * cdiv(M, rows_per_block) < 1024) rows_per_block >>= 1;
+    // up to 128 rows: ONE row block (32 rows per row group, two trips of the unrolled loop), so each column sum is formed in a
+    // fixed order and added to `out` with a single atomicAdd - one rounding on top of what `out` held, as asr_gemm's accum = 1
+    // with one slice gives the weight gradients of the same small batch.  Row blocks arrive in any order.
+    if (M <= 128) rows_per_block = 128;
     dim3 grid(cdiv(N, 64), cdiv(M, rows_per_block));
     hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, lda, M, N, out, out2, rows_per_block);
     ASR_LAUNCH_CHECK("asr_colsum");

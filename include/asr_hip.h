@@ -246,7 +246,8 @@ int asr_ragged_zero_tail(void* buf, const int64_t* lens, int B, int T, int Ttot,
 
 /* dpre = dout * act'(out) for act in {TANH, RELU} (autograd of torch.tanh / nn.ReLU on the path). */
 int asr_act_bwd(const float* dout, const float* out, float* dpre, long n, int act, asr_stream_t stream);
-/* out[j] += sum_i A[i*lda + j]  (bias gradients). */
+/* out[j] += sum_i A[i*lda + j]  (bias gradients).  M <= 128: the sum is formed in a fixed order and added to out[j] once;
+ * larger M: row blocks add their partial sums atomically, in any order. */
 int asr_colsum(const float* A, long lda, int M, int N, float* out, asr_stream_t stream);
 /* the same sums added to two vectors (an LSTM's bias_ih and bias_hh gradients are the same column sums); out2 may be NULL */
 int asr_colsum2(const float* A, long lda, int M, int N, float* out, float* out2, asr_stream_t stream);
