@@ -1,5 +1,5 @@
 // CTC forced alignment: the most probable alignment of a KNOWN transcript to the CTC posteriors (Viterbi), the fourth
-// member of the CTC kernel family beside the loss (ctc.hip), the prefix scorer (decode.hip) and the prefix beam search
+// member of the CTC kernel family beside the loss (ctc.hip), the prefix scorer (ctc_prefix.hip) and the prefix beam search
 // (ctc_decode.hip).  No reference counterpart: the reference never aligns.
 //
 // Lattice of the loss: l' = (0, y1, 0, y2, ..., yL, 0), S = 2L+1 states, blank = 0.  Max-plus recursion

@@ -617,6 +617,18 @@ class _BeamBook(object):
         self.wide_ws = None
         if self.wide:
             self.wide_ws = torch.zeros(H.lib().asr_beam_step_wide_workspace_bytes(U, beam), dtype=torch.uint8, device=dev)
+        # the step's arguments: everything but the state pointers (swapped per step), lm_logp and t is set here, once
+        self.args = args = H.BeamStep()
+        for name, ten in (('att_logp', self.att_lp), ('psi', self.psi), ('candidates', self.cand), ('last_token', self.last_tok),
+                          ('parent', self.parent), ('ctc_index', self.ctc_index), ('tokens', tokens), ('min_len', self.min_len_d),
+                          ('max_len', self.max_len_d), ('done', self.done), ('fin_n', self.fin_n), ('fin_len', self.fin_len),
+                          ('fin_avg', self.fin_avg), ('fin_seq', self.fin_seq), ('fin_score', self.fin_sc)):
+            setattr(args, name, ten.data_ptr() if ten is not None else None)
+        args.tokens_ld = tokens.shape[1]
+        args.U, args.beam, args.V, args.C, args.Lmax = U, beam, V, self.C, Lmax
+        args.ctc_weight = float(bd.ctc_w) if bd.apply_ctc else 0.0
+        args.lm_weight = float(bd.lm_w) if bd.apply_lm else 0.0
+        args.eos_threshold = 1.5
 
     def step(self, t, logits):
         """logits (R,V) of output position t -> parent (R) int64: the source row of every surviving row."""
@@ -631,20 +643,12 @@ class _BeamBook(object):
         lm_lp = lm_new = None
         if bd.apply_lm:
             lm_lp, lm_new = bd.lm.step(self.tokens[:, t].contiguous(), self.lm_state)
-        args = H.BeamStep()
-        for name, ten in (('att_logp', att_lp), ('lm_logp', lm_lp), ('psi', self.psi), ('candidates', self.cand), ('alive_in', a['alive']),
-                          ('sum_in', a['sum']), ('ctcp_in', a['ctcp']), ('len_in', a['len']), ('seq_in', a['seq']), ('score_in', a['sc']),
-                          ('alive_out', b['alive']), ('sum_out', b['sum']), ('ctcp_out', b['ctcp']), ('len_out', b['len']),
-                          ('seq_out', b['seq']), ('score_out', b['sc']), ('last_token', self.last_tok), ('parent', self.parent),
-                          ('ctc_index', self.ctc_index), ('tokens', self.tokens), ('min_len', self.min_len_d), ('max_len', self.max_len_d),
-                          ('done', self.done), ('fin_n', self.fin_n), ('fin_len', self.fin_len), ('fin_avg', self.fin_avg),
-                          ('fin_seq', self.fin_seq), ('fin_score', self.fin_sc)):
-            setattr(args, name, ten.data_ptr() if ten is not None else None)
-        args.tokens_ld = self.tokens.shape[1]
-        args.U, args.beam, args.V, args.C, args.Lmax, args.t = self.U, self.beam, V, C, self.Lmax, t
-        args.ctc_weight = float(bd.ctc_w) if bd.apply_ctc else 0.0
-        args.lm_weight = float(bd.lm_w) if bd.apply_lm else 0.0
-        args.eos_threshold = 1.5
+        args = self.args
+        for key, name in (('alive', 'alive'), ('sum', 'sum'), ('ctcp', 'ctcp'), ('len', 'len'), ('seq', 'seq'), ('sc', 'score')):
+            setattr(args, name + '_in', a[key].data_ptr())
+            setattr(args, name + '_out', b[key].data_ptr())
+        args.lm_logp = lm_lp.data_ptr() if lm_lp is not None else None
+        args.t = t
         if self.wide:
             H.call('asr_beam_step_wide', ctypes.byref(args), H.ptr(self.wide_ws), self.wide_ws.numel(), st)
         else:

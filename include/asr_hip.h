@@ -655,7 +655,7 @@ typedef struct {
 int asr_sample_tokens(const float* logits, long ld, int64_t* out, long out_ld, int rows, int V, uint64_t seed, asr_stream_t stream);
 int asr_beam_candidates(const float* att_logp, int* candidates, int rows, int V, int C, asr_stream_t stream);
 int asr_beam_step(const asr_beam_step_t* args, asr_stream_t stream);
-/* The same two steps for word and subword vocabularies, 2 <= V <= 65536 (csrc/decode.hip, "wide"): a multi-wave workgroup owns
+/* The same two steps for word and subword vocabularies, 2 <= V <= 65536 (csrc/beam_step.hip, "wide"): a multi-wave workgroup owns
  * a row and strides over V.
  *   asr_beam_candidates_wide : att_logp.topk(C) per row (src/decode.py:129), 1 <= C <= min(V, 32), in asr_beam_candidates' order
  *       (descending, the lower token first among equals, token 0 where fewer than C entries are above -inf).

@@ -1,5 +1,6 @@
 """CPU restatement of the reference's INFERENCE leg - TEST INFRASTRUCTURE ONLY (imported by tests/ alone; the product path is
-e2e-asr-pytorch_amd/src/decode.py on the decode kernels of csrc/decode.hip and never touches this file).
+e2e-asr-pytorch_amd/src/decode.py on the decode kernels of csrc/beam_step.hip, csrc/ctc_prefix.hip and csrc/decode.hip and never
+touches this file).
 
   ctc_prefix_init / ctc_prefix_cheap : CTCPrefixScore.init_state / cheap_compute       reference src/ctc.py:19-27, 68-107
   rnnlm_step                         : RNNLM.forward for one token (eval mode)         reference src/lm.py:27-38

@@ -1,4 +1,5 @@
-"""The yardstick of the attention beam search's bookkeeping kernels (csrc/decode.hip): a plain numpy restatement of
+"""The yardstick of the attention beam search's bookkeeping kernels (csrc/beam_step.hip, csrc/ctc_prefix.hip,
+csrc/decode.hip): a plain numpy restatement of
 asr_beam_candidates, asr_ctc_prefix_{init,score}[_batched], asr_beam_step, asr_sample_tokens, asr_lstm_cell and
 asr_gather_rows, with its own checks.  tests/test_hip_beam_step.py imports the restatement, the cases and their generator
 from this file; nothing here imports the code under test except the export check at the end.

@@ -1,4 +1,4 @@
-"""Cases of the wide bookkeeping kernels (csrc/decode.hip: asr_beam_candidates_wide, asr_beam_step_wide; 2048 < V <= 65536),
+"""Cases of the wide bookkeeping kernels (csrc/beam_step.hip: asr_beam_candidates_wide, asr_beam_step_wide; 2048 < V <= 65536),
 held to the SAME yardstick as the narrow ones: R.beam_step, R.beam_candidates, R.init_state, R.log_softmax32 and
 R.candidate_gap of tests/test_beam_step_reference.py.  Nothing is added to R.CASES - the existing files parametrize over
 that dict at collection - so this file keeps its own table, its own table generator and its own drive (copies of the few
@@ -169,7 +169,7 @@ def test_the_table_covers_what_it_must():
 
 
 def test_constants_are_the_kernels():
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'e2e-asr-pytorch_amd', 'csrc', 'decode.hip')).read()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'e2e-asr-pytorch_amd', 'csrc', 'beam_step.hip')).read()
     const = lambda n: int(re.search(r'\b%s = (\d+)\b' % n, src).group(1))
     assert (const('WIDE_NT'), const('WIDE_BITS'), const('WIDE_VMAX'), const('WIDE_CMAX')) == (WIDE_NT, WIDE_BITS, WIDE_VMAX, WIDE_CMAX)
     assert const('VPL') * WAVE == NARROW_VMAX

@@ -1,4 +1,5 @@
-"""The beam-search bookkeeping kernels of csrc/decode.hip, each on its own, against the float64 restatement of
+"""The beam-search bookkeeping kernels of csrc/beam_step.hip, csrc/ctc_prefix.hip and csrc/decode.hip, each on its own,
+against the float64 restatement of
 tests/test_beam_step_reference.py: asr_beam_step, asr_beam_candidates, asr_ctc_prefix_{init,score}[_batched], asr_lstm_cell,
 asr_gather_rows and asr_sample_tokens, driven through src.hipabi on hand-built buffers - no model anywhere.
 
@@ -389,6 +390,29 @@ def test_ctc_prefix_score_batched(Tmax, V, rpu, C):
     H.call('asr_ctc_prefix_init_batched', H.ptr(xd), H.ptr(td), r0.ptr(), N, rpu, Tmax, V, H.stream_ptr())
     torch.cuda.synchronize()
     assert rel_dev(r0.host(), R.ctc_prefix_init_batched(x, tlen, rpu, N)) <= TOL_FACTOR * CTC_DEV
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('T,V,N,C', CTC_SINGLE)
+def test_ctc_prefix_single_is_the_batched_scorer_on_one_utterance(T, V, N, C):
+    """asr_ctc_prefix_score / _init and the batched entries with U = 1, rows_per_utt = N, tlen = [T] run one body
+    (csrc/ctc_prefix.hip): psi, r_out and r0 bit for bit identical, guards intact."""
+    from src import hipabi as H
+    (x, plen, last, cand, r_prev), _, _ = ctc_single_case(T, V, N, C, np.float64)
+    d = lambda a: torch.from_numpy(a).cuda()
+    xd, td, pd, ld, cd, rd, st = d(x), d(np.array([T], dtype=np.int32)), d(plen), d(last), d(cand), d(r_prev), H.stream_ptr()
+    psi = [Guarded((N, C), torch.float32) for _ in range(2)]
+    r_out = [Guarded((N, C, T, 2), torch.float32) for _ in range(2)]
+    r0 = [Guarded((1, T, 2), torch.float32) for _ in range(2)]
+    H.call('asr_ctc_prefix_score', H.ptr(xd), H.ptr(rd), H.ptr(cd), H.ptr(pd), H.ptr(ld), psi[0].ptr(), r_out[0].ptr(), N, C, T, V, st)
+    H.call('asr_ctc_prefix_score_batched', H.ptr(xd), H.ptr(td), H.ptr(rd), H.ptr(cd), H.ptr(pd), H.ptr(ld), psi[1].ptr(), r_out[1].ptr(),
+           N, C, T, V, N, st)
+    H.call('asr_ctc_prefix_init', H.ptr(xd), r0[0].ptr(), T, V, st)
+    H.call('asr_ctc_prefix_init_batched', H.ptr(xd), H.ptr(td), r0[1].ptr(), 1, N, T, V, st)
+    torch.cuda.synchronize()
+    for what, (a, b) in (('psi', psi), ('r_out', r_out), ('r0', r0)):
+        ha, hb = a.host(), b.host()
+        assert (ha.view(np.uint32) == hb.view(np.uint32)).all(), (what, np.argwhere(ha != hb)[:4].tolist())
 
 
 CHAIN = dict(T=37, V=31, C=6, rpu=2, picks=[(2, 0, 5, 3, 1, 4), (1, 1, 0, 5, 2, 3)])

@@ -1,4 +1,4 @@
-"""The joint beam search above V = 2048 on the device: asr_beam_candidates_wide and asr_beam_step_wide (csrc/decode.hip) on
+"""The joint beam search above V = 2048 on the device: asr_beam_candidates_wide and asr_beam_step_wide (csrc/beam_step.hip) on
 canary-bordered buffers against the float64 restatement of tests/test_beam_step_reference.py over the cases of
 tests/test_beam_step_wide_reference.py; the narrow kernels' cases through the wide entries; the refusals; BeamDecoder end to
 end at V = 2100 and V = 5000 against oracle/decode_oracle.py; and the vocabulary projection of asr_att_decoder_step.
@@ -125,16 +125,28 @@ def _narrow_fp32_dev(name):
 
 @pytest.mark.parametrize('name', ['v2047_b8_ctc', 'v2048_b16_lm', 'tie_v2048_b16'])
 def test_narrow_cases_through_the_wide_entries(name):
-    """Where both kernels apply they must decide alike: integers identical to asr_beam_step's, scores within the bound (bit
-    equality is not asked: the narrow kernel's fused score may be contracted)."""
+    """Where both kernels apply they must decide alike, and they evaluate the fused score in one function (BeamFuse,
+    csrc/beam_step.hip): integers identical to asr_beam_step's, the float outputs of the live rows and of the filled finals bit
+    for bit identical, and the scores within the bound."""
     c = R.CASES[name]
     ref = N.reference(name)
     args = (c, R.case_dims(name), R.case_state0(name), lambda t: R.case_tables(name, t), lambda t: R.case_params(name, t), ref)
     narrow, _ = drive(False, *args)
     wide, dev = drive(True, *args)
-    for a, b in zip(narrow, wide):
+    for t, (a, b) in enumerate(zip(narrow, wide)):
         for k in ('alive', 'len', 'seq', 'last_tok', 'parent', 'ctcidx', 'tokens', 'done', 'fin_n', 'fin_len', 'fin_seq'):
             assert (a[k] == b[k]).all(), k
+        live = a['alive'] == 1
+        for k in ('sum', 'ctcp'):
+            assert (a[k][live] == b[k][live]).all(), (t, k)
+        for r in np.nonzero(live)[0]:
+            n = int(a['len'][r])
+            assert (a['sc'][r, :n] == b['sc'][r, :n]).all(), (t, 'sc', r)
+        for u in range(len(a['fin_n'])):
+            for i in range(int(a['fin_n'][u])):
+                n = int(a['fin_len'][u, i])
+                assert a['fin_avg'][u, i] == b['fin_avg'][u, i], (t, 'fin_avg', u, i)
+                assert (a['fin_sc'][u, i, :n] == b['fin_sc'][u, i, :n]).all(), (t, 'fin_sc', u, i)
     allowed = TOL_FACTOR * _narrow_fp32_dev(name)
     print('%s through the wide entry: deviation %.3g (allowed %.3g)' % (name, dev, allowed))
     assert dev <= allowed
