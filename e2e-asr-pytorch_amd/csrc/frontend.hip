@@ -8,6 +8,8 @@
 //                     the order-k delta filters, zero padding at the utterance ends, channel-major stacking.
 //   asr_specaug     : Augment (src/audio.py:364-406): one time mask and one frequency mask per utterance,
 //                     filled with the mean (recomputed after the time mask), in place on the padded batch.
+//   asr_cmvn        : CMVN.forward (src/audio.py:31-34) between Delta and Augment: every column of an utterance minus its mean
+//                     over the valid frames, over (eps + unbiased standard deviation), in place on the padded batch.
 // Every length is taken as min(length, padded extent).  An utterance shorter than the time-mask width, or a feature axis
 // narrower than the frequency-mask width, draws its mask width below its own extent (specaug_draws); the reference raises there.
 #include "common.h"
@@ -225,6 +227,112 @@ __global__ __launch_bounds__(256) void specaug_apply_kernel(float* __restrict__ 
     }
 }
 
+// ---- CMVN (asr_cmvn): per utterance and column, over the len valid frames, y = (x - mean) / (eps + unbiased std).  Two launches
+// over CM_SPLIT x ceil(D / CM_COLS) workgroups per utterance.  Partial sp owns rows [sp R, min((sp + 1) R, len)), R = ceil(T /
+// CM_SPLIT); a thread owns one column (a wave reads 64 neighbouring floats of a row) and every CM_LANES-th row of the range.
+//   moments: float64 Welford (count, mean, M2) per thread, the CM_LANES states of a column merged in lane order (Chan), the
+//            partial's (mean, M2) stored at its fixed slot part[((b CM_SPLIT + sp) 2 + {0,1}) D + d]; its count follows from len.
+//   apply  : every workgroup merges the non-empty partials of its columns in sp order and normalises its own rows in place.
+// No sum of squares is ever formed: M2 is a sum of non-negative terms w (difference)^2, so nothing cancels.  No atomics, fixed
+// merge order: two calls on one input give the same bits.  Rows >= len are neither read nor written.
+constexpr int CM_SPLIT = 16;
+constexpr int CM_COLS = 64;
+constexpr int CM_LANES = 4;
+constexpr int CM_BATCH = 8;      // rows a thread loads before it uses them: one memory round trip per batch, not per row
+
+// (na, ma, Ma) <- (na, ma, Ma) + (nb, mb, Mb); an empty side leaves the other as it is
+__device__ __forceinline__ void cmvn_merge(int& na, double& ma, double& Ma, int nb, double mb, double Mb) {
+    if (nb == 0) return;
+    if (na == 0) { na = nb; ma = mb; Ma = Mb; return; }
+    const double f = (double)nb / (double)(na + nb), d = mb - ma;       // the one division: counts only, off the data's chain
+    ma += d * f;
+    Ma += Mb + d * d * (double)na * f;
+    na += nb;
+}
+
+// rows lane w of a partial with `rows` rows owns: w, w + CM_LANES, ...
+__device__ __forceinline__ int cmvn_lane_rows(int rows, int w) { return rows > w ? (rows - w + CM_LANES - 1) / CM_LANES : 0; }
+
+__global__ __launch_bounds__(CM_COLS * CM_LANES) void cmvn_moments_kernel(const float* __restrict__ x, const int64_t* __restrict__ lens,
+                                                                           double* __restrict__ part, int B, int T, int D) {
+    __shared__ double s_mean[CM_LANES][CM_COLS], s_m2[CM_LANES][CM_COLS];
+    const int ntile = (D + CM_COLS - 1) / CM_COLS;
+    const int sp = blockIdx.x / ntile, b = blockIdx.y, c = threadIdx.x % CM_COLS, w = threadIdx.x / CM_COLS;
+    const int d = (blockIdx.x % ntile) * CM_COLS + c;
+    const int len = (int)max(min(lens[b], (int64_t)T), (int64_t)0);
+    const int R = (T + CM_SPLIT - 1) / CM_SPLIT;
+    const int r0 = sp * R, r1 = min(len, r0 + R);
+    if (r0 >= r1) return;                                       // an empty partial: its slot is never read
+    int n = 0;
+    double mean = 0.0, m2 = 0.0;
+    if (d < D) {
+        const float* xc = x + (long)b * T * D + d;
+        for (int t = r0 + w; t < r1; t += CM_LANES * CM_BATCH) {
+            float v[CM_BATCH];
+#pragma unroll
+            for (int j = 0; j < CM_BATCH; ++j) v[j] = (t + j * CM_LANES < r1) ? xc[(long)(t + j * CM_LANES) * D] : 0.f;
+#pragma unroll
+            for (int j = 0; j < CM_BATCH; ++j) {
+                if (t + j * CM_LANES < r1) {
+                    const double dl = (double)v[j] - mean;
+                    mean += dl / (double)(++n);
+                    m2 += dl * ((double)v[j] - mean);
+                }
+            }
+        }
+    }
+    s_mean[w][c] = mean;
+    s_m2[w][c] = m2;
+    __syncthreads();
+    if (w == 0 && d < D) {
+        for (int k = 1; k < CM_LANES; ++k) cmvn_merge(n, mean, m2, cmvn_lane_rows(r1 - r0, k), s_mean[k][c], s_m2[k][c]);
+        double* p = part + ((long)b * CM_SPLIT + sp) * 2 * D + d;
+        p[0] = mean;
+        p[D] = m2;
+    }
+}
+
+__global__ __launch_bounds__(CM_COLS * CM_LANES) void cmvn_apply_kernel(float* __restrict__ x, const int64_t* __restrict__ lens,
+                                                                         const double* __restrict__ part, float* __restrict__ stats,
+                                                                         int B, int T, int D, float eps) {
+    const int ntile = (D + CM_COLS - 1) / CM_COLS;
+    const int sp = blockIdx.x / ntile, b = blockIdx.y, c = threadIdx.x % CM_COLS, w = threadIdx.x / CM_COLS;
+    const int d = (blockIdx.x % ntile) * CM_COLS + c;
+    if (d >= D) return;
+    const int len = (int)max(min(lens[b], (int64_t)T), (int64_t)0);
+    const int R = (T + CM_SPLIT - 1) / CM_SPLIT;
+    const int r0 = sp * R, r1 = min(len, r0 + R);
+    const bool writes_stats = stats && sp == 0 && w == 0;
+    if (len <= 0) {
+        if (writes_stats) { stats[(long)b * 2 * D + d] = 0.f; stats[((long)b * 2 + 1) * D + d] = 0.f; }
+        return;
+    }
+    if (r0 >= r1) return;
+    int n = 0;
+    double mean = 0.0, m2 = 0.0;
+    double pm[CM_SPLIT], pq[CM_SPLIT];
+#pragma unroll
+    for (int q = 0; q < CM_SPLIT; ++q) {                       // every load first, then the merges in range order
+        const double* p = part + ((long)b * CM_SPLIT + q) * 2 * D + d;
+        pm[q] = (q * R < len) ? p[0] : 0.0;
+        pq[q] = (q * R < len) ? p[D] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < CM_SPLIT; ++q) cmvn_merge(n, mean, m2, max(min(len, (q + 1) * R) - q * R, 0), pm[q], pq[q]);
+    const double sd = sqrt(m2 / (double)(len - 1));            // len == 1: 0 / 0, NaN as torch.std gives it
+    if (writes_stats) { stats[(long)b * 2 * D + d] = (float)mean; stats[((long)b * 2 + 1) * D + d] = (float)sd; }
+    const double den = (double)eps + sd;
+    float* xc = x + (long)b * T * D + d;
+    for (int t = r0 + w; t < r1; t += CM_LANES * CM_BATCH) {
+        float v[CM_BATCH];
+#pragma unroll
+        for (int j = 0; j < CM_BATCH; ++j) v[j] = (t + j * CM_LANES < r1) ? xc[(long)(t + j * CM_LANES) * D] : 0.f;
+#pragma unroll
+        for (int j = 0; j < CM_BATCH; ++j)
+            if (t + j * CM_LANES < r1) xc[(long)(t + j * CM_LANES) * D] = (float)(((double)v[j] - mean) / den);
+    }
+}
+
 inline int grid_for(long n) { long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
 
 }  // namespace
@@ -297,5 +405,23 @@ extern "C" int asr_specaug_ws(float* x, const int64_t* lens, const int* draws_in
     hipLaunchKernelGGL(specaug_apply_kernel, dim3(8, B), dim3(256), 0, st, x, lens, draws_in, (const double*)workspace, B, T, D,
                        time_width, freq_width, seed);
     ASR_LAUNCH_CHECK("asr_specaug_ws");
+    return ASR_OK;
+}
+
+extern "C" size_t asr_cmvn_workspace_bytes(int B, int D) {
+    return (size_t)(B > 0 ? B : 0) * CM_SPLIT * 2 * (size_t)(D > 0 ? D : 0) * sizeof(double);
+}
+
+extern "C" int asr_cmvn(float* x, const int64_t* lens, float* stats_out, int B, int T, int D, float eps,
+                        void* workspace, size_t workspace_bytes, asr_stream_t stream) {
+    ASR_REQUIRE(x && lens && workspace && B > 0 && T > 0 && D > 0, ASR_E_ARG, "asr_cmvn: bad args");
+    ASR_REQUIRE(B <= 65535, ASR_E_ARG, "asr_cmvn: B = %d is beyond one grid axis", B);
+    ASR_REQUIRE(workspace_bytes >= asr_cmvn_workspace_bytes(B, D) && ((uintptr_t)workspace & 7) == 0, ASR_E_ARG,
+                "asr_cmvn: workspace too small or unaligned");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(CM_SPLIT * ((D + CM_COLS - 1) / CM_COLS), B), block(CM_COLS * CM_LANES);
+    hipLaunchKernelGGL(cmvn_moments_kernel, grid, block, 0, st, x, lens, (double*)workspace, B, T, D);
+    hipLaunchKernelGGL(cmvn_apply_kernel, grid, block, 0, st, x, lens, (const double*)workspace, stats_out, B, T, D, eps);
+    ASR_LAUNCH_CHECK("asr_cmvn");
     return ASR_OK;
 }

@@ -1,5 +1,5 @@
 """GPU acoustic front-end with the reference's module names (src/audio.py): ExtractAudioFeature (fbank),
-Delta, Postprocess, Augment (SpecAugment), create_transform.  Unlike the reference — one utterance at a
+Delta, CMVN, Postprocess, Augment (SpecAugment), create_transform.  Unlike the reference — one utterance at a
 time on CPU DataLoader workers — these modules take a zero-padded BATCH on the device plus lengths and run
 the HIP kernels of csrc/frontend.hip.  Only constant tables (window, DFT basis, mel filterbank, delta
 filters) are built on the host."""
@@ -123,6 +123,28 @@ class Delta(nn.Module):
         return out, lens
 
 
+class CMVN(nn.Module):
+    """Per-utterance mean / variance normalisation (src/audio.py:14-37), in place on the padded batch: every column of an
+    utterance over its own valid frames, (x - mean) / (eps + unbiased std)."""
+
+    def __init__(self, mode='global', dim=2, eps=1e-10):
+        super().__init__()
+        if mode != 'global':
+            raise NotImplementedError('Only support global mean variance normalization.')
+        self.mode, self.dim, self.eps = mode, dim, eps
+
+    def forward(self, x, lens):
+        B, T, D = x.shape
+        lens = lens.to(x.device, torch.int64).contiguous()
+        nbytes = H.lib().asr_cmvn_workspace_bytes(B, D)
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+        H.call('asr_cmvn', H.ptr(x), H.ptr(lens), None, B, T, D, self.eps, H.ptr(ws), nbytes, H.stream_ptr())
+        return x, lens
+
+    def extra_repr(self):
+        return 'mode={}, dim={}, eps={}'.format(self.mode, self.dim, self.eps)
+
+
 class Postprocess(nn.Module):
     """Kept for name compatibility: the HIP front-end already emits the (T, C*F) layout."""
 
@@ -167,14 +189,15 @@ def create_transform(audio_config, mode='train'):
     cfg = dict(audio_config)
     delta_order = cfg.pop('delta_order', 0)
     delta_window = cfg.pop('delta_window_size', 2)
-    if cfg.pop('apply_cmvn', False):
-        raise NotImplementedError('CMVN is not part of the HIP front-end')
+    apply_cmvn = cfg.pop('apply_cmvn', False)
     feat_type, feat_dim = cfg.pop('feat_type'), cfg.pop('feat_dim')
     augment = cfg.pop('augment', False)
     cfg.pop('time_aug', False)
     stages = [ExtractAudioFeature(mode=feat_type, num_mel_bins=feat_dim, sample_rate=SAMPLE_RATE, **cfg)]
     if delta_order >= 1:
         stages.append(Delta(delta_order, delta_window))
+    if apply_cmvn:
+        stages.append(CMVN())
     stages.append(Postprocess())
     if augment and mode == 'train':
         stages.append(Augment())

@@ -444,6 +444,18 @@ int asr_embedding_bwd(const float* dy, long dy_ld, const int64_t* idx, float* de
  *     mean after that fill;
  *   - caller-supplied draws_in are clamped into the utterance before use: t0 to [0, len], tend to [t0, len], f0 to [0, D],
  *     fend to [f0, D]; t == 0 / f == 0 switch the band off as in the reference.  No draw can store outside len x D.
+ *   asr_cmvn: CMVN.forward (src/audio.py:31-34, mode 'global', placed after Delta and before Postprocess / Augment by
+ *     create_transform :477-478), in place on x (B,T,D) fp32 using lens: with len = min(lens[b], T), every column d of
+ *     utterance b becomes (x - mean) / (eps + std), mean and std over its len valid frames only, std the unbiased one
+ *     (divisor len - 1), eps added to the standard deviation.  Two launches on `stream`, no host sync, no atomics: 16 workgroups
+ *     per utterance and 64-column tile form float64 (count, mean, M2) moments over disjoint frame ranges (Welford per thread, Chan
+ *     merges in a fixed order, no sum of squares), the second launch merges them in range order and normalises in float64,
+ *     rounding once to fp32.  Two calls on the same input give the same bits.  workspace: asr_cmvn_workspace_bytes(B, D)
+ *     bytes, 8-byte aligned, contents irrelevant.  stats_out (B,2,D) or NULL: [b,0,d] = mean, [b,1,d] = unbiased std, fp32-rounded.
+ *     Edges: rows t >= len are neither read nor written; len <= 0 leaves the utterance alone (stats_out entries 0);
+ *     len == 1 turns the valid row into NaN as the reference does (0 / (eps + NaN); stats_out std NaN, mean the row itself);
+ *     a constant column gives exactly 0.  Refused with ASR_E_ARG, nothing launched: a null x, lens or workspace, B, T or D <= 0,
+ *     B > 65535, workspace_bytes below asr_cmvn_workspace_bytes(B, D), a workspace that is not 8-byte aligned.
  */
 size_t asr_fbank_workspace_bytes(int B, int T, int win, int n_fft);
 int asr_fbank(const float* wav, const int64_t* wav_len, float* out, const float* dft_table, const float* mel_fb,
@@ -458,6 +470,9 @@ int asr_specaug(float* x, const int64_t* lens, const int* draws_in, int* draws_o
 size_t asr_specaug_workspace_bytes(int B);
 int asr_specaug_ws(float* x, const int64_t* lens, const int* draws_in, int* draws_out, int B, int T, int D,
                    int time_width, int freq_width, uint64_t seed, void* workspace, size_t workspace_bytes, asr_stream_t stream);
+size_t asr_cmvn_workspace_bytes(int B, int D);
+int asr_cmvn(float* x, const int64_t* lens, float* stats_out /* (B,2,D) mean, std or NULL */, int B, int T, int D, float eps,
+             void* workspace, size_t workspace_bytes, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * VGG front-ends (VGGExtractor src/module.py:659-716, VGGExtractor_LN :582-657) on channel-last images
