@@ -10,7 +10,9 @@ prefix beam search instead, the whole search of all utterances in ONE launch (as
 an RNN-LM (shallow fusion) by the resumable form of that search, which stops whenever a new prefix needs an LM step
 (asr_ctc_beam_lm_advance).  The reference has no counterpart (`# ToDo : implement pure ctc decode`).  A joint model built
 with rescore=True is decoded in two passes: that CTC search proposes the n-best list, the attention decoder scores the
-hypotheses teacher-forced in one batched pass, and asr_rescore_nbest (csrc/rescore.hip) mixes the scores and re-ranks."""
+hypotheses teacher-forced in one batched pass, and asr_rescore_nbest (csrc/rescore.hip) mixes the scores and re-ranks.  With
+lm_rescore=True an RNN-LM scores that list too, teacher-forced by its full-sequence forward (asr_rescore_token_logp,
+asr_rescore_rank_lm), and stays out of the first pass."""
 import ctypes
 import math
 
@@ -33,6 +35,7 @@ EOS = 1
 # streamed decoder plan takes at once (csrc/decoder_plan.h: B <= 64).
 RESCORE_STATE_BYTES = 1 << 30
 RESCORE_MAX_ROWS = 64
+SOS = 0                     # what the LM sees in front of every sequence (RNNLM's convention: _search_ctc_lm starts its rows with it)
 
 
 def encode_unpadded(asr, audio_feature, feature_len, with_ctc):
@@ -161,12 +164,14 @@ class CTCHypothesis(object):
     emits one) and its score.  CTC gives a sequence no per-token scores, so avgScore() IS the sequence score (not divided by
     the length) - the quantity the search ranks by: the sequence's CTC log-probability `ctc_score`, plus with an LM
     lm_weight * its LM log-probability + len_bonus * its length.  After two-pass decoding (rescore=True) `score` is the mixed
-    score the list was re-ranked by and `att_score` the attention decoder's log-probability of the sequence and its <eos>."""
+    score the list was re-ranked by and `att_score` the attention decoder's log-probability of the sequence and its <eos>; with
+    the LM in the second pass (lm_rescore=True) `lm_score` is the LM's unweighted log-probability of the sequence (no <eos> term),
+    otherwise None."""
 
-    def __init__(self, output_seq, score, ctc_score=None, att_score=None):
+    def __init__(self, output_seq, score, ctc_score=None, att_score=None, lm_score=None):
         self.output_seq, self.score = output_seq, score
         self.ctc_score = score if ctc_score is None else ctc_score
-        self.att_score = att_score
+        self.att_score, self.lm_score = att_score, lm_score
 
     def avgScore(self):
         return self.score
@@ -178,13 +183,20 @@ class CTCHypothesis(object):
 
 class BeamDecoder(nn.Module):
     def __init__(self, asr, emb_decoder, beam_size, min_len_ratio, max_len_ratio, lm_path='', lm_config='', lm_weight=0.0,
-                 ctc_weight=0.0, batch_encode=False, len_bonus=0.0, rescore=False, rescore_rows=None):
+                 ctc_weight=0.0, batch_encode=False, len_bonus=0.0, rescore=False, rescore_rows=None, lm_rescore=False,
+                 lm_rescore_rows=None):
         super().__init__()
         assert emb_decoder is None, 'embedding-fusion decoding is outside the HIP path'
         self.batch_encode = bool(batch_encode)      # opt-in: the batched pass agrees with the per-utterance one to rounding only
         self.beam_size, self.min_len_ratio, self.max_len_ratio, self.asr = beam_size, min_len_ratio, max_len_ratio, asr
         self.ctc_only = not self.asr.enable_att
-        self.rescore = bool(rescore)
+        self.rescore, self.lm_rescore = bool(rescore), bool(lm_rescore)
+        if self.lm_rescore and not self.rescore:
+            raise ValueError('lm_rescore=True puts the LM into the second pass of two-pass decoding, and there is none without '
+                             'rescore=True: give both, or fuse the LM into the search (lm_weight alone)')
+        if self.lm_rescore and lm_rescore_rows is not None and lm_rescore_rows < 1:
+            raise ValueError('lm_rescore_rows = %r: a chunk of the LM pass holds at least one hypothesis row' % (lm_rescore_rows,))
+        self.lm_rescore_rows = lm_rescore_rows
         if self.rescore:
             # two passes: the CTC search below proposes, the attention decoder rescores - the model needs both halves
             if self.ctc_only:
@@ -245,8 +257,31 @@ class BeamDecoder(nn.Module):
     def set_lm(self, lm, weight):
         """Fuse `lm` with `weight`.  A CTC-only model takes anything with RNNLM's decoding interface: init_state(n, device),
         step(tokens, state) -> (log-probs (n,V), state) and gather_state(state, index), the state one fp32 (layers, n, dim)
-        tensor or a tuple of them."""
+        tensor or a tuple of them.  With lm_rescore=True the LM scores the n-best list in the second pass instead and needs
+        RNNLM's full-sequence interface: forward(tokens (B,T) int64 on the device) -> (logits (B,T,V) fp32, anything), position t
+        predicting the token behind tokens[:, :t + 1], <sos> = 0 in column 0, from the zero state, one direction only (so that
+        what follows a position cannot change it), together with eval() / train() and a settable `prec`; an object without such
+        a forward is refused here."""
+        if getattr(self, 'lm_rescore', False):
+            self._check_lm_forward(lm)
         self.apply_lm, self.lm_w, self.lm = True, weight, lm
+
+    @staticmethod
+    def _check_lm_forward(lm):
+        fwd = getattr(lm, 'forward', None)
+        if not callable(fwd) or getattr(fwd, '__func__', fwd) is nn.Module.forward:
+            raise ValueError('lm_rescore=True scores whole hypotheses with the LM\'s full-sequence forward(tokens) -> (logits (B,T,V), _), '
+                             'and %s has none (step() alone serves the first-pass fusion only)' % type(lm).__name__)
+
+    def _check_lm_rescore(self):
+        """What forward refuses with lm_rescore=True, before anything is launched."""
+        if not self.apply_lm or getattr(self, 'lm', None) is None:
+            raise ValueError('lm_rescore=True needs an LM to score the n-best list with, and none was given: name one by lm_config '
+                             '(and lm_path) with lm_weight > 0, or call set_lm(lm, weight)')
+        if not self.lm_w > 0:
+            raise ValueError('lm_rescore=True with lm_weight = %r: the LM pass would change nothing; give a weight above 0 or leave '
+                             'lm_rescore out' % (self.lm_w,))
+        self._check_lm_forward(self.lm)
 
     def create_msg(self):
         if self.rescore:
@@ -254,7 +289,10 @@ class BeamDecoder(nn.Module):
                    '\t| Tokens extended per frame = {}'.format(self.beam_size, self.ctc_cand),
                    '           |Rescoring score = (1 - w) * attention + w * CTC \t| ctc_weight w = {:.2f}'.format(self.ctc_w),
                    '           |Min/Max len ratio are ignored (the frames bound the length)']
-            if self.apply_lm:
+            if self.lm_rescore:
+                msg.append('           |LM scores the n-best list in the second pass (none in the first) \t| weight = {:.2f}'
+                           '\t| length bonus = {:.2f}'.format(self.lm_w if self.apply_lm else 0.0, self.len_bonus))
+            elif self.apply_lm:
                 msg.append('           |LM shallow fusion in the first pass, its terms added unweighted in the second \t| weight = {:.2f}'
                            '\t| length bonus = {:.2f}'.format(self.lm_w, self.len_bonus))
             msg.append(encoder_pass_msg(self.asr, self.batch_encode))
@@ -387,12 +425,18 @@ class BeamDecoder(nn.Module):
         asr_rescore_nbest launch scores, mixes and ranks.  Host reads: the 4-byte max_len (the decoder's step count is a host
         integer) before the decoder pass, the results after the last launch.  Returns, per utterance, the first pass's
         hypotheses (their sequences untouched: the <eos> the scoring appends is not output) in the new order, score = the mixed
-        score, ctc_score as the first pass gave it, att_score the decoder's."""
+        score, ctc_score as the first pass gave it, att_score the decoder's.
+        With lm_rescore the first pass is always the one-launch search without the LM; behind the decoder pass the LM scores the
+        same rows (_lm_pass), asr_rescore_nbest still gives att_score (its own total and order are not used) and
+        asr_rescore_rank_lm mixes in lm_weight * lm_score + len_bonus * length and ranks.  No further host read before the
+        read-back, which brings lm_score along."""
+        if self.lm_rescore:
+            self._check_lm_rescore()
         asr, K, st = self.asr, self.beam_size, H.stream_ptr()
         phase = self.phase_hook or (lambda name: None)
         enc, enc_len, tlen, ctc_lp = self._encode(audio_feature, feature_len)
         phase('encoder')
-        first = self._search_ctc_lm(ctc_lp, tlen) if self.apply_lm else self._search_ctc(ctc_lp, tlen)
+        first = self._search_ctc_lm(ctc_lp, tlen) if self.apply_lm and not self.lm_rescore else self._search_ctc(ctc_lp, tlen)
         phase('first_pass')
         U, Tp, E = enc.shape
         V, dev, R, Lr = asr.vocab_size, enc.device, U * K, Tp + 1
@@ -428,19 +472,30 @@ class BeamDecoder(nn.Module):
         finally:
             asr.train(was_training)
         phase('decoder_pass')
+        tok_logp = None
+        if self.lm_rescore:
+            tok_logp = self._lm_pass(teacher, Lr, first['len'], R, L)
+            phase('lm_pass')
         att, total = torch.empty((U, K), dtype=torch.float32, device=dev), torch.empty((U, K), dtype=torch.float32, device=dev)
         order = torch.empty((U, K), dtype=torch.int32, device=dev)
         H.call('asr_rescore_nbest', H.ptr(logits), logits.stride(0), logits.stride(1), H.ptr(teacher), Lr, H.ptr(tgt_len),
                H.ptr(first['ctc_score']), H.ptr(first['score']), H.ptr(first['n']), U, K, L, V, self.ctc_w, H.ptr(att), H.ptr(total),
                H.ptr(order), st)
+        lm_c = None
+        if self.lm_rescore:
+            lm_score = torch.empty((U, K), dtype=torch.float32, device=dev)
+            H.call('asr_rescore_rank_lm', H.ptr(att), H.ptr(first['ctc_score']), H.ptr(tok_logp), L, H.ptr(first['len']), H.ptr(first['n']),
+                   U, K, L, self.ctc_w, float(self.lm_w), self.len_bonus, H.ptr(lm_score), H.ptr(total), H.ptr(order), st)
         phase('rescore_launch')
         n_c, len_c, tok_c = first['n'].cpu(), first['len'].cpu(), first['tokens'].cpu()
         cs_c, att_c, tot_c, ord_c = first['ctc_score'].cpu(), att.cpu(), total.cpu(), order.cpu()
+        if self.lm_rescore:
+            lm_c = lm_score.cpu()
         out = []
         for u in range(U):
             slots = [int(i) for i in ord_c[u, :int(n_c[u])]]
-            out.append([CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(tot_c[u, i]), float(cs_c[u, i]), float(att_c[u, i]))
-                        for i in slots])
+            out.append([CTCHypothesis(tok_c[u, i, :int(len_c[u, i])].tolist(), float(tot_c[u, i]), float(cs_c[u, i]), float(att_c[u, i]),
+                                      None if lm_c is None else float(lm_c[u, i])) for i in slots])
         phase('read_back')
         return out[0] if U == 1 else out
 
@@ -450,6 +505,53 @@ class BeamDecoder(nn.Module):
         kn = getattr(self.asr.attention.att_layer, 'kernel_num', 1)
         rows = min(RESCORE_MAX_ROWS, max(1, RESCORE_STATE_BYTES // (4 * L * kn * Tp)))
         return rows if self.rescore_rows is None else max(1, min(rows, int(self.rescore_rows)))
+
+    def _lm_pass(self, teacher, Lr, hyp_len, R, L):
+        """The LM's log-probability of every token of every hypothesis -> tok_logp (R,L) fp32, 0 behind a hypothesis.
+        asr_rescore_lm_input shifts the teacher table into the LM's input (<sos> in front), the LM's full-sequence forward - the
+        training forward, only called here: it keeps what a backward pass would need while it runs - goes over chunks of rows in
+        eval() with the model's precision, and asr_rescore_token_logp reduces each chunk's logits (rows, L, V) against the
+        teacher table (int64, as asr_rescore_pack wrote it) and the first pass's len (int32, as it stands).  Training mode is
+        restored afterwards."""
+        lm, dev, st = self.lm, teacher.device, H.stream_ptr()
+        V = self.asr.vocab_size
+        lm_in = torch.empty((R, L), dtype=torch.int64, device=dev)
+        H.call('asr_rescore_lm_input', H.ptr(teacher), Lr, R, L, SOS, H.ptr(lm_in), st)
+        tok_logp = torch.empty((R, L), dtype=torch.float32, device=dev)
+        rows = self._rescore_lm_chunk_rows(L)
+        hyp_len = hyp_len.reshape(R)
+        lm.prec = self.asr.prec
+        was_training = lm.training
+        lm.eval()
+        try:
+            with torch.no_grad():
+                for r0 in range(0, R, rows):
+                    r1 = min(R, r0 + rows)
+                    logits = lm.forward(lm_in[r0:r1])[0]
+                    if tuple(logits.shape) != (r1 - r0, L, V) or logits.dtype != torch.float32:
+                        raise ValueError('lm_rescore: the LM\'s forward returned logits %s %s for tokens (%d, %d), not fp32 (%d, %d, %d)'
+                                         % (tuple(logits.shape), logits.dtype, r1 - r0, L, r1 - r0, L, V))
+                    logits = logits.contiguous()
+                    H.call('asr_rescore_token_logp', H.ptr(logits), L * V, V, H.ptr(teacher[r0:r1]), Lr, H.ptr(hyp_len[r0:r1]), r1 - r0, L, V,
+                           H.ptr(tok_logp[r0:r1]), L, st)
+        finally:
+            lm.train(was_training)
+        return tok_logp
+
+    def _rescore_lm_chunk_rows(self, L):
+        """Hypothesis rows one LM pass of L positions takes: the logit block and the forward's transient state under
+        RESCORE_STATE_BYTES, no more than lm_rescore_rows when the constructor gave one, never less than one row.  Per row and
+        position, in fp32 words: the logits V, a layer's input max(emb_dim, dim), and what its recurrence holds at once - an LSTM
+        layer its gates 4 dim, y and c (6 dim), a GRU layer gi 3 dim, y and the saved gates 4 dim (8 dim):
+            bytes per row = 4 * L * (V + max(emb_dim, dim) + (6 | 8) * dim)
+        A layer's tensors go as the next one runs (no graph is recorded under no_grad), so one layer's count stands for all."""
+        lm, V = self.lm, self.asr.vocab_size
+        dim = int(getattr(lm, 'dim', 0))
+        emb = getattr(getattr(lm, 'emb', None), 'weight', None)
+        emb_dim = int(emb.shape[1]) if emb is not None else dim
+        per_row = 4 * max(1, int(L)) * (V + max(emb_dim, dim) + (8 if getattr(lm, 'module', 'LSTM') == 'GRU' else 6) * dim)
+        rows = max(1, RESCORE_STATE_BYTES // per_row)
+        return rows if self.lm_rescore_rows is None else max(1, min(rows, int(self.lm_rescore_rows)))
 
     @torch.no_grad()
     def forward_host(self, audio_feature, feature_len):

@@ -149,6 +149,9 @@ SIGNATURES = {
     'asr_ctc_beam_lm_readout': [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_rescore_pack': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     'asr_rescore_nbest': [_vp, _l, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    'asr_rescore_lm_input': [_vp, _l, _i, _i, ctypes.c_int64, _vp, _vp],
+    'asr_rescore_token_logp': [_vp, _l, _l, _vp, _l, _vp, _i, _i, _i, _vp, _l, _vp],
+    'asr_rescore_rank_lm': [_vp, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp],
     'asr_ctc_align': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'asr_ragged_align': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'asr_ragged_unalign': [_vp, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],

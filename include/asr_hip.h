@@ -766,6 +766,44 @@ int asr_rescore_nbest(const float* logits, long row_stride, long pos_stride, con
                       const int* tgt_len, const float* ctc_score, const float* first_score, const int* n, int U, int K, int L,
                       int V, float ctc_weight, float* att_score, float* total, int* order, asr_stream_t stream);
 
+/* The RNN-LM in the second pass (csrc/rescore.hip): the LM scores the same n-best list teacher-forced, so the first pass runs
+ * without it.  Between asr_rescore_lm_input and asr_rescore_token_logp the caller runs the LM's full-sequence forward,
+ * lm_in (R,L) -> logits (R,L,V), over chunks of rows if it likes.  For beam slot i of utterance u with the hypothesis l_1..l_n,
+ * n = len[u,i] (the <eos> that asr_rescore_pack appends is not counted):
+ *     lm_score = sum_{j=1..n} log_softmax(LM(sos, l_1..l_{j-1}))[l_j]                      (0 for the empty hypothesis)
+ *     total    = (1 - ctc_weight) * att_score + ctc_weight * ctc_score + lm_weight * lm_score + len_bonus * n
+ *   asr_rescore_lm_input  : lm_in (R,L) int64 contiguous from teacher (R,teacher_ld) int64, teacher_ld >= L:
+ *     lm_in[r,0] = sos, lm_in[r,t] = teacher[r,t-1] for 1 <= t < L.  Every value written is `sos` or a value of the teacher table
+ *     (token ids; its padding and its unused rows are 0), so an embedding gather over lm_in reads valid rows only.  sos >= 0.
+ *   asr_rescore_token_logp: logits fp32, element (r,t,v) at r*row_stride + t*pos_stride + v, both strides >= V; target
+ *     (R,target_ld) int64 = the teacher table as asr_rescore_pack wrote it, not shifted; len (R) int32 = the first pass's len
+ *     (U,K) as it stands (0 in its unused slots), clamped here to 0..L.  out (R,out_ld) fp32, out_ld >= L:
+ *       out[r,t] = log_softmax(logits[r,t,:])[target[r,t]]   for t < min(max(len[r],0), L)     (fp32, the max subtracted)
+ *       out[r,t] = 0                                          for the other t < L
+ *     A -inf logit is legal: a target at -inf or outside 0..V-1 gives -inf, a position whose every logit is -inf gives -inf, never
+ *     NaN.  Nothing is read at or past len[r] along L, past V along a row or from the padding between strides; nothing is
+ *     written past column L of out.  One wave per (r,t), four per workgroup, the grid covers R*L: the bound is one read of the
+ *     logit block, and no logit is loaded twice: the wave takes the row in blocks of 1024 columns held in registers, max and
+ *     then sum of each block, and carries the max m so far and the sum of exp(x - m) across blocks (a block with a larger max
+ *     scales the sum by exp(m - max) first; up to 1024 columns that is max, then sum, with no scaling).  Lane c adds the columns
+ *     c, c+64, .. in order: a value does not depend on R, on the chunk of rows a launch covers or on the launch shape.  V <= 2^30.
+ *   asr_rescore_rank_lm   : att_score, ctc_score (U,K) fp32 (att_score from asr_rescore_nbest, whose own total and order are not
+ *     used then); tok_logp (R,tok_ld) fp32 = out above, tok_ld >= L; len (U,K) int32, clamped to 0..L; n (U) int32.  Writes, (U,K):
+ *       lm_score = sum_{t < len} tok_logp[r,t]   (fp32; lane c of the slot's wave adds positions c, c+64, .. in order, then one
+ *                  butterfly over the lanes: one fixed order whatever U, K and the grid are)
+ *       total    as defined above, in this order: (1-w)*att + w*ctc, + lm_weight*lm_score (left out when lm_weight == 0), + len_bonus*len
+ *       order    int32, rank -> slot, the rule of asr_rescore_nbest: a count over the K totals in LDS, ties to the lower slot.
+ *     att_score, ctc_score or (with lm_weight > 0) lm_score at -inf give total = -inf, never NaN; unused slots (i >= n[u]) get
+ *     lm_score = total = -inf and rank last.  One workgroup per utterance, one wave per slot.  lm_weight >= 0.
+ * Null pointers, bad dims, K outside 1..ASR_CTC_BEAM_MAX, a stride below V or a leading dimension below L return ASR_E_ARG and
+ * launch nothing. */
+int asr_rescore_lm_input(const int64_t* teacher, long teacher_ld, int R, int L, int64_t sos, int64_t* lm_in, asr_stream_t stream);
+int asr_rescore_token_logp(const float* logits, long row_stride, long pos_stride, const int64_t* target, long target_ld,
+                           const int* len, int R, int L, int V, float* out, long out_ld, asr_stream_t stream);
+int asr_rescore_rank_lm(const float* att_score, const float* ctc_score, const float* tok_logp, long tok_ld, const int* len,
+                        const int* n, int U, int K, int L, float ctc_weight, float lm_weight, float len_bonus, float* lm_score,
+                        float* total, int* order, asr_stream_t stream);
+
 /* CTC forced alignment (csrc/ctc_align.hip): the most probable alignment (Viterbi) of a KNOWN transcript to the CTC
  * log-probabilities - token and word timestamps, cutting long recordings, finding bad transcripts by their score.  No reference
  * counterpart.  ONE launch for all B utterances, one workgroup per utterance, one thread per lattice state; nothing is copied

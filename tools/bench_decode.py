@@ -4,6 +4,7 @@ U at a time by the device-side beam search (src/decode.BeamDecoder.forward).  Pr
 usage: python tools/bench_decode.py [--utts 8] [--frames 400] [--max-len-ratio 0.05] [--reps 3] [--host]
        [--model-yaml PATH] [--attention-mode dot|loc] [--num-head N] [--decoder-module LSTM|GRU] [--lm-module LSTM|GRU]
        [--ctc-only] [--ctc-lm] [--batch-encode] [--lengths equal|librispeech] [--vgg N] [--rescore] [--vocab N] [--no-lm]
+       [--profile-out PATH]
 --vocab N builds the synthetic model and the LM with N tokens instead of the character table's 31 (above 2048 the joint search runs
 asr_beam_candidates_wide / asr_beam_step_wide and the decode step's projection is one contraction); --no-lm leaves the LM out of
 the joint search.
@@ -21,10 +22,13 @@ draws the U lengths from SURVEY 8d's length model clip(N(1270,480),150,2450) ins
 overrides the yaml's encoder.vgg (0..7: the front-ends of src/vgg.py / src/module.py), so that --batch-encode measures the
 batched pass of a front-end model.  --rescore measures, in one process, the joint CTC/attention/LM beam search and two-pass
 decoding of the same model (BeamDecoder(rescore=True): CTC prefix beam search, then attention rescoring of its n-best list,
-csrc/rescore.hip) without and with the LM in the first pass: one warm-up each, then the median of --reps runs, and for the two-pass
-modes one more run with a synchronisation after every phase, which splits the time into encoder, first pass, decoder pass (teacher
-table, the 4-byte read of the step count, row expansion, the teacher-forced decoder forward), rescoring launch and read-back.
-With --batch-encode all three use the length-aware batched encoder pass."""
+csrc/rescore.hip) without an LM, with the LM in the first pass and with the LM in the second pass (lm_rescore=True: the first pass
+runs without it, the LM's full-sequence forward scores the n-best list): one warm-up each, then the median of --reps runs, and for
+the two-pass modes one more run with a synchronisation after every phase, which splits the time into encoder, first pass, decoder
+pass (teacher table, the 4-byte read of the step count, row expansion, the teacher-forced decoder forward), LM pass (second-pass LM
+only: the LM's input table, its forward over chunks of rows, the per-token log-probabilities), rescoring launch and read-back.
+With --batch-encode all four use the length-aware batched encoder pass.  The result line also replaces the line of the same
+encoder pass in --profile-out (default profiles/rescore_lm_decode.json; '' writes nothing)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'e2e-asr-pytorch_amd')
@@ -45,6 +49,7 @@ ap.add_argument('--ctc-only', action='store_true'); ap.add_argument('--ctc-lm', 
 ap.add_argument('--batch-encode', action='store_true'); ap.add_argument('--lengths', choices=('equal', 'librispeech'), default='equal')
 ap.add_argument('--vgg', type=int, choices=range(8)); ap.add_argument('--rescore', action='store_true')
 ap.add_argument('--vocab', type=int, default=31); ap.add_argument('--no-lm', action='store_true')
+ap.add_argument('--profile-out', default=os.path.join(ROOT, 'profiles', 'rescore_lm_decode.json'))
 a = ap.parse_args()
 torch.manual_seed(0)
 mc = yaml.safe_load(open(a.model_yaml))['model']
@@ -103,20 +108,21 @@ if a.rescore:
     dec_j = BeamDecoder(model, None, **kw); dec_j.set_lm(lm, 0.3)
     dec_r = BeamDecoder(model, None, rescore=True, **kw)
     dec_rl = BeamDecoder(model, None, rescore=True, **kw); dec_rl.set_lm(lm, 0.3)
-    runs = {'joint_lm': dec_j, 'rescore': dec_r, 'rescore_lm': dec_rl}
+    dec_r2 = BeamDecoder(model, None, rescore=True, lm_rescore=True, **kw); dec_r2.set_lm(lm, 0.3)
+    runs = {'joint_lm': dec_j, 'rescore': dec_r, 'rescore_lm': dec_rl, 'rescore_lm_second_pass': dec_r2}
     ts = {k: [] for k in runs}
     for rep_ in range(1 + a.reps):                     # rep 0 = warm-up: workspaces, packed weights, plans
         for name, d in runs.items():
             torch.cuda.synchronize(); t0 = time.perf_counter(); out = d(feat, flen); torch.cuda.synchronize()
             if rep_: ts[name].append((time.perf_counter() - t0) * 1e3)
-    res = {'metric': 'joint beam search vs two-pass decoding (CTC n-best, attention rescoring), config 4', 'batch_utterances': U,
+    res = {'metric': 'joint beam search vs two-pass decoding (CTC n-best, attention rescoring; LM in neither, the first or the second pass), config 4', 'batch_utterances': U,
            'lengths': a.lengths, 'frames': flen.tolist() if a.lengths != 'equal' else T, 'beam': a.beam, 'prec': a.prec, 'reps': a.reps,
            'ctc_weight': 0.3, 'lm': '4x1024 tied, %s' % a.lm_module, 'lm_weight': 0.3, 'weights': 'random',
            'encoder_pass': 'batched' if a.batch_encode else 'per utterance'}
     for name in runs:
         ms = statistics.median(ts[name])
         res[name] = {'decode_ms': ms, 'utterances_per_s': U * 1e3 / ms}
-    for name in ('rescore', 'rescore_lm'):
+    for name in ('rescore', 'rescore_lm', 'rescore_lm_second_pass'):
         stamps = []
         def hook(phase):
             torch.cuda.synchronize(); stamps.append((phase, time.perf_counter()))
@@ -126,8 +132,21 @@ if a.rescore:
         res[name]['split_ms'] = {ph: (t - tp) * 1e3 for (ph, t), tp in zip(stamps, [t0] + [t for _, t in stamps[:-1]])}
         res[name]['hyps_first_utt'] = len(out[0]) if U > 1 else len(out)
         res[name]['longest_hypothesis'] = max(len(h.outIndex) for hs in (out if U > 1 else [out]) for h in hs)
+    # the LM pass's shape: rows per chunk, positions, and the recurrence plan its LSTM layers get (include/asr_hip.h::asr_lstm_plan)
+    L2 = res['rescore_lm_second_pass']['longest_hypothesis'] + 1
+    rows = min(U * a.beam, dec_r2._rescore_lm_chunk_rows(L2))
+    res['rescore_lm_second_pass']['lm_pass'] = {
+        'rows': U * a.beam, 'rows_per_chunk': rows, 'positions': L2,
+        'lstm_plan': int(H.lib().asr_lstm_plan(rows, L2, lm.dim, 1, model.prec)) if a.lm_module == 'LSTM' else None}
     H.raise_if_aborted()
-    print(json.dumps(res))
+    line = json.dumps(res)
+    print(line)
+    if a.profile_out:
+        keep = []
+        if os.path.exists(a.profile_out):
+            keep = [l for l in open(a.profile_out).read().splitlines() if l.strip() and json.loads(l).get('encoder_pass') != res['encoder_pass']]
+        os.makedirs(os.path.dirname(os.path.abspath(a.profile_out)), exist_ok=True)
+        open(a.profile_out, 'w').write(''.join(l + '\n' for l in sorted(keep + [line], key=lambda l: json.loads(l)['encoder_pass'] == 'batched')))
     sys.exit(0)
 if a.batch_encode:
     import statistics
