@@ -77,6 +77,12 @@ class RNNLM(nn.Module):
         self.dropout = float(dropout)
         if emb_tying:
             assert emb_dim == dim, 'Output dim of RNN should be identical to embedding if using weight tying.'
+        elif emb_dim != dim:
+            # the reference builds trans = nn.Linear(emb_dim, vocab) and feeds it the RNN's outputs of width dim (src/lm.py:20,37):
+            # its first forward raises.  Here the contraction would take K = dim from its input and the row stride emb_dim from
+            # trans.weight, and return numbers (emb_dim > dim) or read past the weight's rows (emb_dim < dim).
+            raise NotImplementedError('untied language model with emb_dim %d != dim %d: the reference applies trans = nn.Linear(emb_dim, '
+                                      'vocab) to outputs of width dim and fails at its first forward' % (emb_dim, dim))
         self.emb = nn.Embedding(vocab_size, emb_dim)
         if self.module == 'LSTM':
             self.rnn = LSTMParams(emb_dim, dim, False, num_layers=n_layers)

@@ -59,10 +59,12 @@ def test_init_state_is_one_tensor():
 def test_other_modules_and_sizes_are_refused():
     from src.lm import GRU_MAX_DIM, RNNLM
     assert GRU_MAX_DIM == 2048
-    RNNLM(31, False, 8, 'GRU', 2048, 1, 0.0)
-    RNNLM(31, False, 8, 'GRU', 37, 1, 0.0)                 # ragged sizes are handled, not refused
-    with pytest.raises(NotImplementedError):
-        RNNLM(31, False, 8, 'GRU', 2049, 1, 0.0)
+    RNNLM(31, False, 2048, 'GRU', 2048, 1, 0.0)
+    RNNLM(31, False, 37, 'GRU', 37, 1, 0.0)                # ragged sizes are handled, not refused
+    with pytest.raises(NotImplementedError, match='outside'):
+        RNNLM(31, False, 2049, 'GRU', 2049, 1, 0.0)
+    with pytest.raises(NotImplementedError, match='emb_dim'):
+        RNNLM(31, False, 8, 'GRU', 37, 1, 0.0)             # untied with emb_dim != dim: the reference's model fails at its first forward
     with pytest.raises(NotImplementedError):
         RNNLM(31, True, 16, 'RNN', 16, 1, 0.0)
     lm = RNNLM(31, True, 16, 'GRU', 16, 1, 0.0)

@@ -331,7 +331,8 @@ def test_lm_chunk_rows():
     per_row = 4 * 37 * (31 + 32 + 6 * 32)
     assert _chunk_rows(31, 37, small) == RESCORE_STATE_BYTES // per_row > 10000
     assert _chunk_rows(31, 37, small, rows=3) == 3 and _chunk_rows(31, 37, small, rows=10 ** 9) == RESCORE_STATE_BYTES // per_row
-    gru = RNNLM(31, False, 16, 'GRU', 32, 1, 0.0)
+    # emb_dim < dim (its shapes only: RNNLM refuses an untied model whose emb_dim differs from dim)
+    gru = types.SimpleNamespace(dim=32, module='GRU', emb=types.SimpleNamespace(weight=torch.empty(1, 16)))
     assert _chunk_rows(31, 37, gru) == RESCORE_STATE_BYTES // (4 * 37 * (31 + 32 + 8 * 32))
     # a word vocabulary: the config's 4 x 1024 tied LM at V = 65 536 (its shapes only: the embedding alone would be 256 MiB)
     big = types.SimpleNamespace(dim=1024, module='LSTM', emb=types.SimpleNamespace(weight=torch.empty(1, 1024)))
