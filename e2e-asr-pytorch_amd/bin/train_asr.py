@@ -57,6 +57,20 @@ class Solver(BaseSolver):
         self.optimizer = Optimizer(self.model.parameters(), **hp)
         self.lr_scheduler = self.optimizer.lr_scheduler
         self.verbose(self.optimizer.create_msg())
+        # word-embedding regulariser (reference bin/train_asr.py:139-147).  Its parameters get an optimizer of the same kind beside
+        # the model's: the fused step kernels work on one flat buffer each (src/step.step_emb_optimizer)
+        self.emb_fuse, self.emb_reg = False, ('emb' in self.config) and self.config['emb'].get('enable', False)
+        if self.emb_reg:
+            from src.plugin import EmbeddingRegularizer, check_emb_config
+            check_emb_config(self.config['emb'], self.config['model'], hp)
+            if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                raise NotImplementedError('the embedding regulariser is not wired into data-parallel training (its gradients are '
+                                          'not all-reduced)')
+            self.emb_decoder = EmbeddingRegularizer(self.tokenizer, self.model.dec_dim, prec=hip.get('prec', 'bf16'),
+                                                    seed=self.paras.seed, **self.config['emb']).to(self.device)
+            self.emb_optimizer = Optimizer(self.emb_decoder.trainable_parameters(), **hp)
+            self.emb_fuse = self.emb_decoder.apply_fuse
+            self.verbose(self.emb_decoder.create_msg())
         from src import dist as D_
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             self.dp = self.model.attach_data_parallel()
@@ -85,7 +99,15 @@ class Solver(BaseSolver):
                 feat, feat_len, txt, txt_len = self.fetch_data(data, train=True)
                 self.timer.cnt('rd')
                 L = int(txt.shape[1])      # = max(txt_len) for a padded batch, without a device sync
-                ctc_output, encode_len, att_output, att_align, _ = self.model(feat, feat_len, L, tf_rate=tf_rate, teacher=txt, ctc_async=True)
+                ctc_output, encode_len, att_output, att_align, dec_state = self.model(feat, feat_len, L, tf_rate=tf_rate, teacher=txt,
+                                                                                      ctc_async=True, get_dec_state=self.emb_reg)
+                emb_loss = None
+                if self.emb_reg:                 # bin/train_asr.py:215-222 of the reference
+                    self.emb_optimizer.opt.zero_grad()
+                    emb_loss, fuse_output = self.emb_decoder(dec_state, att_output, label=txt[:, :att_output.shape[1]])
+                    total_loss = total_loss + self.emb_decoder.weight * emb_loss
+                    if self.emb_fuse:
+                        att_output = fuse_output
                 if ctc_output is not None:
                     if getattr(ctc_output, '_asr_side', False):      # CTC branch on the side stream (src/asr.py, src/step.py)
                         with H.side_branch(False, txt, txt_len):
@@ -114,6 +136,12 @@ class Solver(BaseSolver):
                     if ctc_output is not None:
                         self.write_log('loss', {'tr_ctc': ctc_loss})
                         self.write_log(self.WER, {'tr_ctc': cal_er(self.tokenizer, ctc_output, txt, ctc=True)})
+                    if self.emb_reg:
+                        self.write_log('emb_loss', {'tr': emb_loss})
+                        if self.emb_fuse:
+                            if self.emb_decoder.fuse_learnable:
+                                self.write_log('fuse_lambda', {'emb': self.emb_decoder.get_weight()})
+                            self.write_log('fuse_temp', {'temp': self.emb_decoder.get_temp()})
                 if (self.step == 1) or (self.step % self.valid_step == 0):
                     self.validate(self.dv_set, self.dv_names)
                 if self.lr_scheduler is None and self.step > 99999 and self.step % 2000 == 0:
@@ -127,13 +155,15 @@ class Solver(BaseSolver):
 
     def validate(self, _dv_set, _name):
         self.model.eval()
+        if self.emb_decoder is not None:
+            self.emb_decoder.eval()
         dev_er = {'att': [], 'ctc': []}
         for i, data in enumerate(_dv_set):
             self.progress('Valid step - {}/{}'.format(i + 1, len(_dv_set)))
             feat, feat_len, txt, txt_len = self.fetch_data(data)
             with torch.no_grad():
                 ctc_output, encode_len, att_output, att_align, _ = self.model(
-                    feat, feat_len, int(txt.shape[1] * self.DEV_STEP_RATIO))
+                    feat, feat_len, int(txt.shape[1] * self.DEV_STEP_RATIO), emb_decoder=self.emb_decoder)
             if att_output is not None:
                 dev_er['att'].append(cal_er(self.tokenizer, att_output, txt, mode=self.val_mode))
             if ctc_output is not None:
@@ -148,3 +178,5 @@ class Solver(BaseSolver):
                 self.save_checkpoint('last_{}_{}.pth'.format(task, _name), self.val_mode, er, _name)
             self.write_log(self.WER, {'dv_' + task + '_' + _name.lower(): er})
         self.model.train()
+        if self.emb_decoder is not None:
+            self.emb_decoder.train()

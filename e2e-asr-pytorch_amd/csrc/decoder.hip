@@ -1421,9 +1421,24 @@ static int wgrad_slices(int out_rows, int out_cols, int depth) {
 extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
                                           const float* enc, const int64_t* enc_len, const asr_dec_state_t* state, const float* dlogits,
                                           void* workspace, size_t workspace_bytes, int looped, int prec, asr_stream_t stream);
+// dst[r * dst_ld + c] += src[r * width + c]: an outside gradient on the top layer's h_t joins dh_top (asr_att_decoder_bwd_hs)
+static __global__ __launch_bounds__(256) void add_rows_kernel(float* dst, long dst_ld, const float* src, long rows, int width) {
+    const long n = rows * width;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[(i / width) * dst_ld + i % width] += src[i];
+}
+
 extern "C" int asr_att_decoder_bwd_ex(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
                                       const float* enc, const int64_t* enc_len, const asr_dec_state_t* state,
                                       const float* dlogits, float* denc,
+                                      void* workspace, size_t workspace_bytes, int prec, int defer_params, int* looped_out,
+                                      asr_stream_t stream) {
+    return asr_att_decoder_bwd_hs(dims, weights, grads, enc, enc_len, state, dlogits, nullptr, denc, workspace, workspace_bytes, prec,
+                                  defer_params, looped_out, stream);
+}
+
+extern "C" int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
+                                      const float* enc, const int64_t* enc_len, const asr_dec_state_t* state,
+                                      const float* dlogits, const float* dhs_ext, float* denc,
                                       void* workspace, size_t workspace_bytes, int prec, int defer_params, int* looped_out,
                                       asr_stream_t stream) {
     ASR_REQUIRE(dims && weights && grads && enc && enc_len && state && dlogits && denc && workspace, ASR_E_ARG,
@@ -1471,6 +1486,11 @@ extern "C" int asr_att_decoder_bwd_ex(const asr_dec_dims_t* dims, const asr_dec_
     dh_top.b_kc = 0; dh_top.prec = prec;
     rc = gemm_run(dh_top, st);
     if (rc != ASR_OK) return rc;
+    if (dhs_ext) {
+        const long n = (long)BL * d.Dd;
+        hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, st,
+                           p.dhs + (size_t)(d.NL - 1) * d.Dd, SW, dhs_ext, (long)BL, d.Dd);
+    }
 
     const int taps = 2 * d.Ks + 1;
     const int nw_e = cdiv(d.A, 64);

@@ -66,6 +66,9 @@ def main():
     np.random.seed(paras.seed)
     torch.manual_seed(paras.seed)
     Solver, mode = select_solver(paras)
+    if paras.test and not paras.align and not paras.lm:
+        from bin.emb_asr import with_emb_decoder      # embedding-fused decoding when the checkpoint's config has a fusing `emb:` block
+        Solver = with_emb_decoder(Solver)
     solver = Solver(config, paras, mode)
     solver.load_data()
     solver.set_model()

@@ -277,8 +277,10 @@ class ASR(nn.Module):
                    att_seq [B,1,L,T'], dec_state.'''
         if not audio_feature.is_cuda:
             raise RuntimeError('ASR (HIP path) needs CUDA tensors; there is no CPU fallback')
-        if emb_decoder is not None:
-            raise NotImplementedError('embedding-regulariser plugin is outside the HIP path')
+        # an embedding-fusing plugin takes part in greedy decoding only (reference src/asr.py:167-172); in training the caller
+        # applies it to the returned dec_state / att_output (bin/train_asr.py)
+        fuse_dec = (emb_decoder if emb_decoder is not None and getattr(emb_decoder, 'enable', False) and emb_decoder.apply_fuse
+                    and teacher is None and self.enable_att else None)
         ctx = _RunCtx(self)
         feature_len = feature_len.to(audio_feature.device)
         ctc_output, att_output, att_seq, dec_state = None, None, None, None
@@ -302,14 +304,21 @@ class ASR(nn.Module):
             if not (self.decoder.fast and self.attention.fast and self.emb_drop == 0.0):
                 from src.variants import variant_decoder
                 att_output, att_seq, hs = variant_decoder(self, ctx.anchor, encode_feature, encode_len, L, teacher,
-                                                          float(tf_rate) if teacher is not None else 1.0, ctx)
+                                                          float(tf_rate) if teacher is not None else 1.0, ctx, emb_decoder=fuse_dec)
                 if get_dec_state:
                     dec_state = hs
                 if side_ctc and not ctc_async:
                     H.join_branch(ctc_output)
                 return ctc_output, encode_len, att_output, att_seq, dec_state
-            att_output, att_seq, hs = F_hip.AttDecoderFn.apply(ctx.anchor, encode_feature, encode_len, teacher, L, self, self.prec,
-                                                               float(tf_rate) if teacher is not None else 1.0)
+            if fuse_dec is not None:
+                d, st, att_output = F_hip.att_decoder_forward_fused(self, encode_feature.contiguous(),
+                                                                    encode_len.to(encode_feature.device, torch.int64).contiguous(), L,
+                                                                    self.prec, fuse_dec)
+                att_seq, hs = st['att'].view(d.B, 1, d.L, d.Tp), st['hs']
+                self._last_tokens = st['tokens']
+            else:
+                att_output, att_seq, hs = F_hip.AttDecoderFn.apply(ctx.anchor, encode_feature, encode_len, teacher, L, self, self.prec,
+                                                                   float(tf_rate) if teacher is not None else 1.0)
             if get_dec_state:
                 dec_state = hs[:, :, -1, :]
         if side_ctc and not ctc_async:

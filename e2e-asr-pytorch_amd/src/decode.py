@@ -186,7 +186,16 @@ class BeamDecoder(nn.Module):
                  ctc_weight=0.0, batch_encode=False, len_bonus=0.0, rescore=False, rescore_rows=None, lm_rescore=False,
                  lm_rescore_rows=None):
         super().__init__()
-        assert emb_decoder is None, 'embedding-fusion decoding is outside the HIP path'
+        # an embedding-fusing plugin (src/plugin.py) replaces log_softmax(logits) of every step by its fused log-probs
+        assert emb_decoder is None or hasattr(emb_decoder, 'fuse_rows'), \
+            'emb_decoder must be a src.plugin.EmbeddingRegularizer (its fuse_rows scores every step), got %s' % type(emb_decoder).__name__
+        self.apply_emb = emb_decoder is not None and bool(getattr(emb_decoder, 'enable', False)) and emb_decoder.apply_fuse
+        self.emb_decoder = emb_decoder if self.apply_emb else None
+        if self.apply_emb and rescore:
+            raise ValueError('rescore=True together with an emb_decoder: two-pass rescoring scores whole hypotheses with the plain '
+                             'decoder and has no embedding-fused form; decode with the joint beam search (rescore=False)')
+        if self.apply_emb and not asr.enable_att:
+            raise ValueError('an emb_decoder fuses the attention decoder\'s distribution, and this model has none (CTC-only, ctc_weight = 1)')
         self.batch_encode = bool(batch_encode)      # opt-in: the batched pass agrees with the per-utterance one to rounding only
         self.beam_size, self.min_len_ratio, self.max_len_ratio, self.asr = beam_size, min_len_ratio, max_len_ratio, asr
         self.ctc_only = not self.asr.enable_att
@@ -310,6 +319,8 @@ class BeamDecoder(nn.Module):
             msg.append('           |Joint CTC decoding enabled \t| weight = {:.2f}\t'.format(self.ctc_w))
         if self.apply_lm:
             msg.append('           |Joint LM decoding enabled \t| weight = {:.2f}'.format(self.lm_w))
+        if self.apply_emb:
+            msg.append('           |Joint Emb. decoding enabled \t| weight = {:.2f}'.format(float(self.emb_decoder.get_weight().mean())))
         msg.append(encoder_pass_msg(self.asr, self.batch_encode))
         return msg
 
@@ -338,7 +349,8 @@ class BeamDecoder(nn.Module):
             dec = VariantStep(self.asr, enc, enc_len, self.beam_size, Lmax)
         book = _BeamBook(self, U, Lmax, min_lens, max_lens, ctc_lp, tlen, dec.tokens)
         for t in range(Lmax):
-            parent = book.step(t, dec.step(t))
+            logits = dec.step(t)
+            parent = book.step(t, logits, dec.top_state(t) if self.apply_emb else None)
             dec.reorder(t, parent)                          # state of the survivors: new row i <- row parent[i]
             if (t & 15) == 15 and book.all_done():          # every 16 positions: stop early when every search has ended
                 break
@@ -597,7 +609,10 @@ class BeamDecoder(nn.Module):
             H.call('asr_att_decoder_step', ctypes.byref(d), ctypes.byref(w), H.ptr(enc_rep), H.ptr(len_rep), ctypes.byref(s), t, prec, st)
             logits = sd['logits'][:n, t].contiguous()
             att_lp = torch.empty_like(logits)
-            H.call('asr_log_softmax', H.ptr(logits), H.ptr(att_lp), n, V, st)
+            if self.apply_emb:
+                self.emb_decoder.fuse_rows(sd['hs'][:n, t, -1, :], logits, out=att_lp)
+            else:
+                H.call('asr_log_softmax', H.ptr(logits), H.ptr(att_lp), n, V, st)
             att_cpu = att_lp.cpu()
             cur = att_cpu.clone()
             cands, psi_cpu, r_new = None, None, None
@@ -667,6 +682,10 @@ class _FastStep(object):
                ctypes.byref(self.s), t, self.asr.prec, H.stream_ptr())
         return self.sd['logits'][:, t].contiguous()
 
+    def top_state(self, t):
+        """(R,Dd) hidden state of the top layer at position t (what an embedding-fusing plugin reads)."""
+        return self.sd['hs'][:, t, -1, :]
+
     def reorder(self, t, parent):
         R, st = self.R, H.stream_ptr()
         for name in ('hs', 'cs', 'att'):
@@ -732,12 +751,16 @@ class _BeamBook(object):
         args.lm_weight = float(bd.lm_w) if bd.apply_lm else 0.0
         args.eos_threshold = 1.5
 
-    def step(self, t, logits):
-        """logits (R,V) of output position t -> parent (R) int64: the source row of every surviving row."""
+    def step(self, t, logits, top_state=None):
+        """logits (R,V) of output position t -> parent (R) int64: the source row of every surviving row.  top_state (R,Dd): the
+        decoder's top hidden state, given when an embedding-fusing plugin scores the step instead of log_softmax."""
         bd, R, V, C, Tp, st = self.bd, self.R, self.V, self.C, self.Tp, H.stream_ptr()
         a, b = self.state[t & 1], self.state[(t + 1) & 1]
         att_lp = self.att_lp
-        H.call('asr_log_softmax', H.ptr(logits), H.ptr(att_lp), R, V, st)
+        if top_state is not None:
+            bd.emb_decoder.fuse_rows(top_state, logits, out=att_lp)
+        else:
+            H.call('asr_log_softmax', H.ptr(logits), H.ptr(att_lp), R, V, st)
         if bd.apply_ctc:
             H.call('asr_beam_candidates_wide' if self.wide else 'asr_beam_candidates', H.ptr(att_lp), H.ptr(self.cand), R, V, C, st)
             H.call('asr_ctc_prefix_score_batched', H.ptr(self.ctc_lp), H.ptr(self.tlen), H.ptr(self.ctc_r), H.ptr(self.cand), H.ptr(a['len']),

@@ -153,6 +153,10 @@ class VariantStep(object):
         H.linear_fwd(self.h_new[-1], dec.char_trans.weight, dec.char_trans.bias, self.logits, prec=prec)
         return self.logits
 
+    def top_state(self, t):
+        """(R,dim) hidden state of the top layer just computed (what an embedding-fusing plugin reads)."""
+        return self.h_new[-1]
+
     def reorder(self, t, parent):
         """Row i <- row parent[i] of the state just computed: one gather of the packed state."""
         pieces = self.h_new + self.c_new + ([self.attn] if self.loc else [])

@@ -705,6 +705,29 @@ def att_decoder_forward_sampled(model, enc, enc_len, L, teacher, prec, tf_rate, 
     return d, st
 
 
+@torch.no_grad()
+def att_decoder_forward_fused(model, enc, enc_len, L, prec, emb_decoder):
+    """Greedy decoding through an embedding-fusing plugin (reference src/asr.py:167-172 with emb_decoder): every step runs the
+    per-step C-ABI call, the plugin fuses the step's logits with its embedding distribution (asr_emb_fuse_fwd) and the kernel's
+    argmax of the fused row is the next step's token.  Returns (dims, state, fused log-probs (B,L,V))."""
+    B, Tp, _ = enc.shape
+    d = _dec_dims(model, B, Tp, L)
+    st = _dec_state(d, enc.device, save_conv=False, half_copies=False)
+    st['tokens'].zero_()
+    w = H.dec_weights_struct(_dec_tensors(model, False), d.NL)
+    s = H.dec_state_struct(st)
+    sp = H.stream_ptr()
+    fused = torch.empty((B, L, d.V), dtype=torch.float32, device=enc.device)
+    scratch = torch.empty(B, dtype=torch.int64, device=enc.device)
+    H.call('asr_att_decoder_keys', ctypes.byref(d), ctypes.byref(w), H.ptr(enc), H.ptr(st['key']), prec, sp)
+    for t in range(L):
+        H.call('asr_att_decoder_step', ctypes.byref(d), ctypes.byref(w), H.ptr(enc), H.ptr(enc_len), ctypes.byref(s), t, prec, sp)
+        nxt, ld = (st['tokens'][:, t + 1], st['tokens'].stride(0)) if t + 1 < L else (scratch, 1)
+        row = emb_decoder.fuse_rows(st['hs'][:, t, -1, :], st['logits'][:, t], argmax=nxt, argmax_ld=ld)
+        fused[:, t].copy_(row)
+    return d, st, fused
+
+
 _DEC_WS = {}          # (kind, decoder dims, device) -> uint8 tensor; process-wide, LRU of 32 shapes per pass
 
 
@@ -769,13 +792,17 @@ class AttDecoderFn(torch.autograd.Function):
         ctx.save_for_backward(enc, enc_len)
         att_seq = st['att'].view(d.B, 1, d.L, d.Tp)
         ctx.mark_non_differentiable(att_seq)
+        ctx.set_materialize_grads(False)         # an unused output arrives as None in backward, not as a tensor of zeros
         return st['logits'], att_seq, st['hs']
 
     @staticmethod
-    def backward(ctx, dlogits, _datt, _dhs):
+    def backward(ctx, dlogits, _datt, dhs):
         model, prec, d, st = ctx.model, ctx.prec, ctx.d, ctx.st
         enc, enc_len = ctx.saved_tensors
-        dlogits = dlogits.contiguous()
+        dlogits = torch.zeros_like(st['logits']) if dlogits is None else dlogits.contiguous()
+        # a gradient on the decoder states (the embedding regulariser reads the top layer's h_t, src/plugin.py): the top layer's
+        # slice joins dh_top inside the call; without one this is asr_att_decoder_bwd_ex, launch for launch
+        dhs_top = dhs[:, :, -1, :].contiguous() if dhs is not None else None
         denc = torch.zeros_like(enc)
         w = H.dec_weights_struct(_dec_tensors(model, False), d.NL)
         g = H.dec_weights_struct(_dec_tensors(model, True), d.NL)
@@ -789,9 +816,14 @@ class AttDecoderFn(torch.autograd.Function):
             H.abort_guard(ws, status_off)
         overlap = H.overlap_enabled() and (getattr(model, '_dp', None) is None or H.overlap_dp_enabled())
         looped = ctypes.c_int(0)
-        H.call('asr_att_decoder_bwd_ex', ctypes.byref(d), ctypes.byref(w), ctypes.byref(g), H.ptr(enc), H.ptr(enc_len),
-               ctypes.byref(s), H.ptr(dlogits), H.ptr(denc), H.ptr(ws), nbytes, prec, 1 if overlap else 0, ctypes.byref(looped),
-               H.stream_ptr())
+        if dhs_top is None:
+            H.call('asr_att_decoder_bwd_ex', ctypes.byref(d), ctypes.byref(w), ctypes.byref(g), H.ptr(enc), H.ptr(enc_len),
+                   ctypes.byref(s), H.ptr(dlogits), H.ptr(denc), H.ptr(ws), nbytes, prec, 1 if overlap else 0, ctypes.byref(looped),
+                   H.stream_ptr())
+        else:
+            H.call('asr_att_decoder_bwd_hs', ctypes.byref(d), ctypes.byref(w), ctypes.byref(g), H.ptr(enc), H.ptr(enc_len),
+                   ctypes.byref(s), H.ptr(dlogits), H.ptr(dhs_top), H.ptr(denc), H.ptr(ws), nbytes, prec, 1 if overlap else 0,
+                   ctypes.byref(looped), H.stream_ptr())
         if persistent:
             H.watch_abort(ws, status_off)
         if overlap:

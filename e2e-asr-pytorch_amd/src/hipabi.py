@@ -81,6 +81,13 @@ SIGNATURES = {
     'asr_att_decoder_bwd': [_P(DecDims), _P(DecWeights), _P(DecWeights), _vp, _vp, _P(DecState), _vp, _vp, _vp, _sz, _i, _vp],
     'asr_att_decoder_bwd_ex': [_P(DecDims), _P(DecWeights), _P(DecWeights), _vp, _vp, _P(DecState), _vp, _vp, _vp, _sz, _i, _i,
                                ctypes.POINTER(_i), _vp],
+    'asr_att_decoder_bwd_hs': [_P(DecDims), _P(DecWeights), _P(DecWeights), _vp, _vp, _P(DecState), _vp, _vp, _vp, _vp, _sz, _i, _i,
+                               ctypes.POINTER(_i), _vp],
+    'asr_emb_cos_loss': [_vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    'asr_emb_fuse_fwd': [_vp, _l, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _l, _i, _i, _vp],
+    'asr_emb_fuse_bwd': [_vp, _vp, _l, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    'asr_row_normalize_fwd': [_vp, _vp, _l, _i, _vp],
+    'asr_row_normalize_bwd': [_vp, _vp, _vp, _l, _i, _vp],
     'asr_att_decoder_bwd_params': [_P(DecDims), _P(DecWeights), _P(DecWeights), _vp, _vp, _P(DecState), _vp, _vp, _sz, _i, _i, _vp],
     'asr_fbank': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _sz, _vp],
     'asr_delta_stack': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

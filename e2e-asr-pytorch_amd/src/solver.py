@@ -63,7 +63,8 @@ class BaseSolver():
             self.exp_name = paras.config.split('/')[-1].replace('.yaml', '')
             if mode == 'train':
                 self.exp_name += '_sd{}'.format(paras.seed)
-        self.emb_decoder = None
+        self.emb_decoder = None          # src.plugin.EmbeddingRegularizer when the config has an enabled `emb:` block
+        self.emb_optimizer = None
         self.transfer_learning = False
         self.dp = None
         if mode == 'train':
@@ -101,6 +102,9 @@ class BaseSolver():
         normsq = opt.grad_norm()
         if optimize:
             opt.step(clip=self.GRAD_CLIP, grad_mul=grad_mul, use_norm=True)
+            if getattr(self, 'emb_optimizer', None) is not None:
+                from src.step import step_emb_optimizer
+                step_emb_optimizer(self.emb_optimizer, normsq, grad_mul)
         if time_cnt:
             self.timer.cnt('bw')
         return normsq.sqrt().float().reshape(()) * grad_mul
@@ -109,12 +113,16 @@ class BaseSolver():
         if self.paras.load:
             ckpt = torch.load(self.paras.load, map_location=self.device)
             self.model.load_state_dict(ckpt['model'])
+            if self.emb_decoder is not None:
+                self.emb_decoder.load_state_dict(ckpt['emb_decoder'])
             if self.mode == 'train':
                 self.step = ckpt['global_step']
                 try:
                     self.optimizer.load_opt_state_dict(ckpt['optimizer'])
                 except Exception as e:   # a checkpoint written by another optimizer implementation
                     self.verbose('optimizer state not restored: {}'.format(e))
+                if getattr(self, 'emb_optimizer', None) is not None and 'emb_optimizer' in ckpt:
+                    self.emb_optimizer.load_opt_state_dict(ckpt['emb_optimizer'])
                 self.verbose('Load ckpt from {}, restarting at step {}'.format(self.paras.load, self.step))
             else:
                 metric, score = None, None
@@ -122,6 +130,8 @@ class BaseSolver():
                     if type(v) is float:
                         metric, score = k, v
                 self.model.eval()
+                if self.emb_decoder is not None:
+                    self.emb_decoder.eval()
                 self.verbose('Evaluation target = {} (recorded {} = {:.2f} %)'.format(self.paras.load, metric, (score or 0) * 100))
 
     def verbose(self, msg):
@@ -154,8 +164,13 @@ class BaseSolver():
         ckpt_path = os.path.join(self.ckpdir, f_name)
         if self.rank == 0:
             tmp = ckpt_path + '.tmp'
-            torch.save({'model': self.model.state_dict(), 'optimizer': self.optimizer.get_opt_state_dict(),
-                        'global_step': self.step, metric: score}, tmp)
+            full_dict = {'model': self.model.state_dict(), 'optimizer': self.optimizer.get_opt_state_dict(),
+                         'global_step': self.step, metric: score}
+            if self.emb_decoder is not None:           # reference src/solver.py:192-193, plus the plugin's own optimizer state
+                full_dict['emb_decoder'] = self.emb_decoder.state_dict()
+                if getattr(self, 'emb_optimizer', None) is not None:
+                    full_dict['emb_optimizer'] = self.emb_optimizer.get_opt_state_dict()
+            torch.save(full_dict, tmp)
             os.replace(tmp, ckpt_path)
         if self.world > 1:
             torch.distributed.barrier()

@@ -5,21 +5,34 @@ import torch
 
 
 def train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate=1.0, dp=None,
-               clip=5.0, txt_len=None, optimize=True):
-    """Returns dict(total_loss, ctc_loss, att_loss, grad_normsq (device float64 scalar)).  No host sync."""
+               clip=5.0, txt_len=None, optimize=True, emb_decoder=None, emb_optimizer=None):
+    """Returns dict(total_loss, ctc_loss, att_loss, grad_normsq (device float64 scalar)).  No host sync.
+    emb_decoder: an enabled src.plugin.EmbeddingRegularizer - its loss joins the total with its weight and, when it fuses, its
+    output replaces the decoder's in the sequence loss (reference bin/train_asr.py:215-222); emb_optimizer steps its parameters."""
     from src import hipabi as H
     cur = torch.cuda.current_stream()
     if not (feat.is_cuda and H.overlap_enabled() and (dp is None or H.overlap_dp_enabled())) or cur != torch.cuda.default_stream():
-        return _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, clip, txt_len, optimize)
+        return _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, clip, txt_len, optimize,
+                           emb_decoder, emb_optimizer)
     work = H.work_stream()             # see its docstring: the CU-masked streams serialise against the default stream
     work.wait_stream(cur)
     with torch.cuda.stream(work):
-        out = _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, clip, txt_len, optimize)
+        out = _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, clip, txt_len, optimize,
+                          emb_decoder, emb_optimizer)
     cur.wait_stream(work)
     for v in out.values():
         if torch.is_tensor(v):
             v.record_stream(cur)
     return out
+
+
+def step_emb_optimizer(emb_optimizer, model_normsq, grad_mul=1.0):
+    """The plugin's parameters step beside the model's: the reference clips the MODEL's gradient norm only and skips the whole
+    update when that norm is not finite (src/solver.py:97-103), so the plugin's fused step reads the model's norm for the NaN
+    guard and does not clip."""
+    eo = emb_optimizer.opt if hasattr(emb_optimizer, 'opt') else emb_optimizer
+    eo.normsq = model_normsq
+    eo.step(clip=0.0, grad_mul=grad_mul, use_norm=True)
 
 
 def scale_weight(w_dev, k):
@@ -35,13 +48,25 @@ def scale_weight(w_dev, k):
 
 
 def _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate=1.0, dp=None,
-                clip=5.0, txt_len=None, optimize=True):
+                clip=5.0, txt_len=None, optimize=True, emb_decoder=None, emb_optimizer=None):
     from src import hipabi as H
     opt = optimizer.opt if hasattr(optimizer, 'opt') else optimizer
     opt.zero_grad()
     if txt_len is None:
         txt_len = torch.sum(txt != 0, dim=-1)
-    ctc_output, encode_len, att_output, att_align, _ = model(feat, feat_len, decode_step, tf_rate=tf_rate, teacher=txt, ctc_async=True)
+    if emb_decoder is None:
+        ctc_output, encode_len, att_output, att_align, _ = model(feat, feat_len, decode_step, tf_rate=tf_rate, teacher=txt, ctc_async=True)
+        emb_loss = None
+    else:
+        if getattr(emb_decoder, 'apply_fuse', False) and tf_rate != 1:
+            raise ValueError('embedding fusion cannot be combined with scheduled sampling (tf_rate = %r < 1): the fused output is a '
+                             'log-probability, which the reference hands to Categorical as logits and fails' % (tf_rate,))
+        emb_decoder.zero_grad()
+        ctc_output, encode_len, att_output, att_align, dec_state = model(feat, feat_len, decode_step, tf_rate=tf_rate, teacher=txt,
+                                                                         ctc_async=True, get_dec_state=True)
+        emb_loss, fuse_output = emb_decoder(dec_state, att_output, label=txt[:, :att_output.shape[1]])
+        if fuse_output is not None:
+            att_output = fuse_output
     total, ctc_loss, att_loss = None, None, None
     from src.functions import LossMixFn, loss_weight
     dev = feat.device
@@ -68,6 +93,8 @@ def _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decod
         total = LossMixFn.apply(ctc_loss, loss_weight(model.ctc_weight, dev), None, None)
     else:
         total = LossMixFn.apply(att_loss, w_att, None, None)
+    if emb_loss is not None:                # total += emb.weight * emb_loss (bin/train_asr.py:218)
+        total = LossMixFn.apply(total, loss_weight(1.0, dev), emb_loss, loss_weight(emb_decoder.weight, dev))
     total.backward()
     H.join_side()          # parameter-gradient work issued on the side stream (no-op when the engine callback already ran)
     grad_mul = 1.0
@@ -77,6 +104,8 @@ def _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decod
     normsq = opt.grad_norm()
     if optimize:
         opt.step(clip=clip, grad_mul=grad_mul, use_norm=True)
-    return {'total_loss': total.detach(), 'ctc_loss': ctc_loss, 'att_loss': att_loss, 'grad_normsq': normsq,
+        if emb_optimizer is not None:
+            step_emb_optimizer(emb_optimizer, normsq, grad_mul)
+    return {'total_loss': total.detach(), 'ctc_loss': ctc_loss, 'att_loss': att_loss, 'emb_loss': emb_loss, 'grad_normsq': normsq,
             'grad_mul': grad_mul, 'ctc_output': ctc_output, 'att_output': att_output, 'att_align': att_align,
             'encode_len': encode_len}

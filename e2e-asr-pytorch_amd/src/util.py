@@ -140,5 +140,44 @@ def cal_er(tokenizer, pred, truth, mode='wer', ctc=False):
     return sum(er) / len(er)
 
 
+def load_embedding(text_encoder, embedding_filepath):
+    """Word vectors in the fastText text format -> (vocab_size, E) float64 array in the tokenizer's order, with the meaning the
+    reference gives the file (its src/util.py:142-172): a `count E` header line, then `token v_1 ... v_E` per line; fastText's
+    `</s>` stands for <eos>; a token the tokenizer does not know counts towards <unk>, whose row is the average of all such
+    vectors; a token without a line (<pad>) keeps a zero row; of two lines for one token the later wins.  One addition: a line
+    that begins with a blank carries the vector of the blank itself (character vocabularies have one)."""
+    import numpy as np
+    unk = text_encoder.unk_idx
+
+    def row_of(token):
+        if text_encoder.token_type == 'subword':
+            return text_encoder.spm.piece_to_id(token)
+        if token == '<eos>':
+            return text_encoder.eos_idx
+        if token == ' ':
+            return getattr(text_encoder, '_vocab2idx', {}).get(' ', unk)
+        return text_encoder.encode(token)[0]              # encode appends <eos>: the first id is the token's
+
+    with open(embedding_filepath, 'r') as f:
+        width = int(f.readline().split()[1])
+        table = np.zeros((text_encoder.vocab_size, width))
+        unk_sum, unk_lines = np.zeros(width), 0
+        for raw in f:
+            fields = raw.split()
+            if not fields:
+                continue
+            token, values = (' ', fields) if raw[0] == ' ' else (fields[0], fields[1:])
+            vec = np.array(values, dtype=np.float64)
+            row = row_of('<eos>' if token == '</s>' else token)
+            if row == unk:
+                unk_sum += vec
+                unk_lines += 1
+            else:
+                table[row] = vec
+    if unk_lines:
+        table[unk] = unk_sum / unk_lines
+    return table
+
+
 def count_parameters(model):
     return sum(p.numel() for p in model.parameters() if p.requires_grad)

@@ -307,7 +307,7 @@ class ScaleDotAttention(nn.Module):
 # ---------------------------------------------------------------------------------------------------------------------
 # the step loop (reference ASR.forward src/asr.py:124-175, Attention.forward :331-364, Decoder.forward :262-270)
 # ---------------------------------------------------------------------------------------------------------------------
-def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, ctx):
+def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, ctx, emb_decoder=None):
     from src.functions import EmbeddingFn
     att, dec, prec = model.attention, model.decoder, model.prec
     B, T, _ = enc.shape
@@ -397,6 +397,11 @@ def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, 
                 last_char = EmbeddingFn.apply(anchor, sampled, model.pre_embed)
                 if emb_p > 0:
                     last_char = dropout(last_char, emb_p, ctx.next_seed())
+        elif emb_decoder is not None:
+            # greedy decoding through an embedding-fusing plugin: the fused log-probs are the step's output, their argmax the next token
+            nxt = torch.empty((B,), dtype=torch.int64, device=dev)
+            cur_char = emb_decoder.fuse_rows(d_state.detach(), cur_char.detach().contiguous(), argmax=nxt, argmax_ld=1)
+            last_char = EmbeddingFn.apply(anchor, nxt, model.pre_embed)
         else:
             with torch.no_grad():
                 cand = torch.empty((B, 1), dtype=torch.int32, device=dev)

@@ -383,6 +383,60 @@ int asr_att_decoder_bwd_ex(const asr_dec_dims_t* dims, const asr_dec_weights_t* 
 int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
                                const float* enc, const int64_t* enc_len, const asr_dec_state_t* state, const float* dlogits,
                                void* workspace, size_t workspace_bytes, int looped, int prec, asr_stream_t stream);
+/* asr_att_decoder_bwd_ex with an outside gradient on the decoder states: dhs_ext (B,L,Dd), the gradient wrt the TOP layer's
+ * h_t of every step (what ASR.forward returns as dec_state; the embedding regulariser reads it, src/plugin.py), is added to
+ * dh_top = dlogits W_c by one elementwise launch on `stream` before the first recurrence kernel.  dhs_ext = NULL is
+ * asr_att_decoder_bwd_ex itself: the same launches with the same arguments. */
+int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
+                           const float* enc, const int64_t* enc_len, const asr_dec_state_t* state,
+                           const float* dlogits, const float* dhs_ext, float* denc,
+                           void* workspace, size_t workspace_bytes, int prec, int defer_params, int* looped_out,
+                           asr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Word-embedding regulariser and embedding-fused decoding (reference src/plugin.py::EmbeddingRegularizer), fp32, csrc/emb_fuse.hip.
+ * Every sum below has a fixed order (no float atomics): equal inputs give equal bits.
+ *
+ * asr_emb_cos_loss: nn.CosineEmbeddingLoss(reduction='none') with target +1 between x (B*L,E) and table[label] (table (V,E),
+ *   label (B,label_ld) int64), pad rows masked, per-utterance mean, batch mean (src/plugin.py:145-155), forward and backward
+ *   in one call:
+ *     cos_r = <x_r, y_r> / sqrt((|x_r|^2 + 1e-12) (|y_r|^2 + 1e-12))          (ATen's formula; its epsilon is the FLOAT constant 1e-12)
+ *     w_r   = 1 / (B count_b) when label_r != 0, else 0;  count_b = non-pad labels of the row's utterance
+ *     *loss = sum_r w_r (1 - cos_r);  dx (B*L,E) = d loss / d x;  dy (B*L,E) = d loss / d (gathered table rows), or NULL when
+ *     the table is frozen (asr_embedding_bwd scatters it into the table's gradient).  All three are written, not accumulated.
+ *   An utterance WITHOUT a non-pad label contributes 0 and gets zero gradients; the reference divides 0 by 0 there and returns
+ *   NaN.  Real transcripts end in <eos> and never do this.  A label outside [0,V) counts as pad.
+ *   row_loss: scratch of B*L floats (the per-row terms, summed in row order by one workgroup).
+ *   E >= 1 of any size, 2 <= V <= 65536.
+ *
+ * asr_emb_fuse_fwd: out (N,V) = log((1 - lam_v) softmax(dec_logit)_v + lam_v softmax(relu(temp_v) emb_logit)_v + 1e-8)
+ *   (src/plugin.py:103-123).  dec_logit rows are dec_ld >= V apart, emb_logit and out are dense.
+ *   temp: RAW temperature, relu applied here; temp_stride 0 = one scalar, 1 = one value per token.  temp <= 0: uniform p_emb.
+ *   lam: lam_stride as for temp; lam_sigmoid != 0: lam_v = sigmoid(lam[v]) (the learnable forms), else lam[v] itself.
+ *   lam = 0 gives log(p_dec + 1e-8) as computed, lam = 1 log(p_emb + 1e-8).  Both softmaxes subtract their row maximum.
+ *   stats (N,2): log-sum-exp of dec_logit and of relu(temp) emb_logit, kept for the backward.
+ *   argmax: NULL, or int64 with row r at argmax[r * argmax_ld]: the index of the largest out value, the lowest on a tie.
+ *   2 <= V <= 65536: one wave per row up to V = 2048, one workgroup per row above.
+ * asr_emb_fuse_bwd: d_dec_logit, d_emb_logit (N,V dense, written) from dout (N,V dense); the probabilities are formed again
+ *   from the logits and stats.  g = dout / (fused + 1e-8); each softmax backward is p (dp - <dp, p>).
+ *   d_temp / d_lam_raw: NULL, or the gradient wrt the RAW parameter (1 or V entries by its stride, written): d_temp carries
+ *   1[temp > 0], d_lam_raw carries sigmoid' when lam_sigmoid.  They need `work`: N * (temp_stride ? V : 1) floats when d_temp is
+ *   asked for plus N * (lam_stride ? V : 1) when d_lam_raw is (the per-row terms, summed over the rows in a fixed order).
+ *
+ * asr_row_normalize_fwd / _bwd: y = x / max(||x||_2, 1e-12) per row of x (N,E) (F.normalize(x, dim=-1), src/plugin.py:107-108)
+ *   and dx from dy.  A row below the epsilon is x / 1e-12 with dx = dy / 1e-12, as in torch; an all-zero row (row 0 of an
+ *   embedding table with padding_idx 0) stays zero and gets a ZERO gradient, where torch returns dy / 1e-12.
+ */
+int asr_emb_cos_loss(const float* x, const float* table, const int64_t* label, long label_ld, float* loss, float* dx, float* dy,
+                     float* row_loss, int B, int L, int E, int V, asr_stream_t stream);
+int asr_emb_fuse_fwd(const float* dec_logit, long dec_ld, const float* emb_logit, const float* temp, int temp_stride,
+                     const float* lam, int lam_stride, int lam_sigmoid, float* out, float* stats, int64_t* argmax, long argmax_ld,
+                     int N, int V, asr_stream_t stream);
+int asr_emb_fuse_bwd(const float* dout, const float* dec_logit, long dec_ld, const float* emb_logit, const float* temp,
+                     int temp_stride, const float* lam, int lam_stride, int lam_sigmoid, const float* stats, float* d_dec_logit,
+                     float* d_emb_logit, float* d_temp, float* d_lam_raw, float* work, int N, int V, asr_stream_t stream);
+int asr_row_normalize_fwd(const float* x, float* y, long N, int E, asr_stream_t stream);
+int asr_row_normalize_bwd(const float* dy, const float* x, float* dx, long N, int E, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Flat-buffer step: global-norm clip + NaN guard (src/solver.py:96-103) fused with torch.optim.Adadelta

@@ -1,0 +1,138 @@
+#!/usr/bin/env python
+"""What the word-embedding regulariser (src/plugin.py, csrc/emb_fuse.hip) costs, one JSON line (also profiles/emb_fuse.json):
+
+  train_step   the training step at config/librispeech_asr.yaml's shape (B = 16, T = 1200, L = 180, bf16) without a plugin and
+               with one (random table, E = 300, constant lambda = 0.3, temperature 2): ms per step, median of --reps after warm-up
+  fuse_kernels asr_emb_fuse_fwd / asr_emb_fuse_bwd alone at N = 2880 rows and V = 31 / 2048 / 10 000: us per call and the bytes
+               the call must move (forward: two rows read, one written; backward: three read, two written) over that time
+  decode       the joint search of tools/bench_decode.py (beam 8, ctc_weight 0.3, no LM, 16 utterances of 1270 +- 480 frames)
+               without and with a fusing plugin: ms per batch and utterances per second
+
+    python tools/bench_emb.py [--reps 5] [--skip-decode] [--skip-train]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'e2e-asr-pytorch_amd')
+sys.path.insert(0, ROOT)
+sys.path.insert(0, PKG)
+import numpy as np
+import torch
+import yaml
+
+from src import hipabi as H
+from src.asr import ASR
+from src.decode import BeamDecoder
+from src.optim import Optimizer
+from src.plugin import EmbeddingRegularizer
+from src.step import train_step
+from src.text import load_text_encoder
+from src.util import CTCLoss, CrossEntropyLoss
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--reps', type=int, default=5)
+ap.add_argument('--skip-decode', action='store_true')
+ap.add_argument('--skip-train', action='store_true')
+ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'emb_fuse.json'))
+a = ap.parse_args()
+torch.manual_seed(0)
+cfg = yaml.safe_load(open(os.path.join(PKG, 'config', 'librispeech_asr.yaml')))
+tok = load_text_encoder('character', os.path.join(PKG, 'corpus', 'librispeech_char.txt'))
+V, E = tok.vocab_size, 300
+res = {'metric': 'word-embedding regulariser and embedding-fused decoding', 'E': E, 'V': V, 'lambda': 0.3, 'temperature': 2.0,
+       'reps': a.reps, 'weights': 'random'}
+
+
+def timed(fn, reps, warm=2):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def make_plugin(dec_dim, prec):
+    g = np.random.Generator(np.random.PCG64(300))
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, 'vec.txt')
+        with open(path, 'w', encoding='UTF-8') as f:
+            syms = ['</s>'] + [l.strip('\r\n') for l in open(os.path.join(PKG, 'corpus', 'librispeech_char.txt'), encoding='UTF-8')]
+            f.write('%d %d\n' % (len(syms), E))
+            for s in syms:
+                f.write('%s %s\n' % (s, ' '.join('%.4f' % x for x in g.standard_normal(E))))
+        return EmbeddingRegularizer(tok, dec_dim, True, path, 'CosEmb', 0.5, 0.3, 2.0, prec=prec).cuda()
+
+
+if not a.skip_train:
+    B, T, L, D = 16, 1200, 180, 160
+    feat = torch.rand(B, T, D, device='cuda')
+    flen = torch.full((B,), T, dtype=torch.int64, device='cuda')
+    txt = torch.randint(2, V, (B, L), device='cuda')
+    txt[:, -1] = 1
+    out = {}
+    for name in ('plain', 'emb'):
+        torch.manual_seed(1)
+        model = ASR(D, V, B, prec='bf16', **cfg['model']).cuda().train()
+        plugin = make_plugin(model.dec_dim, 'bf16').train() if name == 'emb' else None
+        opt = Optimizer(model.parameters(), 'Adadelta', 1.0, 1e-8)
+        eopt = Optimizer(plugin.trainable_parameters(), 'Adadelta', 1.0, 1e-8) if plugin is not None else None
+        with torch.cuda.stream(H.work_stream()):
+            out[name] = timed(lambda: train_step(model, opt, CTCLoss(), CrossEntropyLoss(), feat, flen, txt, L, emb_decoder=plugin,
+                                                 emb_optimizer=eopt), a.reps, warm=3)
+        H.raise_if_aborted()
+        del model, plugin, opt, eopt
+    res['train_step'] = {'shape': 'B16 T1200 L180 bf16', 'ms_plain': out['plain'], 'ms_emb': out['emb']}
+
+kern = {}
+N = 2880
+for Vk in (31, 2048, 10000):
+    dec, emb, dout = (torch.randn(N, Vk, device='cuda') for _ in range(3))
+    temp, lam = torch.full((1,), 2.0, device='cuda'), torch.full((1,), 0.3, device='cuda')
+    o, dd, de = (torch.empty(N, Vk, device='cuda') for _ in range(3))
+    stats = torch.empty(N, 2, device='cuda')
+    sp = H.stream_ptr()
+    fwd = lambda: H.call('asr_emb_fuse_fwd', H.ptr(dec), Vk, H.ptr(emb), H.ptr(temp), 0, H.ptr(lam), 0, 0, H.ptr(o), H.ptr(stats), None, 1,
+                         N, Vk, sp)
+    bwd = lambda: H.call('asr_emb_fuse_bwd', H.ptr(dout), H.ptr(dec), Vk, H.ptr(emb), H.ptr(temp), 0, H.ptr(lam), 0, 0, H.ptr(stats), H.ptr(dd),
+                         H.ptr(de), None, None, None, N, Vk, sp)
+    row = {}
+    for nm, fn, nbytes in (('fwd', fwd, 3 * N * Vk * 4), ('bwd', bwd, 5 * N * Vk * 4)):
+        ms = timed(lambda: [fn() for _ in range(20)], a.reps) / 20          # 20 calls enqueued per timing window
+        row[nm] = {'us': ms * 1e3, 'bytes': nbytes, 'GBps': nbytes / (ms * 1e-3) / 1e9}
+    kern['V%d' % Vk] = row
+res['fuse_kernels'] = {'N': N, **kern}
+
+if not a.skip_decode:
+    U = 16
+    ln = np.clip(np.random.RandomState(1234).normal(1270, 480, U), 150, 2450).astype(np.int64)
+    T = int(ln.max())
+    feat, flen = torch.rand(U, T, 160, device='cuda'), torch.from_numpy(ln).cuda()
+    for u in range(U):
+        feat[u, int(ln[u]):] = 0
+    torch.manual_seed(2)
+    model = ASR(160, V, 1, prec='bf16', **cfg['model']).cuda().eval()
+    plugin = make_plugin(model.dec_dim, 'bf16').eval()
+    kw = dict(beam_size=8, min_len_ratio=0.01, max_len_ratio=0.05, ctc_weight=0.3, batch_encode=True)
+    d_plain, d_emb = BeamDecoder(model, None, **kw), BeamDecoder(model, plugin, **kw)
+    ms_p = timed(lambda: d_plain(feat, flen), a.reps, warm=1)
+    ms_e = timed(lambda: d_emb(feat, flen), a.reps, warm=1)
+    H.raise_if_aborted()
+    res['decode'] = {'utterances': U, 'frames_max': T, 'beam': 8, 'ms_plain': ms_p, 'ms_emb': ms_e, 'utt_per_s_plain': U * 1e3 / ms_p,
+                     'utt_per_s_emb': U * 1e3 / ms_e}
+
+line = json.dumps(res)
+print(line)
+if a.out:
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(line + '\n')
