@@ -1,8 +1,9 @@
 """GPU acoustic front-end with the reference's module names (src/audio.py): ExtractAudioFeature (fbank),
-Delta, CMVN, Postprocess, Augment (SpecAugment), create_transform.  Unlike the reference — one utterance at a
+Delta, CMVN, Postprocess, Augment (SpecAugment), create_transform, and WaveAugment for the reference's waveform augmenter
+(time_aug).  Unlike the reference — one utterance at a
 time on CPU DataLoader workers — these modules take a zero-padded BATCH on the device plus lengths and run
-the HIP kernels of csrc/frontend.hip.  Only constant tables (window, DFT basis, mel filterbank, delta
-filters) are built on the host."""
+the HIP kernels of csrc/frontend.hip and csrc/wave_aug.hip.  Only constant tables (window, DFT basis, mel filterbank, delta
+filters, FFT twiddles) are built on the host."""
 import math
 
 import numpy as np
@@ -173,6 +174,46 @@ class Augment(nn.Module):
         return x, lens
 
 
+def wave_aug_table(n_fft):
+    """What the FFT kernels of csrc/wave_aug.hip read: n_fft/2 twiddles (cos, -sin)(2 pi k / n_fft) interleaved, then the periodic
+    Hann window, 2 * n_fft float32 in all, rounded once from float64."""
+    k = np.arange(n_fft // 2, dtype=np.float64)
+    tw = np.stack([np.cos(2.0 * np.pi * k / n_fft), -np.sin(2.0 * np.pi * k / n_fft)], 1).reshape(-1)
+    win = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft, dtype=np.float64) / n_fft)
+    return np.concatenate([tw, win]).astype(np.float32)
+
+
+class WaveAugment(nn.Module):
+    """The reference's ReadAudio.augmenter (src/audio.py:283-309: Gaussian noise, time stretch, pitch shift) on a zero-padded
+    waveform batch, in place: wav (B,N) fp32 + wav_len (B) -> the same two.  draws (B,6) float32 = {noise_on, amp, stretch_on,
+    rate, pitch_on, semitones} skips the device RNG, as Augment's draws do."""
+
+    def __init__(self, seed=0, n_fft=2048):
+        super().__init__()
+        self.seed, self.n_fft, self.calls = seed, n_fft, 0
+        self.register_buffer('table', torch.from_numpy(wave_aug_table(n_fft)), persistent=False)
+        self._ws = None
+
+    def forward(self, wav, wav_len, draws=None):
+        if wav.dtype != torch.float32 or not wav.is_contiguous():
+            raise ValueError('WaveAugment works in place on a contiguous float32 (B,N) batch')
+        B, N = wav.shape
+        lens = wav_len.to(wav.device, torch.int64).contiguous()
+        d_in = None
+        if draws is not None:
+            d_in = draws.to(wav.device, torch.float32).contiguous()
+        self.calls += 1
+        nbytes = H.lib().asr_wave_augment_workspace_bytes(B, N, self.n_fft)
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != wav.device:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=wav.device)
+        H.call('asr_wave_augment', H.ptr(wav), H.ptr(lens), H.ptr(d_in), None, H.ptr(self.table), B, N, self.n_fft,
+               (self.seed * 1000003 + self.calls) & 0xFFFFFFFFFFFF, H.ptr(self._ws), self._ws.numel(), H.stream_ptr())
+        return wav, wav_len
+
+    def extra_repr(self):
+        return 'seed={}, n_fft={}'.format(self.seed, self.n_fft)
+
+
 class FrontEnd(nn.Module):
     def __init__(self, stages):
         super().__init__()
@@ -192,8 +233,9 @@ def create_transform(audio_config, mode='train'):
     apply_cmvn = cfg.pop('apply_cmvn', False)
     feat_type, feat_dim = cfg.pop('feat_type'), cfg.pop('feat_dim')
     augment = cfg.pop('augment', False)
-    cfg.pop('time_aug', False)
-    stages = [ExtractAudioFeature(mode=feat_type, num_mel_bins=feat_dim, sample_rate=SAMPLE_RATE, **cfg)]
+    time_aug = cfg.pop('time_aug', False)
+    stages = [WaveAugment()] if time_aug and mode == 'train' else []
+    stages.append(ExtractAudioFeature(mode=feat_type, num_mel_bins=feat_dim, sample_rate=SAMPLE_RATE, **cfg))
     if delta_order >= 1:
         stages.append(Delta(delta_order, delta_window))
     if apply_cmvn:

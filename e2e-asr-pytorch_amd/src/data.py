@@ -171,6 +171,9 @@ def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, ra
         msg = ['Data spec. | Corpus = synthetic LibriSpeech-shaped %s (no corpus on disk)' % ('waveforms' if wave else 'feature batches'),
                'I/O spec.  | Audio Feature = {}\t| Feature Dim = {}\t| Token Type = {}\t| Vocab Size = {}'.format(
                    audio['feat_type'], feat_dim, tokenizer.token_type, tokenizer.vocab_size)]
+        if audio.get('time_aug', False):
+            msg.append('           | Waveform augmentation (time_aug) on the GPU, training batches only' if wave else
+                       "           | time_aug: True ignored: feature batches carry no waveform to augment (use 'synthetic-wav')")
         return tr, dv, feat_dim, tokenizer.vocab_size, tokenizer, msg
 
     # waveform shards on disk
@@ -200,6 +203,8 @@ def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, ra
            '           | Batch size = {}\t\t| Bucketing = {}'.format(bs, bucketing),
            'I/O spec.  | Audio Feature = {} (GPU front-end)\t| Feature Dim = {}\t| Token Type = {}\t| Vocab Size = {}'.format(
                audio['feat_type'], feat_dim, tokenizer.token_type, tokenizer.vocab_size)]
+    if audio.get('time_aug', False) and mode == 'train':
+        msg.append('           | Waveform augmentation (time_aug) on the GPU, training batches only')
     return tr, dv, feat_dim, tokenizer.vocab_size, tokenizer, msg
 
 

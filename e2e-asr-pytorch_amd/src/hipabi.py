@@ -94,6 +94,13 @@ SIGNATURES = {
     'asr_specaug': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _u64, _vp],
     'asr_specaug_ws': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _u64, _vp, _sz, _vp],
     'asr_cmvn': [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _sz, _vp],
+    'asr_wave_draws': [_vp, _vp, _vp, _vp, _i, _i, _i, _u64, _vp],
+    'asr_wave_noise': [_vp, _vp, _vp, _i, _i, _u64, _vp],
+    'asr_wave_stft': [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
+    'asr_wave_pvoc': [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp],
+    'asr_wave_istft': [_vp, _vp, _vp, _i, _vp, _vp, _l, _i, _i, _i, _i, _vp],
+    'asr_wave_resample': [_vp, _l, _vp, _vp, _i, _vp, _i, _i, _i, _vp],
+    'asr_wave_augment': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _u64, _vp, _sz, _vp],
     'asr_conv3x3': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     'asr_conv_weight_permute': [_vp, _vp, _i, _i, _i, _vp],
     'asr_vgg16_im2col': [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -186,6 +193,7 @@ _RESTYPES = {
     'asr_gru_rec_workspace_bytes': (_sz, [_i, _i]),
     'asr_specaug_workspace_bytes': (_sz, [_i]),
     'asr_cmvn_workspace_bytes': (_sz, [_i, _i]),
+    'asr_wave_augment_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_lstm_set_persistent': (ctypes.c_int, [_i]),
     'asr_lstm_plan': (ctypes.c_int, [_i, _i, _i, _i, _i]),
     'asr_gemm_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _l, _l, _l, _i, _i, _i, _P(_i)]),

@@ -529,6 +529,50 @@ int asr_cmvn(float* x, const int64_t* lens, float* stats_out /* (B,2,D) mean, st
              void* workspace, size_t workspace_bytes, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Waveform augmentation (data.audio.time_aug; ReadAudio.augmenter src/audio.py:283-309: Gaussian noise p = 0.3, time stretch
+ * p = 0.3, pitch shift p = 0.5), in place on wav (B,N) fp32 using wav_len; DESIGN.md 4.14 is the recipe.  All stages keep every
+ * length; samples n >= min(wav_len[b], N) are neither read nor written.
+ *   draws (B,6) fp32 = {noise_on, amp, stretch_on, rate, pitch_on, semitones}.  asr_wave_draws fills draws_out from draws_in, or,
+ *     when that is NULL, from two Philox4x32-10 blocks (b, 0, 3, 0) and (b, 0, 4, 0) keyed by seed: u_i = fp32(r_i) * 2^-32,
+ *     switches u < 0.3 / 0.3 / 0.5, values lo + u * (hi - lo) over (0.001, 0.01), (0.8, 1.25), (-4, 4), all in fp32 without
+ *     contraction.  Switches come out as 0 / 1.  The stretch switch is recorded 0 when len <= n_fft/2 (no reflect padding) or the
+ *     rate is outside [0.5, 2] or NaN; the pitch switch likewise with its rate 2^(-semitones/12).  rates_out (B,2) or NULL:
+ *     {stretch rate, pitch rate} as fp32, 0 where the switch is off - what the four kernels below read.
+ *   rates: rate of utterance b at rates[b * rate_stride].  The rates live on the device, so a bad one cannot be refused by the
+ *     host: an utterance whose rate is outside [0.5, 2] (0, NaN) or whose len <= n_fft/2 is skipped by every kernel.
+ *   table (2 * n_fft) fp32: n_fft/2 twiddles (cos, -sin)(2 pi k / n_fft) interleaved, then the periodic Hann window.
+ *   asr_wave_noise: x[n] += amp * z[n] where noise_on; z as stated in csrc/wave_aug.hip (Box-Muller, Philox (n/4, b, 5, 0)).
+ *   asr_wave_stft: spec (B, F = 1 + N/hop, n_fft/2 + 1) complex fp32, hop = n_fft/4, centred, reflect padding; an utterance
+ *     writes its 1 + len/hop frames.
+ *   asr_wave_pvoc: out (B, 2F, n_fft/2 + 1) complex; an utterance writes ceil(n_frames / rate) frames.
+ *   asr_wave_istft: overlap-add to M = round(len / rate) samples (half to even).  keep_len = 1: dst[b * dst_stride + m] for
+ *     m < len, zeros from M on (dst_stride >= N; the wave itself); keep_len = 0: m < M (dst_stride >= 2N).
+ *   asr_wave_resample: wav[b][i], i < len, = the band-limited interpolation of src[b * src_stride + 0..M) at i / rate
+ *     (src_stride >= 2N).
+ *   asr_wave_augment: asr_wave_draws, asr_wave_noise, then stft -> pvoc -> istft(keep_len) with the stretch rates, then
+ *     stft -> pvoc -> istft -> resample with the pitch rates, in slices of utterances whose spectrograms fit 256 MiB; bit for bit
+ *     what the single entry points give.  workspace: asr_wave_augment_workspace_bytes(B, N, n_fft) bytes (0 for bad
+ *     arguments), 16-byte aligned, contents irrelevant.  No allocation, no host sync, no atomics: two calls give the same bits.
+ * Refused with ASR_E_ARG, nothing launched: a null pointer (draws_in, draws_out of asr_wave_augment and rates_out may be NULL),
+ * B or N <= 0, B > 65535, N > 2^28, n_fft not a power of two in 64..2048, rate_stride <= 0, a stride below the stated one, keep_len
+ * other than 0 / 1, a short or misaligned workspace.
+ */
+int asr_wave_draws(const int64_t* wav_len, const float* draws_in, float* draws_out, float* rates_out, int B, int N, int n_fft,
+                   uint64_t seed, asr_stream_t stream);
+int asr_wave_noise(float* wav, const int64_t* wav_len, const float* draws, int B, int N, uint64_t seed, asr_stream_t stream);
+int asr_wave_stft(const float* wav, const int64_t* wav_len, const float* rates, int rate_stride, const float* table, float* spec,
+                  int B, int N, int n_fft, asr_stream_t stream);
+int asr_wave_pvoc(const float* spec, const int64_t* wav_len, const float* rates, int rate_stride, float* out, int B, int N,
+                  int n_fft, asr_stream_t stream);
+int asr_wave_istft(const float* out_spec, const int64_t* wav_len, const float* rates, int rate_stride, const float* table,
+                   float* dst, long dst_stride, int keep_len, int B, int N, int n_fft, asr_stream_t stream);
+int asr_wave_resample(const float* src, long src_stride, const int64_t* wav_len, const float* rates, int rate_stride, float* wav,
+                      int B, int N, int n_fft, asr_stream_t stream);
+size_t asr_wave_augment_workspace_bytes(int B, int N, int n_fft);
+int asr_wave_augment(float* wav, const int64_t* wav_len, const float* draws_in, float* draws_out, const float* table, int B,
+                     int N, int n_fft, uint64_t seed, void* workspace, size_t workspace_bytes, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * VGG front-ends (VGGExtractor src/module.py:659-716, VGGExtractor_LN :582-657) on channel-last images
  * (B,T,F,C).  asr_conv3x3 = nn.Conv2d(k=3, stride 1, pad 1) as an implicit GEMM on MFMA:
  *   mode 0: out[(b,t,f), n] (+)= act( sum_{tap,ci} img[(b,t+dt,f+df), ci] * w[n][tap*C+ci] + bias[n] )
