@@ -1427,6 +1427,65 @@ static __global__ __launch_bounds__(256) void add_rows_kernel(float* dst, long d
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[(i / width) * dst_ld + i % width] += src[i];
 }
 
+// Both backward loops take the dot of the softmax backward from the SAVED context (att_bwd_energy_kernel and the persistent launch:
+// dot = dctx . ctx), which is exact only when ctx = sum_tau attn[tau] * enc[tau] over the operands the backward itself reads: the fp32
+// attention row and the bf16 copy of enc, as att_softmax_ctx_kernel<true> forms it.  The single-launch forward rounds its context
+// operands differently (coherently for a flat attention row: 0.5 % of ctx measured), which leaves sum_tau de[tau] != 0 and biases
+// every gradient of the energy path (gradient cosine 0.974 against float64 at A = 24).  Behind such a forward the context columns
+// of xin are restated from the saved attention before the loop.  grid (ceil(E/256), B, ceil(L/32)): a block owns 256 columns of 32
+// decoder steps of one utterance; the attention rows pass through LDS 64 frames at a time and each frame of enc is read once
+// for all of them (thread = four columns x 8 steps: one 8-byte load and 8 LDS broadcasts per 32 products).  E % 4 == 0.
+// The kernel OVERWRITES the saved xin: asr_att_decoder_bwd_params then takes dW_ih from the restated context, not from the value the
+// forward's gates saw (they differ by the same 0.5 %; the restated one is the exact sum).  The condition (dec_fwd_has_plan) repeats
+// what the forward tests before it takes the single launch, but for one thing the backward cannot see: a greedy or sampled forward
+// (no teacher) that was handed a work area ran the per-step loop; the restatement then forms the sum att_softmax_ctx_kernel<true>
+// already formed.  src/functions.py hands a work area to teacher-forced forwards only.  An utterance with enc_len <= 0 keeps the
+// forward's context.
+static __global__ __launch_bounds__(256) void ctx_from_saved_att_kernel(DecP p) {
+    __shared__ float s_att[32 * 64];                      // [step][frame]
+    const asr_dec_dims_t& d = p.d;
+    const int b = blockIdx.y, c4 = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int e = blockIdx.x * 256 + 4 * c4, lb = blockIdx.z * 32;
+    const int len = min((int)p.enc_len[b], d.Tp);
+    if (len <= 0) return;                                 // the whole block
+    const unsigned short* ep = reinterpret_cast<const unsigned short*>(p.s.enc16) + (long)b * d.Tp * d.E + min(e, d.E - 4);
+    float4 acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int tau0 = 0; tau0 < len; tau0 += 64) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 32 * 64; i += 256) {
+            const int r = i >> 6, tau = tau0 + (i & 63);
+            s_att[i] = (tau < len && lb + r < d.L) ? p.s.att[((long)b * d.L + lb + r) * d.Tp + tau] : 0.f;
+        }
+        __syncthreads();
+        // sixteen frames of enc in flight per thread (clamped addresses: frames past len meet a zero attention weight in LDS)
+        for (int t0 = 0; t0 < 64 && tau0 + t0 < len; t0 += 16) {
+            float4 x[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) x[u] = ld4_bf16(ep + (long)min(tau0 + t0 + u, len - 1) * d.E);
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float a = s_att[(rg * 8 + j) * 64 + t0 + u];
+                    acc[j].x += a * x[u].x; acc[j].y += a * x[u].y; acc[j].z += a * x[u].z; acc[j].w += a * x[u].w;
+                }
+            }
+        }
+    }
+    if (e < d.E) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int l = lb + rg * 8 + j;
+            if (l < d.L) {                                // Dd need not be a multiple of 4: scalar stores
+                float* o = p.s.xin + ((long)b * d.L + l) * (d.Dd + d.E) + d.Dd + e;
+                o[0] = acc[j].x; o[1] = acc[j].y; o[2] = acc[j].z; o[3] = acc[j].w;
+            }
+        }
+    }
+}
+
 extern "C" int asr_att_decoder_bwd_ex(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
                                       const float* enc, const int64_t* enc_len, const asr_dec_state_t* state,
                                       const float* dlogits, float* denc,
@@ -1515,6 +1574,9 @@ extern "C" int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_
     }
     bool looped = false;
     float* pdg = nullptr;         // gate gradients of the persistent backward (it leaves the saved gates intact)
+    const bool h16 = state->key16 != nullptr && state->enc16 != nullptr && (d.E & 3) == 0;
+    if (bf && h16 && dec_fwd_has_plan(d, *state))
+        hipLaunchKernelGGL(ctx_from_saved_att_kernel, dim3(cdiv(d.E, 256), d.B, cdiv(d.L, 32)), dim3(256), 0, st, p.f);
     if (bf && lay.ntp > 0 && state->enc16 && d.NL == 1) {
         // the whole loop as one persistent, cluster-per-utterance launch (decoder_persist.hip)
         rc = dec_bwd_persistent(d, *weights, *state, enc_len, p.dhs, p.dxin, p.dq, p.dkey, p.slots, lay.slot, p.wcatT[0], p.wqT,
@@ -1527,7 +1589,6 @@ extern "C" int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_
         }
     }
     const dim3 grid_e(lay.nte, d.B), block_e(64 * nw_e * lay.NG);
-    const bool h16 = state->key16 != nullptr && state->enc16 != nullptr && (d.E & 3) == 0;
     const dim3 grid_c(cdiv(d.Tp, lay.TC), d.B);
     for (int t = looped ? -1 : d.L - 1; t >= 0; --t) {
         const int last = (t == d.L - 1);

@@ -421,7 +421,9 @@ def overlap_enabled():
 def overlap_dp_enabled():
     """The same overlap under data parallelism (the bucket signals move into the deferred work, so an all-reduce still starts
     only when its bucket is final).  OFF by default: validated with the recording reducer on one GPU (tests/test_dp_hooks.py),
-    not yet on a multi-GPU node with RCCL kernels beside the masked streams.  ASR_OVERLAP_DP=1 switches it on."""
+    not yet on a multi-GPU node with RCCL kernels beside the masked streams.  ASR_OVERLAP_DP=1 switches it on.  With it off a
+    model that carries a reducer defers nothing, the CTC branch included
+    (tests/test_hip_step_streams.py::test_ctc_side_stays_off_under_data_parallel)."""
     return overlap_enabled() and os.environ.get('ASR_OVERLAP_DP', '0') == '1'
 
 
@@ -429,7 +431,8 @@ def ctc_side_enabled():
     """CTC head + loss on the side stream beside the decoder forward (side_branch).  OFF by default: measured on MI355X the
     16 CTC workgroups and the decoder's 240 (one per CU) need every compute unit at once; whenever three CTC workgroups share
     an XCD one decoder workgroup waits for them and the whole cluster launch with it (dec_fwd_persist 3.24 -> 3.39 ms), which
-    cancels the 0.3 ms saved: 18.05 vs 18.06 ms per step.  ASR_CTC_SIDE=1 switches it on."""
+    cancels the 0.3 ms saved: 18.05 vs 18.06 ms per step.  ASR_CTC_SIDE=1 switches it on; the path is held to the in-line step
+    by tests/test_hip_step_streams.py::test_switch_equals_inline (settings d and e)."""
     return os.environ.get('ASR_CTC_SIDE', '0') == '1'
 
 
