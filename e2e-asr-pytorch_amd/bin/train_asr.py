@@ -1,5 +1,5 @@
 """Training Solver with the reference's surface (bin/train_asr.py:17-394): `load_data`, `set_model`, `exec`,
-`fetch_data`, `validate`.  Every tensor op of the step runs in libasr_hip.so (src/asr.py, src/util.py)."""
+`fetch_data`, `validate`.  The step is src/step.py's: forward_losses here, backward_update in BaseSolver.backward."""
 import torch
 
 from src import hipabi as H
@@ -7,6 +7,7 @@ from src.asr import ASR
 from src.data import load_dataset
 from src.optim import Optimizer
 from src.solver import BaseSolver
+from src.step import forward_losses
 from src.util import human_format, cal_er, CTCLoss, CrossEntropyLoss, LabelSmoothingLoss
 
 
@@ -80,12 +81,9 @@ class Solver(BaseSolver):
     def exec(self):
         # single-process runs overlap the parameter gradients with the BPTT on CU-masked streams, which serialise against
         # the legacy default stream (src/hipabi.work_stream): the whole loop runs on a non-default stream then
-        if (self.dp is None or H.overlap_dp_enabled()) and H.overlap_enabled() and torch.cuda.is_available():
-            ws = H.work_stream()
-            ws.wait_stream(torch.cuda.current_stream())     # model init / flatten / broadcast / load_ckpt ran on the default stream
-            with torch.cuda.stream(ws):
+        if H.step_overlaps(self.dp) and torch.cuda.is_available():
+            with H.on_work_stream():       # behind model init / flatten / broadcast / load_ckpt, which ran on the default stream
                 self._exec()
-            torch.cuda.current_stream().wait_stream(H.work_stream())
         else:
             self._exec()
 
@@ -94,50 +92,28 @@ class Solver(BaseSolver):
         self.timer.set()
         while self.step < self.max_step:
             for data in self.tr_set:
-                tf_rate = self.optimizer.pre_step(self.step)
-                total_loss, ctc_loss, att_loss = 0, None, None
+                tf_rate = self.optimizer.pre_step(self.step)      # zeroes the model's gradient
+                if self.emb_reg:
+                    self.emb_decoder.zero_grad()
                 feat, feat_len, txt, txt_len = self.fetch_data(data, train=True)
                 self.timer.cnt('rd')
                 L = int(txt.shape[1])      # = max(txt_len) for a padded batch, without a device sync
-                ctc_output, encode_len, att_output, att_align, dec_state = self.model(feat, feat_len, L, tf_rate=tf_rate, teacher=txt,
-                                                                                      ctc_async=True, get_dec_state=self.emb_reg)
-                emb_loss = None
-                if self.emb_reg:                 # bin/train_asr.py:215-222 of the reference
-                    self.emb_optimizer.opt.zero_grad()
-                    emb_loss, fuse_output = self.emb_decoder(dec_state, att_output, label=txt[:, :att_output.shape[1]])
-                    total_loss = total_loss + self.emb_decoder.weight * emb_loss
-                    if self.emb_fuse:
-                        att_output = fuse_output
-                if ctc_output is not None:
-                    if getattr(ctc_output, '_asr_side', False):      # CTC branch on the side stream (src/asr.py, src/step.py)
-                        with H.side_branch(False, txt, txt_len):
-                            ctc_loss = self.ctc_loss(ctc_output.transpose(0, 1), txt, encode_len, txt_len)
-                        H.join_branch(ctc_loss, ctc_output)
-                    else:
-                        ctc_loss = self.ctc_loss(ctc_output.transpose(0, 1), txt, encode_len, txt_len)
-                    total_loss = total_loss + ctc_loss * self.model.ctc_weight
-                if att_output is not None:
-                    b, t, _ = att_output.shape
-                    att_loss = self.seq_loss(att_output.view(b * t, -1), txt[:, :t].reshape(-1))
-                    w = 1 - self.model.ctc_weight
-                    if self.dp is not None and self.dp.world > 1:
-                        w = w * self.dp.ce_weight(txt_len.sum())
-                    total_loss = total_loss + att_loss * w
+                out = forward_losses(self.model, self.ctc_loss, self.seq_loss, feat, feat_len, txt, L, tf_rate, self.dp, txt_len, self.emb_decoder)
                 self.timer.cnt('fw')
-                grad_norm = self.backward(total_loss)
+                grad_norm = self.backward(out['total_loss'])
                 self.step += 1
                 if (self.step == 1) or (self.step % self.PROGRESS_STEP == 0):
                     H.raise_if_aborted()      # the host synchronises here anyway (loss.item()): surface a refused step
                     self.progress('Tr stat | Loss - {:.2f} | Grad. Norm - {:.2f} | {}'.format(
-                        total_loss.item(), grad_norm.item(), self.timer.show()))
-                    if att_output is not None:
-                        self.write_log('loss', {'tr_att': att_loss})
-                        self.write_log(self.WER, {'tr_att': cal_er(self.tokenizer, att_output, txt)})
-                    if ctc_output is not None:
-                        self.write_log('loss', {'tr_ctc': ctc_loss})
-                        self.write_log(self.WER, {'tr_ctc': cal_er(self.tokenizer, ctc_output, txt, ctc=True)})
+                        out['total_loss'].item(), grad_norm.item(), self.timer.show()))
+                    if out['att_output'] is not None:
+                        self.write_log('loss', {'tr_att': out['att_loss']})
+                        self.write_log(self.WER, {'tr_att': cal_er(self.tokenizer, out['att_output'], txt)})
+                    if out['ctc_output'] is not None:
+                        self.write_log('loss', {'tr_ctc': out['ctc_loss']})
+                        self.write_log(self.WER, {'tr_ctc': cal_er(self.tokenizer, out['ctc_output'], txt, ctc=True)})
                     if self.emb_reg:
-                        self.write_log('emb_loss', {'tr': emb_loss})
+                        self.write_log('emb_loss', {'tr': out['emb_loss']})
                         if self.emb_fuse:
                             if self.emb_decoder.fuse_learnable:
                                 self.write_log('fuse_lambda', {'emb': self.emb_decoder.get_weight()})

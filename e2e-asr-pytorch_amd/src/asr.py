@@ -82,10 +82,9 @@ class Encoder(nn.Module):
 
     def forward(self, input_x, enc_len, ctx=None):
         if ctx is not None and input_x.is_cuda:
-            H.begin_forward()
             # CU split between the recurrence stream and the side stream follows the widest recurrent layer of THIS model
             # (eval-mode forwards are followed by backward passes too: tests, gradient checks)
-            H.configure_rec_units([m.dim for m in self.layers if isinstance(m, RNNLayer) and m.module == 'LSTM'] or [320])
+            H.begin_forward([m.dim for m in self.layers if isinstance(m, RNNLayer) and m.module == 'LSTM'] or [320])
         if self.training and ctx is not None and input_x.is_cuda:
             F_hip.prepack16([m for m in self.layers if isinstance(m, RNNLayer) and m.module == 'LSTM'], input_x.shape[0], ctx.prec)
         for layer in self.layers:
@@ -288,17 +287,18 @@ class ASR(nn.Module):
         encode_feature = F_hip.to_f32_fn(encode_feature)      # the bf16-storage encoder stack hands over bf16
         # single-process training: the CTC branch (head here, loss in the step function) runs on the side stream beside the
         # decoder loop - see hipabi.side_branch; the caller joins before it uses the loss (`_asr_side` marks the output)
-        side_ctc = (self.enable_ctc and self.enable_att and self.training and torch.is_grad_enabled() and H.overlap_enabled()
-                    and H.ctc_side_enabled() and getattr(self, '_dp', None) is None)
+        dp = getattr(self, '_dp', None)
+        overlaps = H.step_overlaps(dp)
+        side_ctc = (self.enable_ctc and self.enable_att and self.training and torch.is_grad_enabled() and overlaps
+                    and H.ctc_side_enabled() and dp is None)
         if self.enable_ctc:
-            # the head's parameter gradients may run beside the BPTT when no gradient bucket is signalled before them
-            self.ctc_layer[0]._asr_defer = getattr(self, '_dp', None) is None or H.overlap_dp_enabled()
+            # `overlaps`: the head's parameter gradients may run beside the BPTT when no gradient bucket is signalled before them
             if side_ctc:
                 with H.side_branch(True, encode_feature, encode_len):
-                    ctc_output = F_hip.CTCHeadFn.apply(ctx.anchor, encode_feature, self.ctc_layer[0], self.prec, get_logit)
+                    ctc_output = F_hip.CTCHeadFn.apply(ctx.anchor, encode_feature, self.ctc_layer[0], self.prec, get_logit, overlaps)
                 ctc_output._asr_side = bool(ctc_async)      # the step function continues the branch and joins (src/step.py)
             else:
-                ctc_output = F_hip.CTCHeadFn.apply(ctx.anchor, encode_feature, self.ctc_layer[0], self.prec, get_logit)
+                ctc_output = F_hip.CTCHeadFn.apply(ctx.anchor, encode_feature, self.ctc_layer[0], self.prec, get_logit, overlaps)
         if self.enable_att:
             L = int(decode_step)
             if not (self.decoder.fast and self.attention.fast and self.emb_drop == 0.0):

@@ -54,7 +54,7 @@ def encode_unpadded(asr, audio_feature, feature_len, with_ctc):
         encs.append(e[0])
         lens.append(int(el[0]))
         if with_ctc:
-            ctcs.append(F_hip.CTCHeadFn.apply(asr._anchor, e, asr.ctc_layer[0], asr.prec, False)[0])
+            ctcs.append(F_hip.CTCHeadFn.apply(asr._anchor, e, asr.ctc_layer[0], asr.prec, False, False)[0])
     Tp = max(e.shape[0] for e in encs)
     enc = torch.zeros((U, Tp, encs[0].shape[1]), dtype=torch.float32, device=dev)
     ctc = torch.zeros((U, Tp, asr.vocab_size), dtype=torch.float32, device=dev) if with_ctc else None
@@ -592,7 +592,7 @@ class BeamDecoder(nn.Module):
         H.call('asr_att_decoder_keys', ctypes.byref(d), ctypes.byref(w), H.ptr(enc_rep), H.ptr(sd['key']), prec, st)
         ctc_r = None
         if self.apply_ctc:
-            ctc_lp = F_hip.CTCHeadFn.apply(asr._anchor, enc, asr.ctc_layer[0], prec, False)
+            ctc_lp = F_hip.CTCHeadFn.apply(asr._anchor, enc, asr.ctc_layer[0], prec, False, False)
             scorer = CTCPrefixScore(ctc_lp)
             ctc_r = scorer.init_state().unsqueeze(0).repeat(nmax, 1, 1).contiguous()
         lm_state = self.lm.init_state(nmax, dev) if self.apply_lm else None

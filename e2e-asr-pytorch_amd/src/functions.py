@@ -398,7 +398,7 @@ def layer_backward(s, tensors, kept, dout, need_dx, in_dtype):
     # it has been issued: in line the signals stay where they were; deferred, they are deferred too, FIFO behind the work they
     # depend on, and fire on the side stream.  A storage that does not overlap first runs in line whatever the decoder and the
     # layers above deferred (H.join_side), since their buckets are signalled here.
-    defer = s.overlaps and H.overlap_enabled() and (dp is None or H.overlap_dp_enabled())
+    defer = s.overlaps and H.step_overlaps(dp)
     later = H.defer_side if defer else (lambda fn, *keep: fn())
     dout = s.cast(dout)
     if dp is not None:
@@ -455,10 +455,10 @@ def prepack16(layers, B, prec):
     dropped here."""
     for l in layers:
         l.__dict__.pop('_pack16_ev', None)
-    if not (H.overlap_enabled() and prec == H.BF16 and H.fast16_enabled() and torch.is_grad_enabled()):
+    dp = next((l.dp for l in layers if getattr(l, 'dp', None) is not None), None)
+    # data parallel: no CU-masked stream beside RCCL's kernels until that has been run (DESIGN.md 7.2)
+    if not (H.step_overlaps(dp) and prec == H.BF16 and H.fast16_enabled() and torch.is_grad_enabled()):
         return
-    if any(getattr(l, 'dp', None) is not None for l in layers) and not H.overlap_dp_enabled():
-        return                # data parallel: no CU-masked stream beside RCCL's kernels until that has been run (DESIGN.md 7.2)
     todo = [l for l in layers[1:] if fast16_layer_ok(l, B, l.w_ih_cat.shape[1])]
     if not todo:
         return
@@ -478,13 +478,13 @@ def prepack16(layers, B, prec):
 # --------------------------------------------------------------------------------------------------
 class CTCHeadFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, enc, lin, prec, get_logit):
+    def forward(ctx, anchor, enc, lin, prec, get_logit, defer):
         enc = enc.contiguous()
         B, T, E = enc.shape
         V = lin.weight.shape[0]
         act = _empty((B, T, V), enc)
         H.linear_fwd(enc.view(B * T, E), lin.weight, lin.bias, act.view(B * T, V), act=H.ACT_RELU, prec=prec)
-        ctx.lin, ctx.prec, ctx.get_logit = lin, prec, get_logit
+        ctx.lin, ctx.prec, ctx.get_logit, ctx.defer = lin, prec, get_logit, defer
         if get_logit:
             ctx.save_for_backward(enc, act)
             return act
@@ -510,7 +510,7 @@ class CTCHeadFn(torch.autograd.Function):
             dpre = _empty((B * T, V), enc)
             H.call('asr_logsoftmax_relu_bwd', H.ptr(g), H.ptr(logp), H.ptr(act), H.ptr(dpre), B * T, V, H.stream_ptr())
         denc = _empty((B, T, E), enc)
-        if getattr(lin, '_asr_defer', False) and H.overlap_enabled():
+        if ctx.defer:
             # input gradient now; the head's own gradients (a split reduction over B*T rows + a column sum) go to the side
             # stream beside the encoder's BPTT, like the decoder's (AttDecoderFn.backward)
             H.linear_bwd_input(lin.weight, dpre, denc.view(B * T, E), prec=prec)
@@ -518,7 +518,7 @@ class CTCHeadFn(torch.autograd.Function):
             H.defer_side(lambda: H.linear_bwd(x2d, lin.weight, dpre, lin.weight.grad, lin.bias.grad, None, prec=prec), x2d, dpre)
         else:
             H.linear_bwd(enc.view(B * T, E), lin.weight, dpre, lin.weight.grad, lin.bias.grad, denc.view(B * T, E), prec=prec)
-        return None, denc, None, None, None
+        return None, denc, None, None, None, None
 
 
 def scale_by_device_scalar(x, alpha):
@@ -814,7 +814,7 @@ class AttDecoderFn(torch.autograd.Function):
         status_off = int(H.lib().asr_att_decoder_bwd_status_offset(ctypes.byref(d))) if persistent else 0
         if persistent:
             H.abort_guard(ws, status_off)
-        overlap = H.overlap_enabled() and (getattr(model, '_dp', None) is None or H.overlap_dp_enabled())
+        overlap = H.step_overlaps(getattr(model, '_dp', None))
         looped = ctypes.c_int(0)
         if dhs_top is None:
             H.call('asr_att_decoder_bwd_ex', ctypes.byref(d), ctypes.byref(w), ctypes.byref(g), H.ptr(enc), H.ptr(enc_len),

@@ -4,6 +4,7 @@ There is no CPU fallback: importing this module without the built library raises
 wrapper refuses non-CUDA tensors.  PyTorch is used for device memory and streams only.
 """
 import atexit
+import contextlib
 import ctypes
 import os
 
@@ -401,7 +402,7 @@ def rec_units_for(hidden):
 
 
 def configure_rec_units(hidden_dims):
-    """Called by the model constructor with the widths of its recurrent layers: the CU split between the recurrence stream
+    """Called by begin_forward with the widths of the model's recurrent layers: the CU split between the recurrence stream
     and the side stream follows the widest layer (ASR_REC_UNITS overrides).  Changing the split drops the cached streams."""
     global REC_UNITS
     if 'ASR_REC_UNITS' in os.environ or not hidden_dims:
@@ -427,6 +428,12 @@ def overlap_dp_enabled():
     return overlap_enabled() and os.environ.get('ASR_OVERLAP_DP', '0') == '1'
 
 
+def step_overlaps(dp):
+    """Does the step of a model with data-parallel reducer `dp` (None: single process) put work beside its chain?  Asked by the
+    step's stream (src/step.py, the Solver) and by every deferral (src/functions.py, src/asr.py); no device, no stream needed."""
+    return overlap_enabled() and (dp is None or overlap_dp_enabled())
+
+
 def ctc_side_enabled():
     """CTC head + loss on the side stream beside the decoder forward (side_branch).  OFF by default: measured on MI355X the
     16 CTC workgroups and the decoder's 240 (one per CU) need every compute unit at once; whenever three CTC workgroups share
@@ -443,12 +450,22 @@ def work_stream():
     """The non-default stream training runs on while the overlap is enabled.  Streams made by hipExtStreamCreateWithCUMask
     are BLOCKING streams: they serialise against the legacy default stream in both directions, so with the step on the
     default stream nothing overlaps (measured: the side work started when the recurrence had finished).  The training
-    loops (bin/train_asr.py, bench.py) run inside `with torch.cuda.stream(H.work_stream())`; src.step.train_step moves a
-    step that arrives on the default stream over (two cross-stream waits per step, ~0.25 ms)."""
+    loops (bin/train_asr.py, bench.py) run on it (on_work_stream); src.step.train_step moves a step that arrives on the
+    default stream over (two cross-stream waits per step, ~0.25 ms)."""
     dev = torch.cuda.current_device()
     if dev not in _work:
         _work[dev] = torch.cuda.Stream()
     return _work[dev]
+
+
+@contextlib.contextmanager
+def on_work_stream():
+    """with on_work_stream(): the block runs on the work stream behind the caller's stream, which then waits for the work stream."""
+    cur, work = torch.cuda.current_stream(), work_stream()
+    work.wait_stream(cur)
+    with torch.cuda.stream(work):
+        yield work
+    cur.wait_stream(work)
 
 
 def masked_stream(first, count):
@@ -513,6 +530,13 @@ def fast16_enabled():
     return os.environ.get('ASR_FAST16', '1') != '0'
 
 
+def _side_stream():
+    """The side stream, made at its first use: the CU-masked complement of the recurrence stream while the overlap is enabled."""
+    if _side['stream'] is None:
+        _side['stream'] = masked_stream(REC_UNITS, 32 - REC_UNITS) if overlap_enabled() else torch.cuda.Stream()
+    return _side['stream']
+
+
 class on_side_stream:
     """with on_side_stream(event, t1, t2, ...): kernels launched inside run on the side stream once `event` (recorded on the
     producing stream; None = everything issued so far on the current stream) has completed; the listed tensors are kept
@@ -526,9 +550,7 @@ class on_side_stream:
         self.tensors = [t for t in tensors if t is not None]
 
     def __enter__(self):
-        if _side['stream'] is None:
-            _side['stream'] = masked_stream(REC_UNITS, 32 - REC_UNITS) if overlap_enabled() else torch.cuda.Stream()
-        side = _side['stream']
+        side = _side_stream()
         if self.event is not None:
             side.wait_event(self.event)
         else:
@@ -552,9 +574,7 @@ class side_branch:
         self.wait, self.tensors = wait, [t for t in tensors if t is not None]
 
     def __enter__(self):
-        if _side['stream'] is None:
-            _side['stream'] = masked_stream(REC_UNITS, 32 - REC_UNITS) if overlap_enabled() else torch.cuda.Stream()
-        side = _side['stream']
+        side = _side_stream()
         if self.wait:
             side.wait_stream(torch.cuda.current_stream())
         _side['keep'].extend(self.tensors)
@@ -591,15 +611,17 @@ def defer_side(fn, *tensors):
             pass                      # not inside a backward pass: the caller joins explicitly
 
 
-def begin_forward():
+def begin_forward(hidden_dims=None):
     """Called at the start of every model forward.  A backward pass that died with an exception leaves its deferred closures
     and the 'engine callback registered' mark behind; the next backward would then neither register its join nor run its own
     deferred parameter gradients (seen as wrong gradients of the first recurrent layer in the test AFTER a failing one).
-    No backward is in flight when a forward starts, so whatever is still queued here is stale."""
+    No backward is in flight when a forward starts, so whatever is still queued here is stale.
+    hidden_dims: the widths of the model's recurrent layers, if the CU split is to follow them (configure_rec_units)."""
     if _side['deferred'] or _side.get('callback'):
         _side['deferred'] = []
         _side['callback'] = False
         del _side['keep'][:]
+    configure_rec_units(hidden_dims)
 
 
 def flush_side(after=None):

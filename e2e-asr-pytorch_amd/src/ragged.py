@@ -149,8 +149,7 @@ def encode_chunk(asr, feat, flen, with_ctc):
     dev = feat.device
     enc_m = asr.encoder
     ext = _frontend(enc_m)
-    H.begin_forward()
-    H.configure_rec_units([m.dim for m in enc_m.layers if isinstance(m, RNNLayer)] or [320])
+    H.begin_forward([m.dim for m in enc_m.layers if isinstance(m, RNNLayer)] or [320])
     if ext is None:
         # the caller's padding is not trusted: what the first projection reads there is zeros of our own
         x = masked_copy(feat.float(), torch.tensor(flen, dtype=torch.int64, device=dev))
@@ -167,5 +166,5 @@ def encode_chunk(asr, feat, flen, with_ctc):
     enc = masked_copy(F_hip.to_f32(x), lens)
     ctc = None
     if with_ctc:
-        ctc = masked_copy(F_hip.CTCHeadFn.apply(asr._anchor, enc, asr.ctc_layer[0], asr.prec, False), lens)
+        ctc = masked_copy(F_hip.CTCHeadFn.apply(asr._anchor, enc, asr.ctc_layer[0], asr.prec, False, False), lens)
     return enc, tl, el, ctc

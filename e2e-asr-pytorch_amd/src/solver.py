@@ -88,23 +88,11 @@ class BaseSolver():
 
     def backward(self, loss, time_cnt=True, optimize=True):
         """loss.backward(); gradient all-reduce (DP); clip-by-global-norm + NaN guard + optimizer step on the
-        device (reference src/solver.py:88-106).  Returns the gradient norm as a 0-dim device tensor."""
+        device (reference src/solver.py:88-106): src.step.backward_update.  Returns the gradient norm as a 0-dim device tensor."""
+        from src.step import backward_update
         if time_cnt:
             self.timer.set()
-        loss.backward()
-        from src import hipabi as H
-        H.join_side()          # side-stream work of the step (parameter gradients, CTC branch): a no-op when the engine callback ran
-        opt = self.optimizer.opt
-        grad_mul = 1.0
-        if self.dp is not None:
-            self.dp.finish()
-            grad_mul = self.dp.grad_mul
-        normsq = opt.grad_norm()
-        if optimize:
-            opt.step(clip=self.GRAD_CLIP, grad_mul=grad_mul, use_norm=True)
-            if getattr(self, 'emb_optimizer', None) is not None:
-                from src.step import step_emb_optimizer
-                step_emb_optimizer(self.emb_optimizer, normsq, grad_mul)
+        normsq, grad_mul = backward_update(loss, self.optimizer.opt, self.dp, self.GRAD_CLIP, optimize, self.emb_optimizer)
         if time_cnt:
             self.timer.cnt('bw')
         return normsq.sqrt().float().reshape(()) * grad_mul

@@ -1,6 +1,6 @@
-"""One training step on the HIP path, shared by the Solver (bin/train_asr.py) and bench.py:
-forward -> CTC + attention losses -> backward -> [gradient all-reduce] -> global-norm clip + NaN guard
-+ Adadelta, the sequence bin/train_asr.py:200-253 + src/solver.py:88-106 of the reference runs."""
+"""One training step on the HIP path: forward -> CTC + attention losses -> backward -> [gradient all-reduce] -> global-norm clip
++ NaN guard + Adadelta, the sequence bin/train_asr.py:200-253 + src/solver.py:88-106 of the reference runs.  bench.py runs it as
+train_step; the Solver runs its halves, forward_losses and backward_update, with its timer between (bin/train_asr.py)."""
 import torch
 
 
@@ -11,15 +11,12 @@ def train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode
     output replaces the decoder's in the sequence loss (reference bin/train_asr.py:215-222); emb_optimizer steps its parameters."""
     from src import hipabi as H
     cur = torch.cuda.current_stream()
-    if not (feat.is_cuda and H.overlap_enabled() and (dp is None or H.overlap_dp_enabled())) or cur != torch.cuda.default_stream():
+    if not (feat.is_cuda and H.step_overlaps(dp)) or cur != torch.cuda.default_stream():
         return _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, clip, txt_len, optimize,
                            emb_decoder, emb_optimizer)
-    work = H.work_stream()             # see its docstring: the CU-masked streams serialise against the default stream
-    work.wait_stream(cur)
-    with torch.cuda.stream(work):
+    with H.on_work_stream():           # see work_stream's docstring: the CU-masked streams serialise against the default stream
         out = _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, clip, txt_len, optimize,
                           emb_decoder, emb_optimizer)
-    cur.wait_stream(work)
     for v in out.values():
         if torch.is_tensor(v):
             v.record_stream(cur)
@@ -49,11 +46,22 @@ def scale_weight(w_dev, k):
 
 def _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate=1.0, dp=None,
                 clip=5.0, txt_len=None, optimize=True, emb_decoder=None, emb_optimizer=None):
-    from src import hipabi as H
     opt = optimizer.opt if hasattr(optimizer, 'opt') else optimizer
     opt.zero_grad()
     if txt_len is None:
         txt_len = torch.sum(txt != 0, dim=-1)
+    if emb_decoder is not None:
+        emb_decoder.zero_grad()
+    out = forward_losses(model, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, txt_len, emb_decoder)
+    normsq, grad_mul = backward_update(out['total_loss'], opt, dp, clip, optimize, emb_optimizer)
+    out.update(total_loss=out['total_loss'].detach(), grad_normsq=normsq, grad_mul=grad_mul)
+    return out
+
+
+def forward_losses(model, ctc_crit, att_crit, feat, feat_len, txt, decode_step, tf_rate, dp, txt_len, emb_decoder=None):
+    """Model call, the losses and their mix.  Returns dict(total_loss - still attached to its graph, for backward_update -
+    ctc_loss, att_loss, emb_loss, ctc_output, att_output - the plugin's when it fuses - att_align, encode_len).  Zeroes no gradient."""
+    from src import hipabi as H
     if emb_decoder is None:
         ctc_output, encode_len, att_output, att_align, _ = model(feat, feat_len, decode_step, tf_rate=tf_rate, teacher=txt, ctc_async=True)
         emb_loss = None
@@ -61,7 +69,6 @@ def _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decod
         if getattr(emb_decoder, 'apply_fuse', False) and tf_rate != 1:
             raise ValueError('embedding fusion cannot be combined with scheduled sampling (tf_rate = %r < 1): the fused output is a '
                              'log-probability, which the reference hands to Categorical as logits and fails' % (tf_rate,))
-        emb_decoder.zero_grad()
         ctc_output, encode_len, att_output, att_align, dec_state = model(feat, feat_len, decode_step, tf_rate=tf_rate, teacher=txt,
                                                                          ctc_async=True, get_dec_state=True)
         emb_loss, fuse_output = emb_decoder(dec_state, att_output, label=txt[:, :att_output.shape[1]])
@@ -95,8 +102,16 @@ def _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decod
         total = LossMixFn.apply(att_loss, w_att, None, None)
     if emb_loss is not None:                # total += emb.weight * emb_loss (bin/train_asr.py:218)
         total = LossMixFn.apply(total, loss_weight(1.0, dev), emb_loss, loss_weight(emb_decoder.weight, dev))
+    return {'total_loss': total, 'ctc_loss': ctc_loss, 'att_loss': att_loss, 'emb_loss': emb_loss, 'ctc_output': ctc_output,
+            'att_output': att_output, 'att_align': att_align, 'encode_len': encode_len}
+
+
+def backward_update(total, opt, dp=None, clip=5.0, optimize=True, emb_optimizer=None):
+    """total.backward(), the joins, [gradient all-reduce], the gradient norm and - with `optimize` - the fused step of `opt` (the
+    flat optimizer itself, src/optim.py) and of the plugin's.  Returns (normsq - a device float64 scalar - , grad_mul)."""
+    from src import hipabi as H
     total.backward()
-    H.join_side()          # parameter-gradient work issued on the side stream (no-op when the engine callback already ran)
+    H.join_side()          # side-stream work of the step (parameter gradients, CTC branch): a no-op when the engine callback ran
     grad_mul = 1.0
     if dp is not None:
         dp.finish()
@@ -106,6 +121,4 @@ def _train_step(model, optimizer, ctc_crit, att_crit, feat, feat_len, txt, decod
         opt.step(clip=clip, grad_mul=grad_mul, use_norm=True)
         if emb_optimizer is not None:
             step_emb_optimizer(emb_optimizer, normsq, grad_mul)
-    return {'total_loss': total.detach(), 'ctc_loss': ctc_loss, 'att_loss': att_loss, 'emb_loss': emb_loss, 'grad_normsq': normsq,
-            'grad_mul': grad_mul, 'ctc_output': ctc_output, 'att_output': att_output, 'att_align': att_align,
-            'encode_len': encode_len}
+    return normsq, grad_mul

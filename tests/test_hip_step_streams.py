@@ -2,7 +2,7 @@
 
 What is under test is the layer between the kernels (src/hipabi.py defer_side / flush_side / join_side / side_branch /
 join_branch / on_rec_stream / on_side_stream / begin_forward / work_stream; src/functions.py layer_backward / prepack16 /
-CTCHeadFn.backward / AttDecoderFn.backward; the side_ctc branch of src/asr.py; src/step.py and the Solver's own copy of the step
+CTCHeadFn.backward / AttDecoderFn.backward; the side_ctc branch of src/asr.py; src/step.py and the Solver's use of the step
 in bin/train_asr.py).  Families, shapes and the K = 3 schedule: tests/test_step_streams_reference.py.
 
 In-line against float64 (test_inline_step_vs_float64).  ASR_OVERLAP=0, ASR_CTC_SIDE=0.  Before each step the device's
@@ -22,7 +22,7 @@ floored at 1e-3 of the largest gradient norm (the order of the fp32 atomics is t
 the step within PARAM_BOUND = 1e-5 max-abs.  Each case also proves the path it names (storage classes, plans, defer_side calls,
 _pack16_ev from step 2 on, _asr_side, the stream a forward hook sees) and the _side invariants after every step.
 
-A backward that raised (test_backward_that_raised_leaves_nothing_behind), the Solver's copy of the step against train_step and an
+A backward that raised (test_backward_that_raised_leaves_nothing_behind), the Solver's use of the step against train_step and an
 eval pass between steps (test_solver_*): see the tests.
 
 A defect found here and fixed in csrc/decoder.hip.  test_inline_step_vs_float64[base-bf16] first measured 1 - cos = 2.18e-2 .. 2.63e-2
@@ -50,6 +50,9 @@ Worst measured ratios on MI355X, over all families and settings (RATIO lines of 
                              between two Solvers (attention.proj_k.weight; SOLVER_GRAD_BOUND); parameters after one step 1.0e-6
                              (1.12e-5 on the attention-only model; SOLVER_PARAM_BOUND); every update 0.06 of _adadelta_tol from
                              its own gradient
+    Solver (debug_emb.yaml model, joint, fusing plugin)   totals bitwise equal at every step - also when the Solver still summed the
+                             plugin's term first and with torch arithmetic (4.53065777, 4.48111534, 4.43938971 on both sides);
+                             gradients, the plugin's included, 8.65e-4 of the norm (attention.proj_k.weight), parameters 1.94e-6
 """
 import contextlib
 import os
@@ -483,19 +486,21 @@ def test_backward_that_raised_leaves_nothing_behind(monkeypatch, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# part 6: the Solver's copy of the step
+# part 6: the Solver's use of the step
 # ---------------------------------------------------------------------------------------------------------------------
-def _solver_config():
-    cfg = yaml.safe_load(open(os.path.join(PKG, 'config', 'debug.yaml')))
+def _solver_config(emb=False):
+    cfg = yaml.safe_load(open(os.path.join(PKG, 'config', 'debug_emb.yaml' if emb else 'debug.yaml')))
     cfg['data']['corpus'].update(batch_size=4, subset=12)
     cfg['data']['text']['vocab_file'] = os.path.join(PKG, cfg['data']['text']['vocab_file'])
+    if emb:
+        cfg['emb']['src'] = os.path.join(PKG, cfg['emb']['src'])
     cfg['hparas'].update(max_step=3, valid_step=1000)          # the Solver validates behind step 1 whatever valid_step says
-    cfg['model']['ctc_weight'] = 0.5       # debug.yaml is attention-only: a JOINT model, or the Solver's CTC branch (side_branch, the
-    return cfg                             # loss on the side stream, join_branch: bin/train_asr.py) would never run
+    cfg['model']['ctc_weight'] = 0.5       # both files are attention-only: a JOINT model, or the CTC branch of the step (side_branch,
+    return cfg                             # the loss on the side stream, join_branch: src/step.py) would never run under the Solver
 
 
 def _count_side_branches(monkeypatch):
-    """Every `with H.side_branch(...)` entered from here on: the forward's (src/asr.py) and the loss's (the step's own copy)."""
+    """Every `with H.side_branch(...)` entered from here on: the forward's (src/asr.py) and the loss's (src/step.py)."""
     from src import hipabi as H
     n = [0]
 
@@ -507,33 +512,40 @@ def _count_side_branches(monkeypatch):
     return n
 
 
-def _solver_run(tmp_path, name, validate=True, force=None):
+def _solver_run(tmp_path, name, validate=True, force=None, emb=False):
     """Three steps of bin/train_asr.Solver with its fetch_data, backward and validate wrapped: the initial state_dict, the fetched
     batches, the per-step losses and gradients, the state (parameters, Adadelta state, _drop_counter) before and after every step,
     whether a step's CTC output carried _asr_side, and what the eval pass left.  Every step's update is held to its own gradient
-    (_own_update).  force: states to load before each step (step-forced, as everywhere in this file)."""
+    (_own_update).  force: states to load before each step (step-forced, as everywhere in this file).  emb: config/debug_emb.yaml's
+    model and plugin; the plugin's parameters, Adadelta state and gradient are then recorded, loaded and held beside the model's."""
     sys.path.insert(0, PKG)
     from bin.train_asr import Solver
     from src import hipabi as H
     from src.module import RNNLayer
     torch.manual_seed(0)
-    solver = Solver(_solver_config(), _paras(tmp_path, name=name), 'train')
+    solver = Solver(_solver_config(emb), _paras(tmp_path, name=name), 'train')
     solver.load_data()
     solver.set_model()
-    assert solver.model.enable_ctc and solver.model.enable_att
+    assert solver.model.enable_ctc and solver.model.enable_att and (solver.emb_decoder is not None) == emb
     r = {'init': {k: v.detach().clone() for k, v in solver.model.state_dict().items()}, 'fetched': [], 'losses': [], 'grads': [], 'pre': [],
-         'post': [], 'side': [], 'eval': [], 'solver': solver}
+         'post': [], 'side': [], 'eval': [], 'solver': solver, 'egrads': []}
+    if emb:
+        r['init_emb'] = {k: v.detach().clone() for k, v in solver.emb_decoder.state_dict().items()}
     fetch, backward, val = solver.fetch_data, solver.backward, solver.validate
 
     def snap():
         o = solver.optimizer.opt
-        return {'p': solver.model.flat_param.clone(), 'sq': o.square_avg.clone(), 'ad': o.acc_delta.clone(), 'drop': solver.model._drop_counter}
+        st = {'p': solver.model.flat_param.clone(), 'sq': o.square_avg.clone(), 'ad': o.acc_delta.clone(), 'drop': solver.model._drop_counter}
+        if emb:
+            e = solver.emb_optimizer.opt
+            st.update(ep=solver.emb_decoder.flat_param.clone(), esq=e.square_avg.clone(), ead=e.acc_delta.clone())
+        return st
 
     def record_fetch(data, train=False):
         out = fetch(data, train=train)
         if train:
             if force is not None:
-                _load_solver_state(solver.model, solver.optimizer, force[len(r['pre'])])
+                _load_solver_state(solver.model, solver.optimizer, force[len(r['pre'])], solver.emb_decoder, solver.emb_optimizer)
             r['fetched'].append(tuple(t.clone() for t in out))
             r['pre'].append(snap())
         return out
@@ -547,6 +559,8 @@ def _solver_run(tmp_path, name, validate=True, force=None):
         r['losses'].append(loss.detach().clone())
         out = backward(loss, *a, **kw)
         r['grads'].append(solver.model.flat_grad.clone())
+        if emb:
+            r['egrads'].append(solver.emb_decoder.flat_grad.clone())
         r['post'].append(snap())
         return out
 
@@ -570,24 +584,36 @@ def _solver_run(tmp_path, name, validate=True, force=None):
     assert solver.step == 3 and len(r['losses']) == 3 and len(r['eval']) == 1 and len(r['side']) == 3
     for k in range(3):
         assert bool(torch.isfinite(r['losses'][k])), 'the batch must be CTC-feasible'
-        _own_update('solver %s step %d' % (name, k), r['pre'][k], r['grads'][k], r['post'][k], solver.GRAD_CLIP)
+        normsq = _own_update('solver %s step %d' % (name, k), r['pre'][k], r['grads'][k], r['post'][k], solver.GRAD_CLIP)
+        if emb:
+            _own_update('solver %s step %d plugin' % (name, k), r['pre'][k], r['egrads'][k], r['post'][k], 0.0, keys=('ep', 'esq', 'ead'),
+                        normsq=normsq)
     return r
 
 
-def _load_solver_state(model, optimizer, st):
+def _load_solver_state(model, optimizer, st, plugin=None, emb_optimizer=None):
     o = optimizer.opt
     model.flat_param.copy_(st['p']), o.square_avg.copy_(st['sq']), o.acc_delta.copy_(st['ad'])
     model._drop_counter = st['drop']
+    if plugin is not None:             # as _Run.load
+        e = emb_optimizer.opt
+        plugin.flat_param.copy_(st['ep']), e.square_avg.copy_(st['esq']), e.acc_delta.copy_(st['ead'])
 
 
-@pytest.mark.parametrize('ctc_side', ['0', '1'])
-def test_solver_step_equals_train_step(ctc_side, monkeypatch, tmp_path):
-    """bin/train_asr.Solver._exec carries its own copy of the step, the continuation of the CTC side branch included.  Three steps
+@pytest.mark.parametrize('ctc_side,emb', [('0', False), ('1', False), ('0', True)], ids=['0', '1', 'emb'])
+def test_solver_step_equals_train_step(ctc_side, emb, monkeypatch, tmp_path):
+    """bin/train_asr.Solver._exec runs the step of src/step.py in two halves (forward_losses, then backward_update inside
+    BaseSolver.backward) with its own zeroing of the gradients, the continuation of the CTC side branch included.  Three steps
     of it on config/debug.yaml's model made joint (ctc_weight 0.5; synthetic corpus, batches of 4, T up to 2450) against
     train_step over the same fetched batches, from the same initial state_dict and seeds.  Under ASR_CTC_SIDE=1 both take the
     side branch in every step (two `with H.side_branch` per step: the head in ASR.forward, the loss in the step; _asr_side on the
     CTC output), under 0 neither does.  Per-step losses bitwise equal; then gradients within SOLVER_GRAD_BOUND of their norm,
     parameters within SOLVER_PARAM_BOUND, and each side's p / square_avg / acc_delta held to its own gradient (_own_update).
+
+    `emb`: config/debug_emb.yaml's model made joint in the same way, with its fusing plugin: the Solver hands the plugin, its
+    optimizer and the zeroing of its gradient to the shared step.  The total (the plugin's term included) is bitwise equal, the
+    plugin's gradient and parameters are held by the same two bounds as the model's, and its update to its own gradient under the
+    model's norm.
 
     Step-forced: before each step the Solver's parameters, Adadelta state and _drop_counter are copied into the train_step model.
     A free-running loop cannot be held to equal bits at this shape, and neither can two runs of the Solver itself: measured on
@@ -603,9 +629,9 @@ def test_solver_step_equals_train_step(ctc_side, monkeypatch, tmp_path):
     from src.util import CTCLoss, LabelSmoothingLoss
     _setenv(monkeypatch, {'ASR_CTC_SIDE': ctc_side})
     entered = _count_side_branches(monkeypatch)
-    r = _solver_run(tmp_path, 'solver' + ctc_side)
+    r = _solver_run(tmp_path, 'solver' + ctc_side + ('emb' if emb else ''), emb=emb)
     solver = r['solver']
-    # the path: the Solver's own continuation of the side branch ran in every step, or in none
+    # the path: the continuation of the side branch ran under the Solver in every step, or in none
     assert r['side'] == [ctc_side == '1'] * 3, r['side']
     assert entered[0] == (6 if ctc_side == '1' else 0), entered
     cfg = solver.config
@@ -615,35 +641,53 @@ def test_solver_step_equals_train_step(ctc_side, monkeypatch, tmp_path):
     model.train()
     opt = Optimizer(model.parameters(), **dict(cfg['hparas']))
     assert torch.equal(model.flat_param, r['pre'][0]['p'])
-    mine, after, grads, sides = [], [], [], []
+    plugin = eopt = None
+    if emb:
+        from src.plugin import EmbeddingRegularizer
+        plugin = EmbeddingRegularizer(solver.tokenizer, model.dec_dim, prec=cfg['hip']['prec'], seed=solver.paras.seed, **cfg['emb']).cuda()
+        plugin.load_state_dict(r['init_emb'])
+        plugin.train()
+        assert plugin.apply_fuse and torch.equal(plugin.flat_param, r['pre'][0]['ep'])
+        eopt = Optimizer(plugin.trainable_parameters(), **dict(cfg['hparas']))
+    mine, after, grads, sides, egrads = [], [], [], [], []
     ws = H.work_stream()
     ws.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(ws):
         for k, (feat, flen, txt, tl) in enumerate(r['fetched']):
-            _load_solver_state(model, opt, r['pre'][k])
+            _load_solver_state(model, opt, r['pre'][k], plugin, eopt)
             out = train_step(model, opt, CTCLoss(), LabelSmoothingLoss(31, 0.1), feat, flen, txt, int(txt.shape[1]), tf_rate=1.0,
-                             clip=solver.GRAD_CLIP, txt_len=tl)
+                             clip=solver.GRAD_CLIP, txt_len=tl, emb_decoder=plugin, emb_optimizer=eopt)
             mine.append(out['total_loss'].clone())
             grads.append(model.flat_grad.clone())
             o = opt.opt
             after.append({'p': model.flat_param.clone(), 'sq': o.square_avg.clone(), 'ad': o.acc_delta.clone()})
+            if emb:
+                egrads.append(plugin.flat_grad.clone())
+                after[-1].update(ep=plugin.flat_param.clone(), esq=eopt.opt.square_avg.clone(), ead=eopt.opt.acc_delta.clone())
             sides.append(bool(getattr(out['ctc_output'], '_asr_side', False)))
     torch.cuda.current_stream().wait_stream(ws)
     torch.cuda.synchronize()
     H.raise_if_aborted()
     assert sides == r['side'] and entered[0] == (12 if ctc_side == '1' else 0), (sides, entered)
-    diffs = [float((a['p'] - post['p']).abs().max()) for a, post in zip(after, r['post'])]
+    tag = ctc_side + (' emb' if emb else '')
+    diffs = [max(float((a[x] - post[x]).abs().max()) for x in ('p', 'ep') if x in a) for a, post in zip(after, r['post'])]
     ratios = [_grad_ratio(g, gs, _params(model)) for g, gs in zip(grads, r['grads'])]
+    if emb:
+        ratios = [max(x, _grad_ratio(g, gs, [('emb_decoder', 0, g.numel())], 'emb grad')) for x, g, gs in zip(ratios, egrads, r['egrads'])]
     for k, (a, b) in enumerate(zip(r['losses'], mine)):
-        print('RATIO solver ctc_side=%s step %d: loss %.9g train_step %.9g, gradient %.3e of the norm (%s, bound %.0e), parameters after the '
-              'step max-abs %.3e (bound %.0e), moved %.3e' % (ctc_side, k, float(a), float(b), ratios[k][0], ratios[k][1], SOLVER_GRAD_BOUND,
+        print('RATIO solver ctc_side=%s step %d: loss %.9g train_step %.9g (apart %.3e), gradient %.3e of the norm (%s, bound %.0e), parameters after the '
+              'step max-abs %.3e (bound %.0e), moved %.3e' % (tag, k, float(a), float(b), abs(float(a) - float(b)), ratios[k][0], ratios[k][1], SOLVER_GRAD_BOUND,
                                                               diffs[k], SOLVER_PARAM_BOUND, float((r['post'][k]['p'] - r['pre'][k]['p']).abs().max())))
     for k, (a, b) in enumerate(zip(r['losses'], mine)):
         assert torch.equal(a.reshape(()), b.reshape(())), (k, float(a), float(b))
         assert ratios[k][0] <= SOLVER_GRAD_BOUND, (k, ratios[k])
         assert diffs[k] <= SOLVER_PARAM_BOUND, (k, diffs[k])
         assert float((r['post'][k]['p'] - r['pre'][k]['p']).abs().max()) > 0
-        _own_update('train_step ctc_side=%s step %d' % (ctc_side, k), r['pre'][k], grads[k], after[k], solver.GRAD_CLIP)
+        normsq = _own_update('train_step ctc_side=%s step %d' % (tag, k), r['pre'][k], grads[k], after[k], solver.GRAD_CLIP)
+        if emb:
+            assert float((r['post'][k]['ep'] - r['pre'][k]['ep']).abs().max()) > 0
+            _own_update('train_step ctc_side=%s step %d plugin' % (tag, k), r['pre'][k], egrads[k], after[k], 0.0,
+                        keys=('ep', 'esq', 'ead'), normsq=normsq)
     assert solver.model._drop_counter == model._drop_counter == 3
 
 

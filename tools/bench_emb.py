@@ -86,7 +86,7 @@ if not a.skip_train:
         plugin = make_plugin(model.dec_dim, 'bf16').train() if name == 'emb' else None
         opt = Optimizer(model.parameters(), 'Adadelta', 1.0, 1e-8)
         eopt = Optimizer(plugin.trainable_parameters(), 'Adadelta', 1.0, 1e-8) if plugin is not None else None
-        with torch.cuda.stream(H.work_stream()):
+        with H.on_work_stream():
             out[name] = timed(lambda: train_step(model, opt, CTCLoss(), CrossEntropyLoss(), feat, flen, txt, L, emb_decoder=plugin,
                                                  emb_optimizer=eopt), a.reps, warm=3)
         H.raise_if_aborted()
