@@ -1269,6 +1269,12 @@ extern "C" int asr_att_decoder_energy_plan(const asr_dec_dims_t* dims, int* knma
     return ASR_OK;
 }
 
+// first 256 bytes of a work area (the abort word leads them) = 0, and the forward's launch record where the area has a status block
+static __global__ void dec_fwd_begin_kernel(unsigned* status, int has_block) {
+    status[threadIdx.x] = 0u;
+    if (has_block && threadIdx.x == 0) status[DEC_FWD_LAUNCHED_WORD] = 0u;
+}
+
 extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights,
                                    const float* enc, const int64_t* enc_len, const int64_t* teacher, int teacher_ld,
                                    const asr_dec_state_t* state, int prec, asr_stream_t stream) {
@@ -1282,7 +1288,9 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
     const bool bf = (prec == ASR_BF16);
     // the abort word (first word of `work`) is defined after EVERY call, whichever kernels run: callers fold it into
     // their status word without knowing whether the persistent launch was taken
-    if (state->work && state->work_bytes >= 256) hipMemsetAsync(state->work, 0, 256, st);
+    // and so is the word that tells the backward what this forward did (DEC_FWD_LAUNCHED_WORD: 0 here, 1 behind a single launch)
+    if (state->work && state->work_bytes >= 256)
+        hipLaunchKernelGGL(dec_fwd_begin_kernel, dim3(1), dim3(64), 0, st, (unsigned*)state->work, state->work_bytes >= DEC_STATUS_BYTES ? 1 : 0);
 
     // key = tanh(enc W_k^T + b_k), once per batch (src/asr.py:345)
     GemmCall key{enc, weights->Wk, state->key, weights->bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A};
@@ -1436,11 +1444,13 @@ static __global__ __launch_bounds__(256) void add_rows_kernel(float* dst, long d
 // decoder steps of one utterance; the attention rows pass through LDS 64 frames at a time and each frame of enc is read once
 // for all of them (thread = four columns x 8 steps: one 8-byte load and 8 LDS broadcasts per 32 products).  E % 4 == 0.
 // The kernel OVERWRITES the saved xin: asr_att_decoder_bwd_params then takes dW_ih from the restated context, not from the value the
-// forward's gates saw (they differ by the same 0.5 %; the restated one is the exact sum).  The condition (dec_fwd_has_plan) repeats
-// what the forward tests before it takes the single launch, but for one thing the backward cannot see: a greedy or sampled forward
-// (no teacher) that was handed a work area ran the per-step loop; the restatement then forms the sum att_softmax_ctx_kernel<true>
-// already formed.  src/functions.py hands a work area to teacher-forced forwards only.  An utterance with enc_len <= 0 keeps the
-// forward's context.
+// forward's gates saw (they differ by the same 0.5 %; the restated one is the exact sum).  Whether the forward took the single launch
+// is not decided again here: the plan switches can change between the two passes and a launch can be declined for residency.  The
+// forward records what it did in the status block of state->work (DEC_FWD_LAUNCHED_WORD, decoder_internal.h), the backward launches
+// this kernel whenever the state carries such a block, and the kernel returns at once where the word is 0 (per-step loop, greedy or
+// sampled forward handed a work area: att_softmax_ctx_kernel<true> formed this very sum).  The record is as old as the last forward
+// on that work area: a second forward of the same area before the first one's backward replaces it.  An utterance with
+// enc_len <= 0 keeps the forward's context.
 static __global__ __launch_bounds__(256) void ctx_from_saved_att_kernel(DecP p) {
     __shared__ float s_att[32 * 64];                      // [step][frame]
     const asr_dec_dims_t& d = p.d;
@@ -1448,6 +1458,7 @@ static __global__ __launch_bounds__(256) void ctx_from_saved_att_kernel(DecP p) 
     const int e = blockIdx.x * 256 + 4 * c4, lb = blockIdx.z * 32;
     const int len = min((int)p.enc_len[b], d.Tp);
     if (len <= 0) return;                                 // the whole block
+    if (reinterpret_cast<const unsigned*>(p.s.work)[DEC_FWD_LAUNCHED_WORD] == 0u) return;    // the per-step loop ran: its context is this sum
     const unsigned short* ep = reinterpret_cast<const unsigned short*>(p.s.enc16) + (long)b * d.Tp * d.E + min(e, d.E - 4);
     float4 acc[8];
 #pragma unroll
@@ -1575,7 +1586,7 @@ extern "C" int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_
     bool looped = false;
     float* pdg = nullptr;         // gate gradients of the persistent backward (it leaves the saved gates intact)
     const bool h16 = state->key16 != nullptr && state->enc16 != nullptr && (d.E & 3) == 0;
-    if (bf && h16 && dec_fwd_has_plan(d, *state))
+    if (bf && h16 && state->work && state->work_bytes >= DEC_STATUS_BYTES)
         hipLaunchKernelGGL(ctx_from_saved_att_kernel, dim3(cdiv(d.E, 256), d.B, cdiv(d.L, 32)), dim3(256), 0, st, p.f);
     if (bf && lay.ntp > 0 && state->enc16 && d.NL == 1) {
         // the whole loop as one persistent, cluster-per-utterance launch (decoder_persist.hip)

@@ -303,7 +303,9 @@ __device__ __forceinline__ void poll_copy(const u64* src, int n16, float* dst, i
 // work area (round 2 kept an unsynchronised std::unordered_map keyed by pointer).  A fresh area (zeros) starts at epoch 0.
 constexpr int EPOCH_WORD = 1008;                 // unsigned index into the status block: bytes 4032..4035
 constexpr size_t STATUS_CLEAR_BYTES = 4032;     // what a launcher clears of the status block
-__global__ void bump_epoch_kernel(unsigned* status) { status[EPOCH_WORD] = status[EPOCH_WORD] + 1u; }
+// (behind every cluster launch; it also records that the launch was made, DEC_FWD_LAUNCHED_WORD in decoder_internal.h: the forward's
+// area carries the word to the backward, on a backward's own area nobody reads it)
+__global__ void bump_epoch_kernel(unsigned* status) { status[EPOCH_WORD] = status[EPOCH_WORD] + 1u; status[DEC_FWD_LAUNCHED_WORD] = 1u; }
 // clears [0, STATUS_CLEAR_BYTES) and [4096, 4096 + xbuf_bytes) of a work area in one launch (the epoch word survives)
 __global__ void clear_work_kernel(uint4* work, long n16) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x)

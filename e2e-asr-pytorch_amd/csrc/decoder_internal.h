@@ -20,9 +20,13 @@ DecPlanInfo dec_bwd_plan_info(const asr_dec_dims_t& d);
 // persistent plan, negative on error.  `work`: 256-byte aligned, its first 4 KB are the status block of the launch.
 int dec_fwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const float* enc,
                        const int64_t* enc_len, void* work, size_t work_bytes, hipStream_t st);
-// true when dec_fwd_persistent, handed this state's work area, takes a single-launch plan (switches, plan, size and alignment of
-// the area, saved conv: the conditions it tests itself).  asr_att_decoder_fwd calls it for a teacher-forced bf16 loop only.
-bool dec_fwd_has_plan(const asr_dec_dims_t& d, const asr_dec_state_t& s);
+// What the forward did, for the backward: asr_att_decoder_fwd leaves 1 in this word of the status block of state->work when
+// dec_fwd_persistent launched the loop (ASR_OK) and 0 when the per-step kernels ran (switch off, no plan, area too small, launch
+// declined for residency, no teacher).  The word lies in the last 64 bytes of the block, beside the launch epoch
+// (decoder_cluster.h, EPOCH_WORD = 1008), which no launcher clears.  asr_att_decoder_bwd reads it on the device
+// (ctx_from_saved_att_kernel): it does not repeat the forward's decision from switches that may have changed since.
+constexpr int DEC_FWD_LAUNCHED_WORD = 1009;
+constexpr size_t DEC_STATUS_BYTES = 4096;
 // dhs: (B,L,Dd) gradient wrt h from the output layer; wcatT: ((Dd+E+Dd) x 4Dd) fp32 transposed [W_ih | W_hh]; wqT: (Dd x A).
 // *dgates_out: (B*L, 4Dd) gate pre-activation gradients inside `work`.
 int dec_bwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const int64_t* enc_len,

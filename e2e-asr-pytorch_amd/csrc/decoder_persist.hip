@@ -348,15 +348,6 @@ FwdPlan persist_plan(const asr_dec_dims_t& d) {
 
 }  // namespace
 
-bool dec_fwd_has_plan(const asr_dec_dims_t& d, const asr_dec_state_t& s) {
-    // every reason dec_fwd_persistent / dec_fwd_streamed have to decline, in their order
-    read_switches();
-    if (!g_persist_fwd) return false;
-    const FwdPlan pl = fwd_plan(d);
-    if (!pl.kind || !s.work || s.work_bytes < pl.total || ((uintptr_t)s.work & 255) != 0 || !s.conv) return false;
-    return pl.kind != 2 || s.enc16 != nullptr;
-}
-
 int dec_fwd_persistent(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const asr_dec_state_t& s, const float* enc,
                        const int64_t* enc_len, void* work, size_t work_bytes, hipStream_t st) {
     read_switches();

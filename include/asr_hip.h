@@ -334,7 +334,9 @@ typedef struct {        /* forward outputs / saved activations, caller-allocated
     float* conv;        /* (B,L,Kn,Tp) location-convolution output per step, kept for backward; may be NULL for inference */
     void* key16;        /* (B,Tp,A) bf16 working copy of key for the step kernels; NULL = read the fp32 tensor (fp32 mode) */
     void* enc16;        /* (B,Tp,E) bf16 working copy of enc, filled by asr_att_decoder_fwd; NULL = read enc */
-    void* work;         /* optional scratch (256B aligned, asr_att_decoder_fwd_work_bytes) enabling the single-launch forward */
+    void* work;         /* optional scratch (256B aligned, asr_att_decoder_fwd_work_bytes) enabling the single-launch forward.  Its first
+                         * 4 KB are a status block: abort word first, and a word in which asr_att_decoder_fwd records whether it took the
+                         * single launch.  asr_att_decoder_bwd reads that record, so hand it the state with the area as the forward left it. */
     size_t work_bytes;
     int64_t* tokens;    /* (B,L)      input token of each step (<sos>=0 first) */
 } asr_dec_state_t;

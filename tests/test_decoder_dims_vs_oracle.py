@@ -5,7 +5,8 @@ The three implementations of the decoder loop - per-step kernels (csrc/decoder.h
 (B, T', E, A, Dd, Kn, Ks) through their plan predicates, while the model tests only build config/librispeech_asr.yaml.
 Here `AttDecoderFn` runs on a synthetic encoder output at each point of a table of sizes, forced onto every plan the point
 accepts (asr_att_decoder_set_persistent 3: persistent, LDS-resident preferred; 3|4|8: persistent, streamed preferred;
-0: per-step kernels), and its logits, attention rows, decoder / attention / embedding gradients and encoder-output gradient
+0: per-step kernels; the cases named in MIXED_PAIRS and the B=8 resident-limit cases also under the six flag values that pair a
+forward plan with a different backward plan, so that all nine pairs run), and its logits, attention rows, decoder / attention / embedding gradients and encoder-output gradient
 are compared with oracle.asr_oracle.att_decoder run in float64 on the CPU (autograd for the backward).
 
 bf16 contraction mode runs on every plan; the weights and the encoder output are rounded to bf16 before either side sees
@@ -37,7 +38,14 @@ EPOCH_BYTE = 4 * 1008        # launch epoch inside a persistent work area's stat
 # Metrics: 'logits' / 'denc' / 'grad.<param>' relative Frobenius error (a gradient's norm floored at 1e-3 of the largest
 # gradient norm); 'proj.<param>' the systematic part of a gradient's error - its component along the reference, relative to
 # it (|<g - r, r>| / |r|^2: a whole tensor off by a factor shows here at full size while bf16 rounding noise averages out);
-# 'att' max-abs on the attention rows; 'gbias' max |d gen_energy.bias| / largest gradient norm (analytically zero).
+# 'att' max-abs on the attention rows; 'gbias' |d gen_energy.bias| (analytically zero), held in both modes to the identity bound
+# that tests/test_decoder_ctx_reference.py evaluates from the float64 restatement of the case (8 x what fp32 arithmetic of any
+# summation order leaves of the softmax identity), not to a figure read off the kernels.  The figure this table carried for it,
+# 1.94e-4 of the largest gradient norm, was the defect of a saved context that was not the backward's own sum.
+#
+# The other BF16_BENCH figures below were measured BEFORE the backward restated its context (ctx_from_saved_att_kernel) and are kept
+# as they were: re-measuring them on the code under test would repeat that mistake.  On the energy path (proj_q, proj_k, loc_conv,
+# loc_proj, gen_energy) they therefore still admit that defect's size and are superseded there by the identity.
 #
 # bf16 contraction mode, every plan.  BF16_BENCH is the largest error measured at the bench dims over ten input / weight
 # seeds (seed 0 is the one the matrix runs) and the three plans; the bound of every point is BF16_MARGIN times it, per
@@ -48,7 +56,7 @@ EPOCH_BYTE = 4 * 1008        # launch epoch inside a persistent work area's stat
 #     errors grow 16-32x there (denc 2.1e-5 vs 6.7e-7, grad up to 3.0e-5 vs 1.4e-6, six seeds); bf16 needs up to 5.2x the
 #     bench bound, so those two points get SATURATED_FACTOR = 8 and no other point does.
 BF16_BENCH = {
-    'logits': 1.27e-3, 'att': 3.62e-4, 'denc': 3.06e-3, 'gbias': 1.94e-4,
+    'logits': 1.27e-3, 'att': 3.62e-4, 'denc': 3.06e-3,
     'grad.pre_embed.weight': 2.62e-3, 'grad.decoder.char_trans.weight': 3.52e-3, 'grad.decoder.char_trans.bias': 1.05e-7,
     'grad.decoder.layers.weight_ih': 3.44e-3, 'grad.decoder.layers.weight_hh': 3.38e-3,
     'grad.decoder.layers.bias_ih': 2.64e-3, 'grad.decoder.layers.bias_hh': 2.64e-3,
@@ -68,7 +76,8 @@ BF16_MARGIN = 2.5
 BF16_FLOOR = 1e-5            # char_trans.bias: a column sum of dlogits, exact up to fp32 rounding
 SATURATED, SATURATED_FACTOR = 30.0, 8.0
 # fp32 mode, per-step kernels.  Bench dims (ten seeds): logits 2.5e-7, att 2.7e-7, denc 6.7e-7, grad 1.4e-6, proj 2.3e-7,
-# gbias 2e-8; the largest anywhere in the matrix is 3.3e-5 (grad, T'=1, where proj_k's gradient is pure rounding).
+# gbias 2e-8; the largest anywhere in the matrix is 3.3e-5 (grad, T'=1, where proj_k's gradient is pure rounding).  'gbias' here is
+# an upper cap (of the largest gradient norm) that stays beside the identity bound.
 F32_TOL = {'logits': 1e-4, 'att': 1e-5, 'denc': 1e-4, 'grad': 1e-4, 'proj': 1e-4, 'gbias': 1e-6}
 
 
@@ -169,6 +178,11 @@ for _B in (8, 16):
             CASES.append(_case('resident_%s_limit_B%d%s' % (_kind, _B, '+1' if _past else ''), B=_B, Tp=('limit', _kind, _past), L=2, f32=False))
 
 
+# cases that also run the six flag values which pair a forward plan with a DIFFERENT backward plan (the saved context and the
+# backward's operands meet across implementations there), beside the four resident_*_limit_B8* cases
+MIXED_PAIRS = ('bench', 'mid_A128', 'B9', 'enc_len1', 'L72_mid')
+
+
 def _dims(H, c, Tp=None):
     d = H.DecDims()
     d.B, d.Tp, d.E, d.A = c['B'], Tp if Tp is not None else c['Tp'], c['E'], c['A']
@@ -213,7 +227,8 @@ def _runs(H, c):
     """(precision, flags, (fwd plan, bwd plan)) for every distinct plan pair the case accepts."""
     d = _dims(H, c)
     out, seen = [], set()
-    for flags in (3, 3 | 4 | 8, 0):
+    mixed = c['id'] in MIXED_PAIRS or c['id'].startswith('resident_') and '_B8' in c['id']
+    for flags in (3, 3 | 4 | 8, 0) + ((1, 1 | 4, 2, 2 | 8, 3 | 8, 3 | 4) if mixed else ()):
         p = _plans(H, d, flags)
         if p not in seen:
             seen.add(p)
@@ -252,15 +267,13 @@ def _inputs(c, seed):
 
 
 def _oracle(c, sd, enc, enc_len, teacher, dlog):
-    """float64 forward + autograd backward on the rows that carry a gradient."""
+    """float64 forward + autograd backward on the rows that carry a gradient: oracle.att_decoder restated with its intermediates
+    kept (tests/test_decoder_ctx_reference.py, held to the oracle there), and the identity bound on d gen_energy.bias from them."""
+    import test_decoder_ctx_reference as CR          # (imports this module: resolved at call time)
     r0, r1 = c['rows'] or (0, c['B'])
-    cfg = O.ModelCfg(_model_cfg(c), D_IN, V)
-    P = {k: v.double().clone().requires_grad_(True) for k, v in sd.items()}
-    e = enc[r0:r1].clone().requires_grad_(True)
-    logits, att = O.att_decoder(e, enc_len[r0:r1], P, cfg, c['L'], teacher=teacher[r0:r1])
-    (logits * dlog[r0:r1]).sum().backward()
-    grads = {k: p.grad for k, p in P.items() if p.grad is not None}
-    return logits.detach(), att.detach(), grads, e.grad
+    ref = CR.decoder_f64(c, sd, enc[r0:r1], enc_len[r0:r1], teacher[r0:r1], dlog[r0:r1])
+    identity = CR.identity_bound(ref, enc[r0:r1], enc_len[r0:r1], c['temp'])[0]
+    return ref['logits'], ref['att'].unsqueeze(1), ref['grads'], ref['denc'], identity
 
 
 def _device(H, F, model, c, prec, flags, enc, enc_len, teacher, dlog):
@@ -303,7 +316,7 @@ def _errors(c, got, want):
     """Relative Frobenius errors per tensor, max-abs on the attention rows, gen_energy.bias against the gradient scale."""
     r0, r1 = c['rows'] or (0, c['B'])
     logits, att, grads, denc = got
-    rl, ra, rg, rd = want
+    rl, ra, rg, rd = want[:4]
     rel = lambda a, b: float((a - b).norm() / (b.norm() + 1e-30))
     err = {'logits': rel(logits[r0:r1], rl), 'att': float((att[r0:r1] - ra).abs().max()), 'denc': rel(denc[r0:r1], rd)}
     # rows without a gradient stay without one
@@ -313,8 +326,10 @@ def _errors(c, got, want):
     for n, g in grads.items():
         assert n in rg, n
         if n.endswith('gen_energy.bias'):
-            # analytically zero (softmax is shift invariant): both sides are rounding noise
-            err['gbias'] = max(float(g.abs().max()), float(rg[n].abs().max())) / gmax
+            # analytically zero (softmax is shift invariant): 'gbias' is the device's absolute value, held to the identity bound of
+            # the case; 'gbias_rel' the value against the gradient scale, which the fp32 mode's older cap reads
+            err['gbias'] = float(g.abs().max())
+            err['gbias_rel'] = max(float(g.abs().max()), float(rg[n].abs().max())) / gmax
         else:
             den = max(float(rg[n].norm()), 1e-3 * gmax)
             err['grad.' + n] = float((g - rg[n]).norm() / den)
@@ -322,17 +337,23 @@ def _errors(c, got, want):
     return err
 
 
-def _check(c, prec, err):
+def _check(c, prec, err, identity=None):
+    """identity: the case's bound on |d gen_energy.bias| (tests/test_decoder_ctx_reference.py::identity_bound) for 'gbias'."""
     bad = []
     for k, v in err.items():
-        t = 0.0 if k == 'denc_outside_rows' else _bound(c, prec, k)
+        if k == 'gbias':
+            t = identity
+        elif k == 'gbias_rel':
+            t = F32_TOL['gbias'] if prec == 'fp32' else float('inf')       # bf16: the identity bound alone
+        else:
+            t = 0.0 if k == 'denc_outside_rows' else _bound(c, prec, k)
         if not (v <= t):
             bad.append('%-48s %.3e > %.2e' % (k, v, t))
     return bad
 
 
 def measure(c, seed=0):
-    """Every run of one case: [(precision, flags, plans, launches seen, errors)].  Asserts the plan taken."""
+    """Every run of one case: [(precision, flags, plans, errors, identity bound)].  Asserts the plan taken."""
     H = _hipabi()
     from src import functions as F
     from src.asr import ASR
@@ -364,7 +385,7 @@ def _measure_runs(H, F, ASR, c, seed):
         *got, ran = _device(H, F, model, c, prec, flags, encp, enc_len, teacher, dlog)
         # a persistent plan launched exactly once per pass; the per-step kernels launched none
         assert ran == (int(plans[0] > 0), int(plans[1] > 0)), '%s %s flags %d: plans %s, persistent launches %s' % (c['id'], prec, flags, plans, ran)
-        out.append((prec, flags, plans, _errors(c, got, want)))
+        out.append((prec, flags, plans, _errors(c, got, want), want[4]))
     return out
 
 
@@ -373,8 +394,9 @@ def _measure_runs(H, F, ASR, c, seed):
 def test_decoder_vs_float64_oracle(case):
     c, runs = measure(case)
     report = []
-    for prec, flags, plans, err in runs:
-        bad = _check(c, prec, err)
+    for prec, flags, plans, err, identity in runs:
+        print('RATIO %s %s plans %s: |d gen_energy.bias| %.3e = %.3f of the identity bound' % (c['id'], prec, plans, err['gbias'], err['gbias'] / identity))
+        bad = _check(c, prec, err, identity)
         report += ['%s flags %d plans %s: %s' % (prec, flags, plans, b) for b in bad]
     assert not report, 'dims %s\n' % ({k: c[k] for k in ('B', 'Tp', 'E', 'A', 'Dd', 'Kn', 'Ks', 'NL', 'temp', 'L', 'scale')},) + '\n'.join(report)
 
@@ -471,9 +493,12 @@ def test_matrix_covers_every_plan():
     """Forward plans 1 and 2 and backward plans 1 and 2 each run at >= 4 points of the GPU matrix that differ from the
     bench point in A, E, Dd, Kn or Ks (every case asserts that it took the plan the query reports)."""
     H = _hipabi()
-    cover = {}
+    cover, pairs = {}, {}
     for c in CASES:
         c = _resolve(H, c)
+        for prec, flags, (f, b) in _runs(H, c):
+            if prec == 'bf16':
+                pairs.setdefault((f, b), set()).add(c['id'])
         if all(c[k] == BENCH[k] for k in ('A', 'E', 'Dd', 'Kn', 'Ks')):
             continue
         for prec, flags, (f, b) in _runs(H, c):
@@ -481,3 +506,6 @@ def test_matrix_covers_every_plan():
             cover.setdefault(('bwd', b), set()).add(c['id'])
     for key in (('fwd', 1), ('fwd', 2), ('bwd', 1), ('bwd', 2), ('fwd', 0), ('bwd', 0)):
         assert len(cover.get(key, ())) >= 4, (key, sorted(cover.get(key, ())))
+    # all nine (forward plan, backward plan) pairs run in bf16 somewhere in the matrix, each at more than one point
+    for pair in [(f, b) for f in range(3) for b in range(3)]:
+        assert len(pairs.get(pair, ())) >= 2, (pair, sorted(pairs.get(pair, ())))

@@ -106,9 +106,11 @@ def test_persistent_backward_matches_step_kernels(B, Tp, L, tiles):
         a, b_ = out[3][n].double(), out[1][n].double()
         assert torch.isfinite(a).all(), n
         if n.endswith('gen_energy.bias'):
-            # analytically zero (softmax is shift invariant): sum_t (1 - sum attn_t) dot_t, i.e. fp32 rounding of the attention
-            # rows times the size of dctx . ctx - both values are rounding noise whose sample changes with any rounding upstream
-            # (seen 0.8e-3 .. 1.7e-3 over the forward variants of round 3)
+            # analytically zero (softmax is shift invariant).  The 0.8e-3 .. 1.7e-3 once seen here and explained as fp32 rounding of
+            # the attention rows were a defect: both loops took dot = dctx . ctx from a saved context that the single-launch forward
+            # had rounded differently from the backward's own sum.  Since the backward restates the context the value is ~1e-7; it is
+            # held to a bound derived from float64 in tests/test_hip_decoder_ctx_vs_float64.py.  This file has no float64 side to
+            # evaluate that bound from, so the old allowance stays as a coarse cap.
             assert float(a.abs().max()) < 3e-3 and float(b_.abs().max()) < 3e-3
             continue
         rel = float((a - b_).norm() / (b_.norm() + 1e-12))
