@@ -1,8 +1,8 @@
 """GPU acoustic front-end with the reference's module names (src/audio.py): ExtractAudioFeature (fbank),
 Delta, CMVN, Postprocess, Augment (SpecAugment), create_transform, and WaveAugment for the reference's waveform augmenter
-(time_aug).  Unlike the reference — one utterance at a
-time on CPU DataLoader workers — these modules take a zero-padded BATCH on the device plus lengths and run
-the HIP kernels of csrc/frontend.hip and csrc/wave_aug.hip.  Only constant tables (window, DFT basis, mel filterbank, delta
+(time_aug); SpecAugmentPolicy (augment as a mapping: time warp, several masks, mean or zero fill) has no counterpart there.
+Unlike the reference — one utterance at a time on CPU DataLoader workers — these modules take a zero-padded BATCH on the device plus lengths and run
+the HIP kernels of csrc/frontend.hip, csrc/specaug_policy.hip and csrc/wave_aug.hip.  Only constant tables (window, DFT basis, mel filterbank, delta
 filters, FFT twiddles) are built on the host."""
 import math
 
@@ -174,6 +174,84 @@ class Augment(nn.Module):
         return x, lens
 
 
+POLICY_KEYS = {'time_warp': 0, 'freq_masks': 0, 'freq_width': 27, 'time_masks': 0, 'time_width': 100, 'time_ratio': 1.0,
+               'time_count_ratio': 0, 'fill': 'mean'}
+POLICY_MAX_FREQ_MASKS, POLICY_MAX_TIME_MASKS, POLICY_RECORD = 8, 32, 82
+
+
+def parse_policy(cfg):
+    """A mapping under data.audio.augment -> the settings asr_specaug_policy takes (seven integers and the fill), as a dict.  Missing keys take the values
+    of POLICY_KEYS (an empty mapping is the identity); ratios become per-mille with round(x * 1000).  ValueError names the key."""
+    cfg = dict(cfg)
+    for k in cfg:
+        if k not in POLICY_KEYS:
+            raise ValueError('augment: unknown key %r (known: %s)' % (k, ', '.join(POLICY_KEYS)))
+    v = dict(POLICY_KEYS, **cfg)
+    out = {}
+    for k, cap in (('time_warp', None), ('freq_masks', POLICY_MAX_FREQ_MASKS), ('freq_width', None),
+                   ('time_masks', POLICY_MAX_TIME_MASKS), ('time_width', None)):
+        x = v[k]
+        if isinstance(x, bool) or not isinstance(x, int) or x < 0 or x >= 2 ** 31 or (cap is not None and x > cap):
+            raise ValueError('augment: %s = %r must be an integer in 0..%s' % (k, x, cap if cap is not None else '2^31 - 1'))
+        out[k] = x
+    for k in ('time_ratio', 'time_count_ratio'):
+        x = v[k]
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x <= 1.0:
+            raise ValueError('augment: %s = %r must be a number in 0..1' % (k, x))
+        out[k + '_pm'] = int(round(x * 1000))
+    if v['fill'] not in ('mean', 'zero'):
+        raise ValueError("augment: fill = %r must be 'mean' or 'zero'" % (v['fill'],))
+    out['fill'] = v['fill']
+    return out
+
+
+class SpecAugmentPolicy(nn.Module):
+    """A SpecAugment policy on the padded batch (csrc/specaug_policy.hip): time warp W, freq_masks masks of at most freq_width bins,
+    time_masks masks of at most min(time_width, time_ratio * len) frames (their count min(time_masks, time_count_ratio * len) when
+    that ratio is > 0), filled with the utterance's mean or with zero.  Out of place - the warp gathers along time: x (B,T,D)
+    fp32 + lens -> (out, lens), out a buffer the module keeps between calls.  draws (B,82) int32 = {w0, c, (f0, fend) x 8,
+    (t0, tend) x 32} skips the device RNG, as Augment's draws do."""
+
+    def __init__(self, time_warp=0, freq_masks=0, freq_width=27, time_masks=0, time_width=100, time_ratio=1.0, time_count_ratio=0,
+                 fill='mean', seed=0):
+        super().__init__()
+        self.policy = parse_policy({'time_warp': time_warp, 'freq_masks': freq_masks, 'freq_width': freq_width, 'time_masks': time_masks,
+                                    'time_width': time_width, 'time_ratio': time_ratio, 'time_count_ratio': time_count_ratio, 'fill': fill})
+        self.seed, self.calls = seed, 0
+        self._ws = self._out = None
+
+    def forward(self, x, lens, draws=None):
+        if x.dtype != torch.float32 or x.dim() != 3:
+            raise ValueError('SpecAugmentPolicy takes a float32 (B,T,D) batch')
+        x = x.contiguous()
+        B, T, D = x.shape
+        lens = lens.to(x.device, torch.int64).contiguous()
+        d_in = None
+        if draws is not None:
+            d_in = draws.to(x.device, torch.int32).contiguous()
+            if d_in.numel() != B * POLICY_RECORD:
+                raise ValueError('SpecAugmentPolicy: draws must be (B, %d)' % POLICY_RECORD)
+        self.calls += 1
+        nbytes = H.lib().asr_specaug_policy_workspace_bytes(B)
+        if self._ws is None or self._ws.numel() * 8 < nbytes or self._ws.device != x.device:
+            self._ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+        if self._out is None or self._out.numel() < x.numel() or self._out.device != x.device:
+            self._out = torch.empty(x.numel(), dtype=torch.float32, device=x.device)
+        out = self._out[:x.numel()].view(B, T, D)
+        p = self.policy
+        H.call('asr_specaug_policy', H.ptr(x), H.ptr(lens), H.ptr(out), H.ptr(d_in), None, B, T, D, p['time_warp'], p['freq_masks'],
+               p['freq_width'], p['time_masks'], p['time_width'], p['time_ratio_pm'], p['time_count_ratio_pm'],
+               1 if p['fill'] == 'zero' else 0, (self.seed * 1000003 + self.calls) & 0xFFFFFFFFFFFF, H.ptr(self._ws),
+               self._ws.numel() * 8, H.stream_ptr())
+        return out, lens
+
+    def extra_repr(self):
+        p = self.policy
+        return ('time_warp={time_warp}, freq_masks={freq_masks}, freq_width={freq_width}, time_masks={time_masks}, '
+                'time_width={time_width}, time_ratio={tr}, time_count_ratio={tc}, fill={fill}, seed={seed}').format(
+                    tr=p['time_ratio_pm'] / 1000.0, tc=p['time_count_ratio_pm'] / 1000.0, seed=self.seed, **p)
+
+
 def wave_aug_table(n_fft):
     """What the FFT kernels of csrc/wave_aug.hip read: n_fft/2 twiddles (cos, -sin)(2 pi k / n_fft) interleaved, then the periodic
     Hann window, 2 * n_fft float32 in all, rounded once from float64."""
@@ -226,7 +304,8 @@ class FrontEnd(nn.Module):
 
 
 def create_transform(audio_config, mode='train'):
-    """Same keys as the reference's create_transform (src/audio.py:453-486); returns (module, feature dim)."""
+    """Same keys as the reference's create_transform (src/audio.py:453-486); returns (module, feature dim).  augment may also be
+    a mapping (POLICY_KEYS): the training chain then ends in SpecAugmentPolicy instead of Augment."""
     cfg = dict(audio_config)
     delta_order = cfg.pop('delta_order', 0)
     delta_window = cfg.pop('delta_window_size', 2)
@@ -234,6 +313,7 @@ def create_transform(audio_config, mode='train'):
     feat_type, feat_dim = cfg.pop('feat_type'), cfg.pop('feat_dim')
     augment = cfg.pop('augment', False)
     time_aug = cfg.pop('time_aug', False)
+    policy = parse_policy(augment) if isinstance(augment, dict) else None          # checked in every mode
     stages = [WaveAugment()] if time_aug and mode == 'train' else []
     stages.append(ExtractAudioFeature(mode=feat_type, num_mel_bins=feat_dim, sample_rate=SAMPLE_RATE, **cfg))
     if delta_order >= 1:
@@ -241,6 +321,10 @@ def create_transform(audio_config, mode='train'):
     if apply_cmvn:
         stages.append(CMVN())
     stages.append(Postprocess())
-    if augment and mode == 'train':
+    if policy is not None and mode == 'train':
+        stages.append(SpecAugmentPolicy(policy['time_warp'], policy['freq_masks'], policy['freq_width'], policy['time_masks'],
+                                        policy['time_width'], policy['time_ratio_pm'] / 1000.0, policy['time_count_ratio_pm'] / 1000.0,
+                                        policy['fill']))
+    elif policy is None and augment and mode == 'train':
         stages.append(Augment())
     return FrontEnd(stages), feat_dim * (delta_order + 1)

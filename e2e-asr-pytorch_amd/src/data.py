@@ -150,6 +150,17 @@ class _RankShard(torch.utils.data.Sampler):
         return iter(order[self.rank::self.world])
 
 
+def _policy_msg(audio):
+    """The message line of a SpecAugment policy (data.audio.augment as a mapping), none for True / False."""
+    if not isinstance(audio.get('augment', False), dict):
+        return []
+    from src.audio import parse_policy
+    p = parse_policy(audio['augment'])
+    return ['           | SpecAugment policy on the GPU, training batches only: warp {time_warp}, {freq_masks} x F {freq_width}, '
+            '{time_masks} x T {time_width} (p {tr}, count ratio {tc}), {fill} fill'.format(
+                tr=p['time_ratio_pm'] / 1000.0, tc=p['time_count_ratio_pm'] / 1000.0, **p)]
+
+
 def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, rank=0, world=1, mode=None):
     from functools import partial
     from src.audio import create_transform
@@ -174,6 +185,8 @@ def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, ra
         if audio.get('time_aug', False):
             msg.append('           | Waveform augmentation (time_aug) on the GPU, training batches only' if wave else
                        "           | time_aug: True ignored: feature batches carry no waveform to augment (use 'synthetic-wav')")
+        if wave and mode != 'eval':
+            msg.extend(_policy_msg(audio))
         return tr, dv, feat_dim, tokenizer.vocab_size, tokenizer, msg
 
     # waveform shards on disk
@@ -205,6 +218,8 @@ def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, ra
                audio['feat_type'], feat_dim, tokenizer.token_type, tokenizer.vocab_size)]
     if audio.get('time_aug', False) and mode == 'train':
         msg.append('           | Waveform augmentation (time_aug) on the GPU, training batches only')
+    if mode == 'train':
+        msg.extend(_policy_msg(audio))
     return tr, dv, feat_dim, tokenizer.vocab_size, tokenizer, msg
 
 

@@ -95,6 +95,7 @@ SIGNATURES = {
     'asr_specaug': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _u64, _vp],
     'asr_specaug_ws': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _u64, _vp, _sz, _vp],
     'asr_cmvn': [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _sz, _vp],
+    'asr_specaug_policy': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u64, _vp, _sz, _vp],
     'asr_wave_draws': [_vp, _vp, _vp, _vp, _i, _i, _i, _u64, _vp],
     'asr_wave_noise': [_vp, _vp, _vp, _i, _i, _u64, _vp],
     'asr_wave_stft': [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
@@ -194,6 +195,7 @@ _RESTYPES = {
     'asr_gru_rec_workspace_bytes': (_sz, [_i, _i]),
     'asr_specaug_workspace_bytes': (_sz, [_i]),
     'asr_cmvn_workspace_bytes': (_sz, [_i, _i]),
+    'asr_specaug_policy_workspace_bytes': (_sz, [_i]),
     'asr_wave_augment_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_lstm_set_persistent': (ctypes.c_int, [_i]),
     'asr_lstm_plan': (ctypes.c_int, [_i, _i, _i, _i, _i]),

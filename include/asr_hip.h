@@ -531,6 +531,37 @@ int asr_cmvn(float* x, const int64_t* lens, float* stats_out /* (B,2,D) mean, st
              void* workspace, size_t workspace_bytes, asr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SpecAugment policies (data.audio.augment as a mapping): time warp, up to 8 frequency masks, up to 32 time
+ * masks, mean or zero fill.  Out of place: x (B,T,D) fp32 is read only, out (B,T,D) must not overlap it.  Every length is taken
+ * as n = min(max(lens[b], 0), T).  At most two launches on `stream`, no allocation, no host sync, no atomics: two calls give
+ * the same bits.
+ *   Draws: word group k of utterance b is philox4x32(counter (b, k, 3, 0), key (seed lo, seed hi)); a group uses r0, r1.
+ *     group 0: the warp, active iff warp > 0 && n >= 2 warp + 1; w0 = warp + r0 % (n - 2 warp), w = r1 % (2 warp + 1) - warp,
+ *       c = clamp(w0 + w, 1, n - 2): source frame w0 lands on destination frame c;
+ *     group 1 + j, j < freq_masks: Fw = min(freq_width, D), f = r0 % (Fw + 1), f0 = r1 % (D - f + 1), band [f0, f0 + f);
+ *     group 9 + j, j < cnt, cnt = time_count_pm ? min(time_masks, n time_count_pm / 1000) : time_masks:
+ *       Tw = min(time_width, n time_ratio_pm / 1000), t = r0 % (Tw + 1), t0 = r1 % (n - t + 1), band [t0, t0 + t).
+ *   Record: (B,82) int32 per utterance {w0, c, (f0, fend) x 8, (t0, tend) x 32}, (0, 0) where a group is inactive.  draws_out
+ *     (or NULL) receives it as applied.  draws_in (or NULL) has the same layout and replaces the RNG: the warp is off unless
+ *     1 <= w0 <= n - 2 && 1 <= c <= n - 2, bands are clamped into [0, D] and [0, n] with end >= start.
+ *   Warp: destination frame t < n reads source position base + num / den: t <= c: num = t w0, den = c, base = 0; otherwise
+ *     num = (t - c)(n - 1 - w0), den = n - 1 - c, base = w0.  With i = base + num / den and r = num % den in integers the value
+ *     is x[i] when r == 0, else x[i] + float(r) / float(den) * (x[i + 1] - x[i]) in fp32.  Warp off: out = x bit for bit.
+ *   Fill: 1 = exactly 0.0f; 0 = one value per utterance, float32(sum / (n D)) over the n D valid values of x, the sum formed in
+ *     float64 at fixed slots and added in a fixed order (with fill = 1 that launch is skipped and workspace may be NULL).
+ *   Output: t < n: the fill inside any band, else the warped value; rows t >= n, and an utterance with n == 0, are copies of x.
+ *   workspace: asr_specaug_policy_workspace_bytes(B) bytes, 8-byte aligned, contents irrelevant.
+ * Refused with ASR_E_ARG, nothing launched: a null x, lens or out; B, T or D <= 0; freq_masks outside 0..8, time_masks outside
+ * 0..32; a negative warp, freq_width or time_width; a per-mille value outside 0..1000; fill outside {0, 1}; x and out that
+ * overlap; a workspace below the stated size or not 8-byte aligned; a NULL workspace with fill = 0; B beyond 2^25.
+ */
+size_t asr_specaug_policy_workspace_bytes(int B);
+int asr_specaug_policy(const float* x, const int64_t* lens, float* out, const int* draws_in, int* draws_out,
+                       int B, int T, int D, int warp, int freq_masks, int freq_width, int time_masks, int time_width,
+                       int time_ratio_pm, int time_count_pm, int fill /* 0 mean, 1 zero */, uint64_t seed,
+                       void* workspace, size_t workspace_bytes, asr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Waveform augmentation (data.audio.time_aug; ReadAudio.augmenter src/audio.py:283-309: Gaussian noise p = 0.3, time stretch
  * p = 0.3, pitch shift p = 0.5), in place on wav (B,N) fp32 using wav_len; DESIGN.md 4.14 is the recipe.  All stages keep every
  * length; samples n >= min(wav_len[b], N) are neither read nor written.
