@@ -14,11 +14,25 @@
 #include "gemm_plan.h"
 #include "decoder_internal.h"
 #include <stdlib.h>
+#include <initializer_list>
+#include <type_traits>
 
 namespace {
 
-constexpr int TT = 16;   // encoder frames per workgroup in the energy kernels (4 waves x TPW frames)
-constexpr int TPW = TT / 4;
+// Run-time switches that pick a template instantiation: f receives them as std::integral_constant arguments.
+template <typename F> void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+// (Kn, h16) -> (KNMAX, H16) of the energy kernels, forward and backward: the location filters a thread holds in registers
+template <typename F> void with_knmax_h16(int Kn, bool h16, F&& f) {
+    with_bool(h16, [&](auto h) {
+        if (Kn <= 4) f(std::integral_constant<int, 4>{}, h);
+        else if (Kn <= 10) f(std::integral_constant<int, 10>{}, h);
+        else f(std::integral_constant<int, 16>{}, h);
+    });
+}
+
+// Tap ranges the location convolution of a tile (att_energy_kernel) and its transpose (att_bwd_conv_body) are split into, for
+// nout = Kn * tile / 4 outputs per range over 512 threads.  Each range has a partial-sum tile in LDS: kernels and host sizes ask here.
+__host__ __device__ inline int conv_parts(int nout) { const int p = 512 / nout; return p < 1 ? 1 : (p > 8 ? 8 : p); }
 
 // tanh via one v_exp and one v_rcp: 1 - 2/(1+e^{2x}); absolute error ~2e-7 (the energy kernels evaluate ~6 M of these per step)
 __device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
@@ -125,38 +139,6 @@ __global__ __launch_bounds__(256) void dec_query_kernel(DecP p, int t) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// shared tile prologue of the energy kernels: previous attention window + location convolution
-//   s_conv[k*TT + i] = sum_j Wconv[k][j] * prev_att[tau0 + i + j - Ks]
-// prev_att for t == 0 is the uniform initialisation 1/len over valid frames (src/module.py:1157-1160).
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void conv_tile(const DecP& p, int b, int t, int tau0, float* s_pa, float* s_wc, float* s_conv) {
-    const asr_dec_dims_t& d = p.d;
-    const int taps = 2 * d.Ks + 1;
-    const int len = (int)p.enc_len[b];
-    const int win = TT + 2 * d.Ks;
-    const float* prev = (t > 0) ? p.s.att + ((long)b * d.L + (t - 1)) * d.Tp : nullptr;
-    for (int i = threadIdx.x; i < win; i += blockDim.x) {
-        const int tau = tau0 + i - d.Ks;
-        float v = 0.f;
-        if (tau >= 0 && tau < d.Tp) v = prev ? prev[tau] : (tau < len ? 1.f / (float)len : 0.f);
-        s_pa[i] = v;
-    }
-    for (int i = threadIdx.x; i < d.Kn * taps; i += blockDim.x) s_wc[i] = p.w.Wconv[i];
-    __syncthreads();
-    // one (frame, kernel) output per thread
-    for (int o = threadIdx.x; o < d.Kn * TT; o += blockDim.x) {
-        const int i = o % TT, k = o / TT;
-        const float* wk = s_wc + k * taps;
-        float a0 = 0.f, a1 = 0.f;
-        int j = 0;
-        for (; j + 1 < taps; j += 2) { a0 += wk[j] * s_pa[i + j]; a1 += wk[j + 1] * s_pa[i + j + 1]; }
-        if (j < taps) a0 += wk[j] * s_pa[i + j];
-        s_conv[o] = a0 + a1;
-    }
-    __syncthreads();
-}
-
-// ------------------------------------------------------------------------------------------------
 // K2: energies.  grid (ceil(T'/TE), B), TE = 8 waves x TPW frames; wave w owns frames w*TPW.., lanes sweep the
 // attention dimension.  TPW is chosen by the host so that the whole batch is ONE round of workgroups (<= 1 per CU):
 // the kernel is a chain of dependent round trips (window -> conv -> keys -> reduce), not bandwidth, so a second
@@ -164,6 +146,14 @@ __device__ __forceinline__ void conv_tile(const DecP& p, int b, int t, int tau0,
 // convolution is computed; the convolution itself is spread over all 512 threads (tap ranges x 4-frame groups).
 // conv (B,L,Kn,T') is kept for the backward pass when state.conv != NULL.
 // ------------------------------------------------------------------------------------------------
+// Floats of the kernel's dynamic LDS regions, in order: previous attention window [win], location filters [Kn*taps], conv output
+// of the tile [Kn*TE], W_proj transposed [Kn][A], partial conv sums [parts][Kn*TE].  The kernel chains its pointers over them and
+// energy_plan sums them (lds_bytes); the *_regions functions of the backward kernels below serve the same two readers.
+__host__ __device__ inline void energy_regions(int TE, int Kn, int Ks, int A, int n[4]) {      // the partial sums close the carve
+    n[0] = (TE + 2 * Ks + 3) & ~3; n[1] = (Kn * (2 * Ks + 1) + 3) & ~3; n[2] = Kn * TE; n[3] = (Kn * A + 3) & ~3;
+}
+inline size_t lds_bytes(const int* n, int count) { size_t f = 0; for (int i = 0; i < count; ++i) f += n[i]; return sizeof(float) * f; }
+
 template <int KNMAX, int TPW, bool H16>
 __global__ __launch_bounds__(512) void att_energy_kernel(DecP p, int t) {
     constexpr int TE = 8 * TPW, NA = 5;                 // NA: attention columns per lane held in flight
@@ -173,11 +163,9 @@ __global__ __launch_bounds__(512) void att_energy_kernel(DecP p, int t) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int taps = 2 * d.Ks + 1, win = TE + 2 * d.Ks;
     const int len = min((int)p.enc_len[b], d.Tp);
-    float* s_pa = smem_f;                               // [win]            previous attention window
-    float* s_wc = s_pa + ((win + 3) & ~3);              // [Kn*taps]        location filters
-    float* s_conv = s_wc + ((d.Kn * taps + 3) & ~3);    // [Kn*TE]          conv output of the tile
-    float* s_wp = s_conv + d.Kn * TE;                   // [Kn][A]          W_proj transposed
-    float* s_part = s_wp + ((d.Kn * d.A + 3) & ~3);     // [parts][Kn*TE]   partial conv sums
+    int n[4];
+    energy_regions(TE, d.Kn, d.Ks, d.A, n);
+    float *s_pa = smem_f, *s_wc = s_pa + n[0], *s_conv = s_wc + n[1], *s_wp = s_conv + n[2], *s_part = s_wp + n[3];
     // ---- stage 0: every global read that does not depend on the convolution, all in flight together
     const float* prev = (t > 0) ? p.s.att + ((long)b * d.L + (t - 1)) * d.Tp : nullptr;
     const float uni = 1.f / (float)max(len, 1);
@@ -222,7 +210,7 @@ __global__ __launch_bounds__(512) void att_energy_kernel(DecP p, int t) {
     // ---- stage 1: conv[k][i] = sum_j Wconv[k][j] * pa[i + j];  item = (tap range, k, group of 4 frames)
     {
         const int ngrp = TE / 4, nout = d.Kn * ngrp;
-        const int parts = max(1, min(8, 512 / nout));
+        const int parts = conv_parts(nout);
         const int tp = (taps + parts - 1) / parts;
         const float inv_nout = 1.f / (float)nout;
         for (int it = tid; it < parts * nout; it += 512) {
@@ -594,6 +582,16 @@ __global__ __launch_bounds__(256) void dec_cell_bwd_mm_kernel(DecB p, int t, int
 // Threads: NG frame groups x ceil(A/64) waves; wave (g, wa) owns attention dims a = 64*wa + lane for the frames of
 // group g, so the per-a sums have one writer per group and meet in LDS.  TE is chosen by the host so that the batch is
 // one round of workgroups; all global operands are requested before the first barrier.
+// LDS regions: conv of the tile [TE][KP] (KP: the kernel's KNMAX rounded up to 4), de [TE], dattn [TE], dctx [E], W_proj transposed
+// [Kn][AP], dl [TE][AP], the groups' sums [NG][Kn+2][A].  Returns AP / 4.
+__host__ __device__ inline int bwd_energy_regions(int TE, int KP, int NG, int A, int E, int Kn, int n[7]) {
+    int ap4 = (A + 3) >> 2; if ((ap4 & 1) == 0) ++ap4;
+    const int AP = 4 * ap4;                             // row stride of the [frame][a] / [k][a] tiles: 16B rows, odd in float4 units
+    n[0] = TE * KP; n[1] = n[2] = TE; n[3] = (E + 3) & ~3; n[4] = Kn * AP; n[5] = TE * AP; n[6] = NG * (Kn + 2) * A;
+    return ap4;
+}
+constexpr int BWD_ENERGY_KP_HOST = 16;      // bwd_layout's KP, the widest instantiation's: TE and the bytes do not depend on the dispatch
+
 template <int KNMAX, bool H16>
 __global__ __launch_bounds__(640) void att_bwd_energy_kernel(DecB p, int t, int TE, int NG, int last) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -604,16 +602,11 @@ __global__ __launch_bounds__(640) void att_bwd_energy_kernel(DecB p, int t, int 
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6;
     const int nwa = (d.A + 63) >> 6, g = wave / nwa, wa = wave - g * nwa;
     const int FG = TE / NG;                              // frames per group
-    int ap4 = (d.A + 3) >> 2; if ((ap4 & 1) == 0) ++ap4;
-    const int AP = 4 * ap4;                              // row stride of the [frame][a] / [k][a] tiles: 16B rows, odd in float4 units
+    int n[7];
+    const int ap4 = bwd_energy_regions(TE, KP, NG, d.A, d.E, d.Kn, n), AP = 4 * ap4;
     const int XW = d.Dd + d.E;
-    float* s_cv = smem_f;                                // [TE][KP]   conv of the tile
-    float* s_de = s_cv + TE * KP;                        // [TE]
-    float* s_dat = s_de + TE;                            // [TE]
-    float* s_dctx = s_dat + TE;                          // [E]
-    float* s_wpT = s_dctx + ((d.E + 3) & ~3);            // [Kn][AP]
-    float* s_dl = s_wpT + d.Kn * AP;                     // [TE][AP]
-    float* s_acc = s_dl + TE * AP;                       // [NG][Kn+2][A]
+    float *s_cv = smem_f, *s_de = s_cv + n[0], *s_dat = s_de + n[1], *s_dctx = s_dat + n[2], *s_wpT = s_dctx + n[3];
+    float *s_dl = s_wpT + n[4], *s_acc = s_dl + n[5];
     const int len = min((int)p.f.enc_len[b], d.Tp);
     const int tmax = max(len - 1, 0);
     const long row = (long)b * d.L + t;
@@ -807,15 +800,21 @@ __global__ __launch_bounds__(640) void att_bwd_energy_kernel(DecB p, int t, int 
 //   datt_next[tau'] = sum_k sum_j W[k][j] * dconv[k][tau' - j + Ks]      (dconv = this step's rows of state.conv)
 // grid (ceil(T'/TC), B), 512 threads; item = (tap range, k, group of 4 outputs) with a sliding register window.
 // (d W_conv needs no place in the sequential chain: wconv_grad_kernel after the loop.)
+// LDS regions: filters [Kn*taps], dconv window tau0-Ks .. tau0+TC+Ks [Kn][winp], partial sums [parts*Kn][TC].  Returns winp.
+__host__ __device__ inline int bwd_conv_regions(int TC, int Kn, int Ks, int n[3]) {
+    const int winp = TC + 2 * Ks + 4;
+    n[0] = (Kn * (2 * Ks + 1) + 3) & ~3; n[1] = Kn * winp; n[2] = conv_parts(Kn * (TC / 4)) * Kn * TC;
+    return winp;
+}
+
 __device__ __forceinline__ void att_bwd_conv_body(const DecB& p, int t, int TC, int bx, int by) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const asr_dec_dims_t& d = p.f.d;
     const int b = by, tau0 = bx * TC, tid = threadIdx.x;
     const int taps = 2 * d.Ks + 1, win = TC + 2 * d.Ks;
-    float* s_wc = smem_f;                                // [Kn*taps]
-    float* s_dc = s_wc + ((d.Kn * taps + 3) & ~3);       // [Kn][win+4]  dconv window tau0-Ks .. tau0+TC+Ks
-    const int winp = win + 4;
-    float* s_part = s_dc + d.Kn * winp;                  // [parts*Kn][TC]
+    int n[3];
+    const int winp = bwd_conv_regions(TC, d.Kn, d.Ks, n);
+    float *s_wc = smem_f, *s_dc = s_wc + n[0], *s_part = s_dc + n[1];
     const float* dconv = p.f.s.conv + ((long)b * d.L + t) * d.Kn * d.Tp;
     for (int i = tid; i < d.Kn * taps; i += 512) s_wc[i] = p.f.w.Wconv[i];
     for (int i = tid; i < d.Kn * winp; i += 512) {
@@ -824,7 +823,7 @@ __device__ __forceinline__ void att_bwd_conv_body(const DecB& p, int t, int TC, 
     }
     __syncthreads();
     const int ngrp = TC / 4, nout = d.Kn * ngrp;
-    const int parts = max(1, min(8, 512 / nout));
+    const int parts = conv_parts(nout);
     const int tp = (taps + parts - 1) / parts;
     for (int it = tid; it < parts * nout; it += 512) {
         const int pz = it / nout, o = it - pz * nout, k = o / ngrp, ig = o - k * ngrp;
@@ -853,6 +852,13 @@ __device__ __forceinline__ void att_bwd_conv_body(const DecB& p, int t, int TC, 
 // d W_conv[k][j] += sum_{l,b} sum_tau dconv_l[b,k,tau] * prev_att_l[b, tau + j - Ks]   after the loop, all steps at once.
 // grid (NCH, B): workgroup (c, b) walks the steps l = c, c+NCH, ...; thread (k, group of 4 taps) slides over tau.
 // Partial sums per workgroup land in `out` (gridDim.x*gridDim.y, Kn*taps) and are reduced by slot_reduce_kernel.
+// LDS regions: zero-padded previous attention [wpa = Tp + 2Ks + 8], dconv [Kn][Tp].  Returns wpa.
+__host__ __device__ inline int wconv_regions(int Tp, int Kn, int Ks, int n[2]) {
+    const int wpa = Tp + 2 * Ks + 8;
+    n[0] = (wpa + 3) & ~3; n[1] = Kn * Tp;
+    return wpa;
+}
+
 __global__ __launch_bounds__(512) void wconv_grad_kernel(DecP p, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const asr_dec_dims_t& d = p.d;
@@ -860,9 +866,9 @@ __global__ __launch_bounds__(512) void wconv_grad_kernel(DecP p, float* __restri
     const int taps = 2 * d.Ks + 1;
     const int tg = (taps + 3) / 4, nitem = d.Kn * tg;
     const int len = min((int)p.enc_len[b], d.Tp);
-    const int wpa = d.Tp + 2 * d.Ks + 8;
-    float* s_pa = smem_f;                                // [Tp + 2Ks + 8]  zero-padded previous attention
-    float* s_dc = s_pa + ((wpa + 3) & ~3);               // [Kn][Tp]
+    int n[2];
+    const int wpa = wconv_regions(d.Tp, d.Kn, d.Ks, n);
+    float *s_pa = smem_f, *s_dc = s_pa + n[0];
     float acc[4][4];                                     // up to 4 items per thread
 #pragma unroll
     for (int u = 0; u < 4; ++u) { acc[u][0] = acc[u][1] = acc[u][2] = acc[u][3] = 0.f; }
@@ -914,20 +920,35 @@ __global__ __launch_bounds__(512) void wconv_grad_kernel(DecP p, float* __restri
 // dconv rows of a 32-frame chunk (loaded once per chunk), B tile = 32 x 16 window of pa for taps j0..j0+15 (eight LDS words
 // per lane); 16-tap tiles are dealt round-robin to the 4 waves, whose accumulators run over all frames and all steps of
 // the workgroup.  Same grid, slots and reduction as wconv_grad_kernel.
+// LDS regions: zero-padded previous attention s_pa[i] = att[seg + i - Ks] [wpa = SEG + 16*ntile + 16], dconv rows of the segment,
+// zero beyond Kn / len [16][SEG].  Returns wpa.
+__host__ __device__ inline int wconv_mfma_regions(int Tp, int Ks, int n[2], int* ntile, int* SEG) {
+    *ntile = (2 * Ks + 1 + 15) >> 4;                     // 16-tap output tiles
+    // frames are walked in segments of <= 768 (one LDS image of the dconv rows and of the attention window per segment), so any
+    // T' is covered (round 2 took this kernel only up to T' = 768 and fell back to the VALU kernel beyond: 14 ms at config 5)
+    const int TpP = 32 * ((Tp + 31) >> 5);
+    *SEG = TpP < 768 ? TpP : 768;
+    const int wpa = *SEG + 16 * *ntile + 16;
+    n[0] = (wpa + 3) & ~3; n[1] = 16 * *SEG;
+    return wpa;
+}
+// The shapes the kernel takes: bf16 mode, the Kn rows in one 16-row A tile, 16 tap tiles over its 4 waves x MAXT accumulators,
+// and an attention window its four 256-thread staging batches cover.  Returns the launch's dynamic LDS bytes, 0 for any other shape.
+inline size_t wconv_mfma_lds(const asr_dec_dims_t& d, bool bf) {
+    int n[2], ntile, SEG;
+    const int wpa = wconv_mfma_regions(d.Tp, d.Ks, n, &ntile, &SEG);
+    return (bf && d.Kn <= 16 && ntile <= 16 && lds_bytes(n, 2) <= 150 * 1024 && wpa <= 1024) ? lds_bytes(n, 2) : 0;
+}
+
 __global__ __launch_bounds__(256) void wconv_grad_mfma_kernel(DecP p, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const asr_dec_dims_t& d = p.d;
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int taps = 2 * d.Ks + 1;
-    const int ntile = (taps + 15) >> 4;                   // 16-tap output tiles
     const int len = min((int)p.enc_len[b], d.Tp);
-    // frames are walked in segments of <= 768 (one LDS image of the dconv rows and of the attention window per segment), so any
-    // T' is covered (round 2 took this kernel only up to T' = 768 and fell back to the VALU kernel beyond: 14 ms at config 5)
-    const int TpP = 32 * ((d.Tp + 31) >> 5);
-    const int SEG = min(TpP, 768);
-    const int wpa = SEG + 16 * ntile + 16;
-    float* s_pa = smem_f;                                // [SEG + 16*ntile + 16]  zero-padded previous attention: s_pa[i] = att[seg + i - Ks]
-    float* s_dc = s_pa + ((wpa + 3) & ~3);               // [16][SEG]  dconv rows of the segment, zero beyond Kn / len
+    int n[2], ntile, SEG;
+    const int wpa = wconv_mfma_regions(d.Tp, d.Ks, n, &ntile, &SEG);
+    float *s_pa = smem_f, *s_dc = s_pa + n[0];
     constexpr int MAXT = 4;                              // tiles per wave (taps <= 256)
     f32x4 acc[MAXT];
 #pragma unroll
@@ -1153,12 +1174,8 @@ BwdLayout bwd_layout(const asr_dec_dims_t& d) {
     // one round of workgroups and fits the LDS budget
     const int nwa = cdiv(d.A, 64);
     o.NG = nwa <= 2 ? 4 : (nwa <= 5 ? 2 : 1);
-    int ap4 = (d.A + 3) / 4; if ((ap4 & 1) == 0) ++ap4;
-    const int AP = 4 * ap4, KP = 16;
-    auto lds_of = [&](int te) {
-        return sizeof(float) * ((size_t)te * KP + 2 * (size_t)te + ((d.E + 3) & ~3) + (size_t)d.Kn * AP + (size_t)te * AP +
-                                (size_t)o.NG * (d.Kn + 2) * d.A);
-    };
+    int n[7];
+    auto lds_of = [&](int te) { bwd_energy_regions(te, BWD_ENERGY_KP_HOST, o.NG, d.A, d.E, d.Kn, n); return lds_bytes(n, 7); };
     const int te_cand[] = {8, 16, 24, 32, 40, 48, 64};
     o.TE = 8;
     for (int i = 0; i < 7; ++i) {
@@ -1174,15 +1191,13 @@ BwdLayout bwd_layout(const asr_dec_dims_t& d) {
     const int tc_cand[] = {8, 16, 24, 32, 40, 48, 64};
     o.TC = 64;
     for (int i = 0; i < 7; ++i) if ((long)d.B * cdiv(d.Tp, tc_cand[i]) <= 256) { o.TC = tc_cand[i]; break; }
-    {
-        const int nout = d.Kn * (o.TC / 4);
-        const int parts = nout >= 512 ? 1 : (512 / nout > 8 ? 8 : 512 / nout);
-        o.lds_c = sizeof(float) * ((size_t)((d.Kn * taps + 3) & ~3) + (size_t)d.Kn * (o.TC + 2 * d.Ks + 4) + (size_t)parts * d.Kn * o.TC);
-    }
+    bwd_conv_regions(o.TC, d.Kn, d.Ks, n);
+    o.lds_c = lds_bytes(n, 3);
     // W_conv gradient
     o.nch = (int)(256 / d.B > 0 ? 256 / d.B : 1);
     if (o.nch > d.L) o.nch = d.L;
-    o.lds_w = sizeof(float) * ((size_t)((d.Tp + 2 * d.Ks + 8 + 3) & ~3) + (size_t)d.Kn * d.Tp);
+    wconv_regions(d.Tp, d.Kn, d.Ks, n);
+    o.lds_w = lds_bytes(n, 2);
     // the zero-initialised accumulators first and back to back, the persistent launch's status block right behind them: ONE fill
     // from `dhs` to `pwork + 256` at the start of a call (five separate fills before)
     o.dhs = take((size_t)d.B * d.L * d.NL * d.Dd);
@@ -1228,28 +1243,48 @@ EnergyPlan energy_plan(const asr_dec_dims_t& d) {
         if ((long)d.B * cdiv(d.Tp, 8 * cand[i]) <= 256) { tpw = cand[i]; break; }
     EnergyPlan pl;
     pl.tpw = tpw;
-    const int TE = 8 * tpw, taps = 2 * d.Ks + 1, win = TE + 2 * d.Ks;
+    const int TE = 8 * tpw;
     pl.grid = dim3(cdiv(d.Tp, TE), d.B);
-    const int nout = d.Kn * (TE / 4);
-    const int parts = nout >= 512 ? 1 : (512 / nout > 8 ? 8 : 512 / nout);
-    pl.lds = sizeof(float) * ((size_t)((win + 3) & ~3) + ((d.Kn * taps + 3) & ~3) + (size_t)d.Kn * TE + ((d.Kn * d.A + 3) & ~3) +
-                              (size_t)parts * d.Kn * TE);
+    int n[5];
+    energy_regions(TE, d.Kn, d.Ks, d.A, n);
+    n[4] = conv_parts(d.Kn * (TE / 4)) * d.Kn * TE;     // (a division the kernel does not need before its stage 1)
+    pl.lds = lds_bytes(n, 5);
     return pl;
 }
-template <int KNMAX, bool H16>
-void launch_energy_k(const DecP& p, int t, const EnergyPlan& pl, hipStream_t st) {
-    switch (pl.tpw) {
-        case 2: hipLaunchKernelGGL((att_energy_kernel<KNMAX, 2, H16>), pl.grid, dim3(512), pl.lds, st, p, t); break;
-        case 4: hipLaunchKernelGGL((att_energy_kernel<KNMAX, 4, H16>), pl.grid, dim3(512), pl.lds, st, p, t); break;
-        case 5: if constexpr (KNMAX <= 10) { hipLaunchKernelGGL((att_energy_kernel<KNMAX, 5, H16>), pl.grid, dim3(512), pl.lds, st, p, t); } break;
-        default: if constexpr (KNMAX <= 4) { hipLaunchKernelGGL((att_energy_kernel<KNMAX, 8, H16>), pl.grid, dim3(512), pl.lds, st, p, t); } break;
-    }
-}
 void launch_energy(const DecP& p, int t, const EnergyPlan& pl, hipStream_t st) {
-    const bool h16 = p.s.key16 != nullptr;
-    if (p.d.Kn <= 4) { if (h16) launch_energy_k<4, true>(p, t, pl, st); else launch_energy_k<4, false>(p, t, pl, st); }
-    else if (p.d.Kn <= 10) { if (h16) launch_energy_k<10, true>(p, t, pl, st); else launch_energy_k<10, false>(p, t, pl, st); }
-    else { if (h16) launch_energy_k<16, true>(p, t, pl, st); else launch_energy_k<16, false>(p, t, pl, st); }
+    // the if constexpr guards keep (KNMAX, TPW) pairs beyond the register budget from being instantiated (energy_plan never picks them)
+    with_knmax_h16(p.d.Kn, p.s.key16 != nullptr, [&](auto kn, auto h) {
+        constexpr int KNMAX = decltype(kn)::value;
+        constexpr bool H16 = decltype(h)::value;
+        switch (pl.tpw) {
+            case 2: hipLaunchKernelGGL((att_energy_kernel<KNMAX, 2, H16>), pl.grid, dim3(512), pl.lds, st, p, t); break;
+            case 4: hipLaunchKernelGGL((att_energy_kernel<KNMAX, 4, H16>), pl.grid, dim3(512), pl.lds, st, p, t); break;
+            case 5: if constexpr (KNMAX <= 10) { hipLaunchKernelGGL((att_energy_kernel<KNMAX, 5, H16>), pl.grid, dim3(512), pl.lds, st, p, t); } break;
+            default: if constexpr (KNMAX <= 4) { hipLaunchKernelGGL((att_energy_kernel<KNMAX, 8, H16>), pl.grid, dim3(512), pl.lds, st, p, t); } break;
+        }
+    });
+}
+
+// One decoder step on the per-step kernels: the token's embedding row (unless the whole table was embedded), query, energies, softmax +
+// context, one cell per layer.  Context and energy pick their half copies apart (enc16 / key16): a caller may pass one without the other.
+void launch_step(const DecP& p, int t, bool bf, const EnergyPlan& epl, bool embed, hipStream_t st) {
+    const asr_dec_dims_t& d = p.d;
+    if (embed)
+        hipLaunchKernelGGL(embed_kernel, dim3(cdiv((long)d.B * d.Dd, 256)), dim3(256), 0, st, p.w.emb, p.s.tokens, p.s.xin, d.B, d.L, d.Dd,
+                           d.Dd + d.E, t, 1, d.V);
+    with_bool(bf, [&](auto b) { hipLaunchKernelGGL(dec_query_kernel<decltype(b)::value>, dim3(cdiv(d.A, 16)), dim3(256), 0, st, p, t); });
+    launch_energy(p, t, epl, st);
+    if (p.s.enc16 && (d.E & 3) == 0) hipLaunchKernelGGL(att_softmax_ctx_kernel<true>, dim3(cdiv(d.E, 64), d.B), dim3(256), sizeof(float) * d.Tp, st, p, t);
+    else hipLaunchKernelGGL(att_softmax_ctx_kernel<false>, dim3(cdiv(d.E, 64), d.B), dim3(256), sizeof(float) * d.Tp, st, p, t);
+    for (int l = 0; l < d.NL; ++l)
+        with_bool(bf, [&](auto b) { hipLaunchKernelGGL(dec_cell_fwd_kernel<decltype(b)::value>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l); });
+}
+
+// key = tanh(enc W_k^T + b_k), once per batch (src/asr.py:345)
+GemmCall key_call(const asr_dec_dims_t& d, const asr_dec_weights_t& w, const float* enc, float* key, int prec) {
+    GemmCall c{enc, w.Wk, key, w.bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A};
+    c.act = ASR_ACT_TANH; c.prec = prec;
+    return c;
 }
 
 }  // namespace
@@ -1264,7 +1299,7 @@ extern "C" int asr_att_decoder_energy_plan(const asr_dec_dims_t* dims, int* knma
     ASR_REQUIRE(dims && knmax && tpw, ASR_E_ARG, "asr_att_decoder_energy_plan: null pointer");
     const int rc = check_dims(*dims, "asr_att_decoder_energy_plan");
     if (rc != ASR_OK) return rc;
-    *knmax = dims->Kn <= 4 ? 4 : (dims->Kn <= 10 ? 10 : 16);
+    with_knmax_h16(dims->Kn, false, [&](auto kn, auto) { *knmax = decltype(kn)::value; });      // the dispatch's own thresholds
     *tpw = energy_plan(*dims).tpw;
     return ASR_OK;
 }
@@ -1284,7 +1319,6 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
     if (rc != ASR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     DecP p{d, *weights, *state, enc, enc_len};
-    const int XW = d.Dd + d.E;
     const bool bf = (prec == ASR_BF16);
     // the abort word (first word of `work`) is defined after EVERY call, whichever kernels run: callers fold it into
     // their status word without knowing whether the persistent launch was taken
@@ -1292,10 +1326,7 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
     if (state->work && state->work_bytes >= 256)
         hipLaunchKernelGGL(dec_fwd_begin_kernel, dim3(1), dim3(64), 0, st, (unsigned*)state->work, state->work_bytes >= DEC_STATUS_BYTES ? 1 : 0);
 
-    // key = tanh(enc W_k^T + b_k), once per batch (src/asr.py:345)
-    GemmCall key{enc, weights->Wk, state->key, weights->bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A};
-    key.act = ASR_ACT_TANH; key.prec = prec;
-    rc = gemm_run(key, st);
+    rc = gemm_run(key_call(d, *weights, enc, state->key, prec), st);
     if (rc != ASR_OK) return rc;
     // bf16 working copies of the two tensors every step re-reads (bf16 contraction mode only; the caller provides the
     // buffers): they halve the loop's HBM traffic and bring its per-XCD working set under the 4 MB L2
@@ -1305,7 +1336,7 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
     if (teacher) {
         hipLaunchKernelGGL(shift_tokens_kernel, dim3(cdiv(d.B * d.L, 256)), dim3(256), 0, st, teacher, state->tokens, d.B, d.L, teacher_ld);
         hipLaunchKernelGGL(embed_kernel, dim3(cdiv((long)d.B * d.L * d.Dd, 256)), dim3(256), 0, st, weights->emb, state->tokens,
-                           state->xin, d.B, d.L, d.Dd, XW, 0, d.L, d.V);
+                           state->xin, d.B, d.L, d.Dd, d.Dd + d.E, 0, d.L, d.V);
     } else {
         hipMemsetAsync(state->tokens, 0, sizeof(int64_t) * d.B * d.L, st);
     }
@@ -1320,18 +1351,7 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
         if (rc == ASR_OK) t_begin = d.L;
     }
     for (int t = t_begin; t < d.L; ++t) {
-        if (!teacher)
-            hipLaunchKernelGGL(embed_kernel, dim3(cdiv((long)d.B * d.Dd, 256)), dim3(256), 0, st, weights->emb, state->tokens,
-                               state->xin, d.B, d.L, d.Dd, XW, t, 1, d.V);
-        if (bf) hipLaunchKernelGGL(dec_query_kernel<true>, dim3(cdiv(d.A, 16)), dim3(256), 0, st, p, t);
-        else    hipLaunchKernelGGL(dec_query_kernel<false>, dim3(cdiv(d.A, 16)), dim3(256), 0, st, p, t);
-        launch_energy(p, t, epl, st);
-        if (state->enc16 && (d.E & 3) == 0) hipLaunchKernelGGL(att_softmax_ctx_kernel<true>, dim3(cdiv(d.E, 64), d.B), dim3(256), sizeof(float) * d.Tp, st, p, t);
-        else hipLaunchKernelGGL(att_softmax_ctx_kernel<false>, dim3(cdiv(d.E, 64), d.B), dim3(256), sizeof(float) * d.Tp, st, p, t);
-        for (int l = 0; l < d.NL; ++l) {
-            if (bf) hipLaunchKernelGGL(dec_cell_fwd_kernel<true>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
-            else    hipLaunchKernelGGL(dec_cell_fwd_kernel<false>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
-        }
+        launch_step(p, t, bf, epl, !teacher, st);      // the teacher's tokens were embedded above, all steps at once
         if (!teacher) hipLaunchKernelGGL(dec_greedy_kernel, dim3(d.B), dim3(256), 0, st, p, t);
     }
     ASR_LAUNCH_CHECK("asr_att_decoder_fwd");
@@ -1353,10 +1373,7 @@ extern "C" int asr_att_decoder_fwd(const asr_dec_dims_t* dims, const asr_dec_wei
 extern "C" int asr_att_decoder_keys(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const float* enc,
                                     float* key, int prec, asr_stream_t stream) {
     ASR_REQUIRE(dims && weights && enc && key, ASR_E_ARG, "asr_att_decoder_keys: null pointer");
-    const asr_dec_dims_t& d = *dims;
-    GemmCall c{enc, weights->Wk, key, weights->bk, d.B * d.Tp, d.A, d.E, d.E, d.E, d.A};
-    c.act = ASR_ACT_TANH; c.prec = prec;
-    return gemm_run(c, (hipStream_t)stream);
+    return gemm_run(key_call(*dims, *weights, enc, key, prec), (hipStream_t)stream);
 }
 
 extern "C" int asr_att_decoder_step(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights,
@@ -1369,21 +1386,9 @@ extern "C" int asr_att_decoder_step(const asr_dec_dims_t* dims, const asr_dec_we
     ASR_REQUIRE(t >= 0 && t < d.L, ASR_E_ARG, "asr_att_decoder_step: step %d outside [0,%d)", t, d.L);
     hipStream_t st = (hipStream_t)stream;
     DecP p{d, *weights, *state, enc, enc_len};
-    const int XW = d.Dd + d.E;
-    const bool bf = (prec == ASR_BF16);
     const EnergyPlan epl = energy_plan(d);
     ASR_REQUIRE(epl.lds <= 64 * 1024, ASR_E_UNSUPPORTED, "asr_att_decoder_step: energy tile needs %zu B of LDS", epl.lds);
-    hipLaunchKernelGGL(embed_kernel, dim3(cdiv((long)d.B * d.Dd, 256)), dim3(256), 0, st, weights->emb, state->tokens, state->xin,
-                       d.B, d.L, d.Dd, XW, t, 1, d.V);
-    if (bf) hipLaunchKernelGGL(dec_query_kernel<true>, dim3(cdiv(d.A, 16)), dim3(256), 0, st, p, t);
-    else    hipLaunchKernelGGL(dec_query_kernel<false>, dim3(cdiv(d.A, 16)), dim3(256), 0, st, p, t);
-    launch_energy(p, t, epl, st);
-    if (state->enc16 && (d.E & 3) == 0) hipLaunchKernelGGL(att_softmax_ctx_kernel<true>, dim3(cdiv(d.E, 64), d.B), dim3(256), sizeof(float) * d.Tp, st, p, t);
-    else hipLaunchKernelGGL(att_softmax_ctx_kernel<false>, dim3(cdiv(d.E, 64), d.B), dim3(256), sizeof(float) * d.Tp, st, p, t);
-    for (int l = 0; l < d.NL; ++l) {
-        if (bf) hipLaunchKernelGGL(dec_cell_fwd_kernel<true>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
-        else    hipLaunchKernelGGL(dec_cell_fwd_kernel<false>, dim3(cdiv(d.Dd, 4)), dim3(256), 0, st, p, t, l);
-    }
+    launch_step(p, t, prec == ASR_BF16, epl, true, st);
     ASR_LAUNCH_CHECK("asr_att_decoder_step");
     if (d.V > DEC_LOGITS_ROW_MAX_V) {
         // word and subword vocabularies: logits[:, t] = hs_top[:, t] Wc^T + bc as ONE contraction over all rows, which reads Wc
@@ -1426,9 +1431,28 @@ static int wgrad_slices(int out_rows, int out_cols, int depth) {
     return s < 1 ? 1 : (s > 64 ? 64 : s);
 }
 
-extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
-                                          const float* enc, const int64_t* enc_len, const asr_dec_state_t* state, const float* dlogits,
-                                          void* workspace, size_t workspace_bytes, int looped, int prec, asr_stream_t stream);
+// What both halves of the backward start with: argument checks under the name of the entry point called, the workspace
+// layout, and the kernels' argument block over that workspace (every pointer, whichever half reads it).
+static int bwd_begin(const char* who, const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
+                     const float* enc, const int64_t* enc_len, const asr_dec_state_t* state, const float* dlogits,
+                     void* workspace, size_t workspace_bytes, BwdLayout* lay, DecB* p) {
+    ASR_REQUIRE(dims && weights && grads && enc && enc_len && state && dlogits && workspace, ASR_E_ARG, "%s: null pointer", who);
+    const asr_dec_dims_t& d = *dims;
+    const int rc = check_dims(d, who);
+    if (rc != ASR_OK) return rc;
+    *lay = bwd_layout(d);
+    ASR_REQUIRE(workspace_bytes >= lay->total, ASR_E_ARG, "%s: workspace %zu < %zu", who, workspace_bytes, lay->total);
+    auto at = [&](size_t off) { return (float*)((char*)workspace + off); };
+    p->f = DecP{d, *weights, *state, enc, enc_len};
+    p->g = *grads;
+    p->dhs = at(lay->dhs); p->dxin = at(lay->dxin); p->dq = at(lay->dq);
+    p->dkey = at(lay->dkey); p->datt_next = at(lay->datt_next);
+    p->dcf = at(lay->dcf); p->wqT = at(lay->wq_t);
+    p->slots = at(lay->slots); p->nte = lay->nte; p->slot = lay->slot;
+    for (int l = 0; l < ASR_MAX_DEC_LAYERS; ++l) p->wcatT[l] = (l < d.NL) ? at(lay->wcat[l]) : nullptr;
+    return ASR_OK;
+}
+
 // dst[r * dst_ld + c] += src[r * width + c]: an outside gradient on the top layer's h_t joins dh_top (asr_att_decoder_bwd_hs)
 static __global__ __launch_bounds__(256) void add_rows_kernel(float* dst, long dst_ld, const float* src, long rows, int width) {
     const long n = rows * width;
@@ -1511,31 +1535,20 @@ extern "C" int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_
                                       const float* dlogits, const float* dhs_ext, float* denc,
                                       void* workspace, size_t workspace_bytes, int prec, int defer_params, int* looped_out,
                                       asr_stream_t stream) {
-    ASR_REQUIRE(dims && weights && grads && enc && enc_len && state && dlogits && denc && workspace, ASR_E_ARG,
-                "asr_att_decoder_bwd: null pointer");
-    const asr_dec_dims_t& d = *dims;
-    int rc = check_dims(d, "asr_att_decoder_bwd");
+    ASR_REQUIRE(denc, ASR_E_ARG, "asr_att_decoder_bwd: null pointer");
+    BwdLayout lay;
+    DecB p;
+    int rc = bwd_begin("asr_att_decoder_bwd", dims, weights, grads, enc, enc_len, state, dlogits, workspace, workspace_bytes, &lay, &p);
     if (rc != ASR_OK) return rc;
-    const BwdLayout lay = bwd_layout(d);
-    ASR_REQUIRE(workspace_bytes >= lay.total, ASR_E_ARG, "asr_att_decoder_bwd: workspace %zu < %zu", workspace_bytes, lay.total);
     ASR_REQUIRE(((uintptr_t)workspace & 255) == 0, ASR_E_ARG, "asr_att_decoder_bwd: workspace must be 256B aligned");
+    const asr_dec_dims_t& d = *dims;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int XW = d.Dd + d.E;
     const bool bf = (prec == ASR_BF16);
     const long SW = (long)d.NL * d.Dd;
     const int BL = d.B * d.L;
-
-    DecB p;
-    p.f = DecP{d, *weights, *state, enc, enc_len};
-    p.g = *grads;
-    p.dhs = (float*)(ws + lay.dhs); p.dxin = (float*)(ws + lay.dxin); p.dq = (float*)(ws + lay.dq);
-    p.dkey = (float*)(ws + lay.dkey); p.datt_next = (float*)(ws + lay.datt_next);
-    p.dcf = (float*)(ws + lay.dcf); p.wqT = (float*)(ws + lay.wq_t);
-    p.slots = (float*)(ws + lay.slots); p.nte = lay.nte; p.slot = lay.slot;
-    float* wslots = (float*)(ws + lay.wslots);
     float* dkeypre = (float*)(ws + lay.dkeypre);
-    for (int l = 0; l < ASR_MAX_DEC_LAYERS; ++l) p.wcatT[l] = (l < d.NL) ? (float*)(ws + lay.wcat[l]) : nullptr;
 
     // zero-initialised accumulators dhs, dq, dkey, slots (dxin is fully written by the loop) and the abort word of the persistent
     // launch's status block (defined, 0, after every call - see asr_att_decoder_fwd): contiguous in the layout, one fill
@@ -1571,12 +1584,12 @@ extern "C" int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_
                 "asr_att_decoder_bwd: shape needs %zu / %zu / %zu B of LDS", lay.lds_e, lay.lds_c, lay.lds_w);
     static bool attr_set = false;
     if (!attr_set) {
-        hipFuncSetAttribute((const void*)att_bwd_energy_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        hipFuncSetAttribute((const void*)att_bwd_energy_kernel<10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        hipFuncSetAttribute((const void*)att_bwd_energy_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        hipFuncSetAttribute((const void*)att_bwd_energy_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        hipFuncSetAttribute((const void*)att_bwd_energy_kernel<10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        hipFuncSetAttribute((const void*)att_bwd_energy_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
+        for (int kn : {4, 10, 16})                      // one Kn per arm of with_knmax_h16: all six instantiations
+            for (bool h : {false, true})
+                with_knmax_h16(kn, h, [](auto k, auto hh) {
+                    hipFuncSetAttribute((const void*)att_bwd_energy_kernel<decltype(k)::value, decltype(hh)::value>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
+                });
         // (4 KB of static LDS of the query part count against the 160 KB)
         hipFuncSetAttribute((const void*)att_bwd_tail_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192);
         hipFuncSetAttribute((const void*)att_bwd_tail_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192);
@@ -1608,18 +1621,11 @@ extern "C" int asr_att_decoder_bwd_hs(const asr_dec_dims_t* dims, const asr_dec_
             if (!fuse || last)
                 hipLaunchKernelGGL(dec_cell_bwd_elem_kernel, dim3(cdiv(d.B * d.Dd, 256)), dim3(256), 0, st, p, t, l, last);
             const int width = ((l == 0) ? XW : d.Dd) + d.Dd;
-            if (bf) hipLaunchKernelGGL(dec_cell_bwd_mm_kernel<true>, dim3(cdiv(width, 16)), dim3(256), 0, st, p, t, l);
-            else    hipLaunchKernelGGL(dec_cell_bwd_mm_kernel<false>, dim3(cdiv(width, 16)), dim3(256), 0, st, p, t, l);
+            with_bool(bf, [&](auto b) { hipLaunchKernelGGL(dec_cell_bwd_mm_kernel<decltype(b)::value>, dim3(cdiv(width, 16)), dim3(256), 0, st, p, t, l); });
         }
-        if (h16) {
-            if (d.Kn <= 4)       hipLaunchKernelGGL((att_bwd_energy_kernel<4, true>), grid_e, block_e, lay.lds_e, st, p, t, lay.TE, lay.NG, last);
-            else if (d.Kn <= 10) hipLaunchKernelGGL((att_bwd_energy_kernel<10, true>), grid_e, block_e, lay.lds_e, st, p, t, lay.TE, lay.NG, last);
-            else                 hipLaunchKernelGGL((att_bwd_energy_kernel<16, true>), grid_e, block_e, lay.lds_e, st, p, t, lay.TE, lay.NG, last);
-        } else {
-            if (d.Kn <= 4)       hipLaunchKernelGGL((att_bwd_energy_kernel<4, false>), grid_e, block_e, lay.lds_e, st, p, t, lay.TE, lay.NG, last);
-            else if (d.Kn <= 10) hipLaunchKernelGGL((att_bwd_energy_kernel<10, false>), grid_e, block_e, lay.lds_e, st, p, t, lay.TE, lay.NG, last);
-            else                 hipLaunchKernelGGL((att_bwd_energy_kernel<16, false>), grid_e, block_e, lay.lds_e, st, p, t, lay.TE, lay.NG, last);
-        }
+        with_knmax_h16(d.Kn, h16, [&](auto kn, auto h) {
+            hipLaunchKernelGGL((att_bwd_energy_kernel<decltype(kn)::value, decltype(h)::value>), grid_e, block_e, lay.lds_e, st, p, t, lay.TE, lay.NG, last);
+        });
         if (t > 0) {
             // the location path reaches attn_{t-1}; step 0 convolves the constant initial attention
             const int nconv = (int)(grid_c.x * grid_c.y), nq = cdiv(d.Q, 16);
@@ -1661,12 +1667,11 @@ extern "C" int asr_att_decoder_bwd(const asr_dec_dims_t* dims, const asr_dec_wei
 extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_dec_weights_t* weights, const asr_dec_grads_t* grads,
                                           const float* enc, const int64_t* enc_len, const asr_dec_state_t* state, const float* dlogits,
                                           void* workspace, size_t workspace_bytes, int looped, int prec, asr_stream_t stream) {
-    ASR_REQUIRE(dims && weights && grads && enc && enc_len && state && dlogits && workspace, ASR_E_ARG, "asr_att_decoder_bwd_params: null pointer");
-    const asr_dec_dims_t& d = *dims;
-    int rc = check_dims(d, "asr_att_decoder_bwd_params");
+    BwdLayout lay;
+    DecB p;
+    int rc = bwd_begin("asr_att_decoder_bwd_params", dims, weights, grads, enc, enc_len, state, dlogits, workspace, workspace_bytes, &lay, &p);
     if (rc != ASR_OK) return rc;
-    const BwdLayout lay = bwd_layout(d);
-    ASR_REQUIRE(workspace_bytes >= lay.total, ASR_E_ARG, "asr_att_decoder_bwd_params: workspace %zu < %zu", workspace_bytes, lay.total);
+    const asr_dec_dims_t& d = *dims;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int XW = d.Dd + d.E;
@@ -1674,11 +1679,6 @@ extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_
     const long SW = (long)d.NL * d.Dd;
     const int BL = d.B * d.L;
     const int taps = 2 * d.Ks + 1;
-    DecB p;
-    p.f = DecP{d, *weights, *state, enc, enc_len};
-    p.g = *grads;
-    p.dxin = (float*)(ws + lay.dxin); p.dq = (float*)(ws + lay.dq);
-    p.slots = (float*)(ws + lay.slots); p.nte = lay.nte; p.slot = lay.slot;
     float* wslots = (float*)(ws + lay.wslots);
     float* dkeypre = (float*)(ws + lay.dkeypre);
     const float* pdg = looped ? dec_bwd_dgates(d, ws + lay.pwork) : nullptr;
@@ -1741,9 +1741,7 @@ extern "C" int asr_att_decoder_bwd_params(const asr_dec_dims_t* dims, const asr_
     hipLaunchKernelGGL(slot_reduce_kernel, dim3(cdiv(d.A * d.Kn, 4)), dim3(256), 0, st, p.slots, nslots, lay.slot, grads->Wproj, d.A, d.A * d.Kn, d.A, d.Kn);
     hipLaunchKernelGGL(slot_reduce_kernel, dim3(1), dim3(256), 0, st, p.slots, nslots, lay.slot, grads->bg, d.A * (1 + d.Kn), 1, 0, 0);
     {
-        const int ntile = (taps + 15) / 16, SEG = std::min(32 * cdiv(d.Tp, 32), 768);
-        const size_t lds_m = sizeof(float) * ((size_t)((SEG + 16 * ntile + 16 + 3) & ~3) + (size_t)16 * SEG);
-        if (bf && d.Kn <= 16 && ntile <= 16 && lds_m <= 150 * 1024 && SEG + 16 * ntile + 16 <= 1024) {
+        if (const size_t lds_m = wconv_mfma_lds(d, bf)) {
             static bool attr_m = false;
             if (!attr_m) { hipFuncSetAttribute((const void*)wconv_grad_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); attr_m = true; }
             hipLaunchKernelGGL(wconv_grad_mfma_kernel, dim3(lay.nch, d.B), dim3(256), lds_m, st, p.f, wslots);

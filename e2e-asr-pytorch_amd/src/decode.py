@@ -44,7 +44,7 @@ def encode_unpadded(asr, audio_feature, feature_len, with_ctc):
     inside the padding) - written into zero-padded (U,T'max,.) tensors for a batched search or alignment.  Returns
     (enc, enc_len int64 (U), tlen int32 (U), ctc log-probs or None)."""
     dev = audio_feature.device
-    ctx = type('C', (), {'anchor': asr._anchor, 'prec': asr.prec, 'next_seed': lambda s: 0})()
+    ctx = ragged.eval_ctx(asr)
     U = audio_feature.shape[0]
     encs, lens, ctcs = [], [], []
     for u in range(U):
@@ -460,7 +460,7 @@ class BeamDecoder(nn.Module):
         L = max(1, int(max_len.item()))
         rows = self._rescore_chunk_rows(L, Tp)
         fast = asr.decoder.fast and asr.attention.fast and asr.emb_drop == 0.0        # the choice of ASR.forward
-        ctx = type('C', (), {'anchor': asr._anchor, 'prec': asr.prec, 'next_seed': lambda s: 0})()
+        ctx = ragged.eval_ctx(asr)
         enc2d = enc.reshape(U, Tp * E)
         logits = None if rows >= R else torch.empty((R, L, V), dtype=torch.float32, device=dev)
         was_training = asr.training
@@ -577,19 +577,15 @@ class BeamDecoder(nn.Module):
         flen = int(feature_len.reshape(-1)[0])
         max_len = int(math.ceil(flen * self.max_len_ratio))
         min_len = int(math.ceil(flen * self.min_len_ratio))
-        ctx = type('C', (), {'anchor': asr._anchor, 'prec': prec, 'next_seed': lambda s: 0})()
+        ctx = ragged.eval_ctx(asr)
         enc, enc_len = asr.encoder(audio_feature.float(), feature_len.to(dev), ctx)
         enc = F_hip.to_f32(enc)
         Tp = enc.shape[1]
         nmax = self.beam_size
         L = max(max_len, 1)
-        d = F_hip._dec_dims(asr, nmax, Tp, L)
-        sd = F_hip._dec_state(d, dev, save_conv=False)
-        w = H.dec_weights_struct(F_hip._dec_tensors(asr, False), d.NL)
-        s = H.dec_state_struct(sd)
-        enc_rep = enc.expand(nmax, Tp, enc.shape[2]).contiguous()
-        len_rep = enc_len.to(dev, torch.int64).expand(nmax).contiguous()
-        H.call('asr_att_decoder_keys', ctypes.byref(d), ctypes.byref(w), H.ptr(enc_rep), H.ptr(sd['key']), prec, st)
+        dec = F_hip.DecoderStepper(asr, enc.expand(nmax, Tp, enc.shape[2]).contiguous(),
+                                   enc_len.to(dev, torch.int64).expand(nmax).contiguous(), L, prec)
+        sd = dec.sd
         ctc_r = None
         if self.apply_ctc:
             ctc_lp = F_hip.CTCHeadFn.apply(asr._anchor, enc, asr.ctc_layer[0], prec, False, False)
@@ -605,8 +601,7 @@ class BeamDecoder(nn.Module):
             n = len(hyps)
             toks = torch.tensor([h.output_seq[-1] if h.output_seq else 0 for h in hyps], dtype=torch.int64)
             sd['tokens'][:n, t] = toks.to(dev)
-            d.B = n
-            H.call('asr_att_decoder_step', ctypes.byref(d), ctypes.byref(w), H.ptr(enc_rep), H.ptr(len_rep), ctypes.byref(s), t, prec, st)
+            dec.step(t, live_rows=n)
             logits = sd['logits'][:n, t].contiguous()
             att_lp = torch.empty_like(logits)
             if self.apply_emb:
@@ -658,28 +653,19 @@ class BeamDecoder(nn.Module):
         return finals[:self.beam_size]
 
 
-class _FastStep(object):
-    """Decoder state and step of the shipped decoder on the decode kernels (asr_att_decoder_keys / _step)."""
+class _FastStep(F_hip.DecoderStepper):
+    """Decoder state and step of the shipped decoder on the decode kernels: every utterance's rows of enc `beam` times over."""
 
     def __init__(self, asr, enc, enc_len, beam, Lmax):
         U, Tp, E = enc.shape
-        R = U * beam
-        self.asr, self.R = asr, R
-        self.d = F_hip._dec_dims(asr, R, Tp, Lmax + 1)
-        self.sd = F_hip._dec_state(self.d, enc.device, save_conv=False)
-        self.sd['tokens'].zero_()
+        self.R = R = U * beam
+        super().__init__(asr, enc.unsqueeze(1).expand(U, beam, Tp, E).reshape(R, Tp, E).contiguous(),
+                         enc_len.unsqueeze(1).expand(U, beam).reshape(R).contiguous(), Lmax + 1, asr.prec)
         self.tokens = self.sd['tokens']
-        self.w = H.dec_weights_struct(F_hip._dec_tensors(asr, False), self.d.NL)
-        self.s = H.dec_state_struct(self.sd)
-        self.enc_rep = enc.unsqueeze(1).expand(U, beam, Tp, E).reshape(R, Tp, E).contiguous()
-        self.len_rep = enc_len.unsqueeze(1).expand(U, beam).reshape(R).contiguous()
-        H.call('asr_att_decoder_keys', ctypes.byref(self.d), ctypes.byref(self.w), H.ptr(self.enc_rep), H.ptr(self.sd['key']), asr.prec,
-               H.stream_ptr())
         self.tmp = {k: torch.empty_like(self.sd[k][:, 0]) for k in ('hs', 'cs', 'att')}
 
     def step(self, t):
-        H.call('asr_att_decoder_step', ctypes.byref(self.d), ctypes.byref(self.w), H.ptr(self.enc_rep), H.ptr(self.len_rep),
-               ctypes.byref(self.s), t, self.asr.prec, H.stream_ptr())
+        super().step(t)
         return self.sd['logits'][:, t].contiguous()
 
     def top_state(self, t):

@@ -674,24 +674,37 @@ def _dec_state(d, dev, save_conv=True, half_copies=False):
     }
 
 
+class DecoderStepper(object):
+    """The per-step C-ABI calls over dims `d` and state dict `sd` (tokens zeroed); the key projection runs on construction.
+    The caller writes sd['tokens'][:, t] and, for t > 0, the step t-1 rows of hs / cs / att, then calls step(t)."""
+
+    def __init__(self, model, enc, enc_len, L, prec, save_conv=False):
+        self.enc, self.enc_len, self.prec = enc, enc_len, prec
+        self.d = _dec_dims(model, enc.shape[0], enc.shape[1], L)
+        self.sd = _dec_state(self.d, enc.device, save_conv=save_conv, half_copies=False)
+        self.sd['tokens'].zero_()
+        self.w = H.dec_weights_struct(_dec_tensors(model, False), self.d.NL)
+        self.s = H.dec_state_struct(self.sd)
+        H.call('asr_att_decoder_keys', ctypes.byref(self.d), ctypes.byref(self.w), H.ptr(enc), H.ptr(self.sd['key']), prec, H.stream_ptr())
+
+    def step(self, t, live_rows=None):
+        self.d.B = self.enc.shape[0] if live_rows is None else live_rows
+        H.call('asr_att_decoder_step', ctypes.byref(self.d), ctypes.byref(self.w), H.ptr(self.enc), H.ptr(self.enc_len),
+               ctypes.byref(self.s), t, self.prec, H.stream_ptr())
+
+
 def att_decoder_forward_sampled(model, enc, enc_len, L, teacher, prec, tf_rate, decisions=None):
     """Scheduled sampling (reference src/asr.py:145-158): after every step ONE uniform draw decides for the whole batch
     whether the next input token is the teacher's (probability tf_rate) or a sample from softmax(logits) of this step.
     The loop runs through the per-step C-ABI call; the token table records what was fed, so the backward pass (tokens
     are data) is the ordinary one.  decisions: optional list of booleans (True = teacher) replacing the host draws (tests)."""
-    B, Tp, _ = enc.shape
-    d = _dec_dims(model, B, Tp, L)
-    st = _dec_state(d, enc.device, save_conv=True, half_copies=False)
-    st['tokens'].zero_()
-    w = H.dec_weights_struct(_dec_tensors(model, False), d.NL)
-    s = H.dec_state_struct(st)
-    sp = H.stream_ptr()
+    dec = DecoderStepper(model, enc, enc_len, L, prec, save_conv=True)
+    d, st = dec.d, dec.sd
     teacher = teacher.contiguous()
-    H.call('asr_att_decoder_keys', ctypes.byref(d), ctypes.byref(w), H.ptr(enc), H.ptr(st['key']), prec, sp)
     model._ss_counter = getattr(model, '_ss_counter', 0)
     st['tf_decisions'] = []
     for t in range(L):
-        H.call('asr_att_decoder_step', ctypes.byref(d), ctypes.byref(w), H.ptr(enc), H.ptr(enc_len), ctypes.byref(s), t, prec, sp)
+        dec.step(t)
         if t + 1 < L:
             use_teacher = bool(decisions[t]) if decisions is not None else (tf_rate == 1 or torch.rand(1).item() <= tf_rate)
             st['tf_decisions'].append(use_teacher)
@@ -701,7 +714,7 @@ def att_decoder_forward_sampled(model, enc, enc_len, L, teacher, prec, tf_rate, 
                 model._ss_counter += 1
                 seed = (model.seed * 7919 + model._ss_counter) & 0xFFFFFFFFFFFF
                 H.call('asr_sample_tokens', H.ptr(st['logits'][:, t]), st['logits'].stride(0), H.ptr(st['tokens'][:, t + 1]),
-                       st['tokens'].stride(0), B, d.V, seed, sp)
+                       st['tokens'].stride(0), d.B, d.V, seed, H.stream_ptr())
     return d, st
 
 
@@ -710,18 +723,12 @@ def att_decoder_forward_fused(model, enc, enc_len, L, prec, emb_decoder):
     """Greedy decoding through an embedding-fusing plugin (reference src/asr.py:167-172 with emb_decoder): every step runs the
     per-step C-ABI call, the plugin fuses the step's logits with its embedding distribution (asr_emb_fuse_fwd) and the kernel's
     argmax of the fused row is the next step's token.  Returns (dims, state, fused log-probs (B,L,V))."""
-    B, Tp, _ = enc.shape
-    d = _dec_dims(model, B, Tp, L)
-    st = _dec_state(d, enc.device, save_conv=False, half_copies=False)
-    st['tokens'].zero_()
-    w = H.dec_weights_struct(_dec_tensors(model, False), d.NL)
-    s = H.dec_state_struct(st)
-    sp = H.stream_ptr()
-    fused = torch.empty((B, L, d.V), dtype=torch.float32, device=enc.device)
-    scratch = torch.empty(B, dtype=torch.int64, device=enc.device)
-    H.call('asr_att_decoder_keys', ctypes.byref(d), ctypes.byref(w), H.ptr(enc), H.ptr(st['key']), prec, sp)
+    dec = DecoderStepper(model, enc, enc_len, L, prec)
+    d, st = dec.d, dec.sd
+    fused = torch.empty((d.B, L, d.V), dtype=torch.float32, device=enc.device)
+    scratch = torch.empty(d.B, dtype=torch.int64, device=enc.device)
     for t in range(L):
-        H.call('asr_att_decoder_step', ctypes.byref(d), ctypes.byref(w), H.ptr(enc), H.ptr(enc_len), ctypes.byref(s), t, prec, sp)
+        dec.step(t)
         nxt, ld = (st['tokens'][:, t + 1], st['tokens'].stride(0)) if t + 1 < L else (scratch, 1)
         row = emb_decoder.fuse_rows(st['hs'][:, t, -1, :], st['logits'][:, t], argmax=nxt, argmax_ld=ld)
         fused[:, t].copy_(row)

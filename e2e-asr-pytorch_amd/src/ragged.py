@@ -25,6 +25,11 @@ from src import functions as F_hip
 from src import hipabi as H
 
 
+def eval_ctx(asr):
+    """Stand-in for the per-forward context (src/asr.py:_RunCtx) where a layer runs outside ASR.forward, in evaluation."""
+    return type('C', (), {'anchor': asr._anchor, 'prec': asr.prec, 'next_seed': lambda s: 0})()
+
+
 def group_consecutive(items, n):
     """Yields lists of n consecutive items of any iterable: order kept, the last group short."""
     n = max(1, int(n))
@@ -135,7 +140,7 @@ def run_frontend(asr, ext, feat, flen):
         return x, tl, el
     # per-frame front-ends on features whose padding is zeros of our own
     x = masked_copy(feat.float(), torch.tensor(flen, dtype=torch.int64, device=dev))
-    ctx = type('C', (), {'anchor': asr._anchor, 'prec': asr.prec, 'next_seed': lambda s: 0})()
+    ctx = eval_ctx(asr)
     x, _ = ext(x, torch.tensor(flen, dtype=torch.int64, device=dev), ctx)
     return x, tl, el
 
