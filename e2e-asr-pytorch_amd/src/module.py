@@ -42,6 +42,11 @@ class RNNLayer(nn.Module):
             raise ValueError('Unsupported Sample Style: ' + sample_style)
         self.dim, self.nd = dim, (2 if bidirection else 1)
         rnn_out_dim = self.nd * dim
+        if proj and sample_rate > 1 and sample_style == 'concat':
+            # the projection is rnn_out_dim x rnn_out_dim (as the reference's, which fails on this shape at its first forward):
+            # behind a 'concat' of `sample_rate` frames the contraction would read past the rows of pj.weight
+            raise ValueError("proj behind 'concat' down-sampling at rate %d: the projection is %d x %d, the layer's output %d wide"
+                             % (sample_rate, rnn_out_dim, rnn_out_dim, sample_rate * rnn_out_dim))
         self.out_dim = sample_rate * rnn_out_dim if (sample_rate > 1 and sample_style == 'concat') else rnn_out_dim
         self.dropout, self.layer_norm, self.sample_rate, self.sample_style, self.proj = dropout, layer_norm, sample_rate, sample_style, proj
         if self.module == 'LSTM':
