@@ -228,6 +228,9 @@ extern "C" size_t asr_lstm16_workspace_bytes(int B, int H, int ND, int backward)
     return persist_mode() >= 1 ? lstm_gen3_pass(B, H, ND, backward != 0).bytes : 0;
 }
 
+extern "C" int asr_lstm16_set_bwd_form(int form) { return lstm_gen3_set_bwd_form(form); }
+extern "C" int asr_lstm16_bwd_form(int B, int H, int ND) { return lstm_gen3_bwd_gather(B, H, ND) ? 1 : 0; }
+
 // asr_lstm16_fwd (dy16 == nullptr) / asr_lstm16_bwd (y16 = dy16, read-only)
 static int lstm16_pass(const char* name, void* gates16, const float* whh, void* y16, float* c, bool bwd, int B, int T, int H, int ND,
                        void* workspace, size_t workspace_bytes, unsigned epoch, int reserved_cus, asr_stream_t stream) {

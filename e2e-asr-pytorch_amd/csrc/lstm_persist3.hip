@@ -24,13 +24,14 @@
 // products, the NKS / NTO class lists) are stated once in lstm_persist_common.h.
 #include "common.h"
 #include <stdlib.h>
+#include <atomic>
 #include "handoff.h"
 #include "lstm_persist_common.h"
 #include "lstm_plan.h"
 
 namespace {
 
-constexpr int HDR_BYTES = 1024;         // status block: abort word, per-group consensus words (u64 8..15), modes (26..33), diag (64..)
+constexpr int HDR_BYTES = 1024;         // status block: abort word, per-group consensus words (u64 8..15), modes (26..33), backward form (34), diag (64..)
 // TWO status blocks per workspace, used by launch epoch parity: a launch works in block (epoch & 1) and clears the OTHER one for
 // its successor (first workgroup, before anything else) - the per-launch `hipMemsetAsync` of the header is gone (eight fill
 // launches per training step on the critical stream).  A fresh / scrubbed workspace is all zero.
@@ -253,6 +254,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
         const int parity = i / (P * BS * 8), r = i - parity * (P * BS * 8), pc = r / (BS * 8), rr = r - pc * (BS * 8);
         st_gran_local(xg + (long)parity * per_par + (((long)pc * P + me) * BS * 8) + rr, 0ull);
     }
+    if (blockIdx.x == 0 && tid == 0) reinterpret_cast<u64*>(p.abort_flag)[34] = 1ull;       // status: backward form (1 reduce-scatter, 2 gather)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const bool local = xcd_consensus(reinterpret_cast<u64*>(p.abort_flag) + 8 + gid, P, p.allow_local, p.abort_flag);
@@ -408,10 +410,285 @@ __global__ __launch_bounds__(512) void lstm_bwd_p3(P3 p) {
     LSTM_DIAG_DUMP(0, 64)
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward (BPTT), gather form: groups of at most 4 batch rows (BS <= 4)
+// ------------------------------------------------------------------------------------------------
+// What is exchanged is dh itself, as in dec_bwd_persist: workgroup `me` publishes dh_{prev}[b][16 me .. +15] of its nb rows
+// (nb x 64 bytes per step) and polls the whole BS x H vector; every workgroup then recomputes the elementwise cell backward of
+// ALL BS x H elements, so there is no gate-gradient all-gather and no P-way sum of partials.
+//   waves 4-7 (gather):  poll the 16-byte pairs (4 units of one row) of dh, run the cell backward of exactly those elements
+//                        (they keep the elements' dc carry for the whole launch) from coefficients the compute waves left in
+//                        LDS, write the bf16 gate-gradient tile [b][k = 4*unit + gate].  LDS traffic only.
+//   one barrier
+//   waves 0-3 (compute): wave w owns output units j0 + 4w .. +3.  The 12 MFMA columns that are no batch row carry the split
+//                        of K = 4H in quarters: A row m = 4*u + kq = W_hh of output unit u over quarter kq, B column
+//                        n = 4*kq + b = row b's gate gradients of quarter kq.  Lane (n, q) finds the partial of (unit q, row
+//                        n & 3, quarter n >> 2) in accumulator register n >> 2; two DPP steps sum the quarters.  Then: publish,
+//                        store the own 16 units' gate gradients over the saved gates, form the coefficients of step s+2 for
+//                        all elements (thread ct: elements ct, ct + 256, ...) into LDS, request the operands of step s+4.
+// Both LDS buffers (tile, coefficients) are double buffered by step parity: what the gather waves read or write between the
+// barriers of steps s-1 and s is buffer s & 1, what the compute waves fill there is the other one.
+// SAVED GATES ARE READ BY EVERY WORKGROUP OF THE GROUP and overwritten by their owner: the owner stores the gradients of step
+// x behind its barrier of step x, i.e. behind the dh of step x-1 of every peer, which a peer publishes behind ITS barrier x-1
+// and so behind its coefficient fill of step x (done in the tail of step x-2: the loaded values were consumed).  Steps 0 and
+// 1 are filled before the XCD consensus, which no workgroup leaves before all have arrived.
+// Exchange region: [group][parity][b (BS)][H/2] granules of two fp32, tagged like the partial sums of lstm_bwd_p3.
+// The two forms lay the same region out differently, and the switch may change between launches on one workspace (tests,
+// A/B runs; a training run keeps one form).  What protects such a switch is not the 4-bit epoch of the tag alone: in either
+// form every producer clears ALL slots it will publish to in this launch - both parities, all BS rows, i.e. every slot a
+// consumer of this launch polls - before the consensus, behind which polling starts.  A granule the other form left in a
+// slot, whatever its tag, does not survive that.
+template <int NKS>
+__global__ __launch_bounds__(512) void lstm_bwd_g3(P3 p) {
+    constexpr int CH = (NKS + 7) / 8;      // 16-byte pairs per gather thread:  ceil(4 * (H/4) / 256)
+    constexpr int CE = (NKS + 1) / 2;      // elements per compute thread:      ceil(4 * H / 256)
+    if (blockIdx.x == 0 && threadIdx.x < HDR_BYTES / 4) p.clear_next[threadIdx.x] = 0u;      // the successor's status block (see HDR_SLOTS)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int H = p.H, T = p.T, ND = p.ND, P = p.P, BS = p.BS;
+    const int gid = blockIdx.x & 7, me = blockIdx.x >> 3;
+    const int d = gid % ND, slice = gid / ND;
+    if (slice >= p.NS) return;
+    const int b0 = slice * BS, nb = min(BS, p.B - b0);
+    if (nb <= 0) return;
+    const int j0 = me * 16;
+    const int tid = threadIdx.x;
+    const int LD = 4 * H + 8;                                // bf16 per tile row (16-byte pad)
+    const int NE = 4 * H;                                    // element slots of one coefficient plane
+    const int tile_elems = 2 * 4 * LD + NKS * 32;            // [2][4][LD] + what the last padded k-step reads behind the end
+    __bf16* tiles = reinterpret_cast<__bf16*>(smem);
+    float* coefs = reinterpret_cast<float*>(smem + (size_t)tile_elems * 2);      // [2][7][NE]
+    for (int i = tid; i < tile_elems / 2; i += 512) reinterpret_cast<unsigned*>(smem)[i] = 0u;
+    const int HG = H >> 1;
+    u64* xg = p.xbuf + (long)gid * 2 * BS * HG;              // this group's [parity][BS][HG]
+    // clear this producer's granules in the L2 (see lstm_fwd_p3)
+    for (int i = tid; i < 2 * BS * 8; i += 512) {
+        const int parity = i / (BS * 8), r = i - parity * (BS * 8);
+        st_gran_local(xg + ((long)parity * BS + (r >> 3)) * HG + (j0 >> 1) + (r & 7), 0ull);
+    }
+    if (blockIdx.x == 0 && tid == 0) reinterpret_cast<u64*>(p.abort_flag)[34] = 2ull;       // status: backward form (1 reduce-scatter, 2 gather)
+
+    const long g_ts = (long)ND * 4 * H, c_ts = (long)ND * H;
+    auto tix = [&](int s_) { return (d == 0) ? T - 1 - s_ : s_; };
+    // ---- compute role, part 1: the elements whose coefficients this thread forms, their operands of steps 0..3, the
+    //      coefficients of steps 0 and 1 ----
+    const int ct = tid & 255;
+    long e_off[CE];                                          // (row, unit) of element ct + 256 i in c / dy; x 4 in the gates
+    bool e_ok[CE];
+#pragma unroll
+    for (int i = 0; i < CE; ++i) {
+        const int E = ct + 256 * i;
+        e_ok[i] = E < nb * H;
+        const int Ec = e_ok[i] ? E : 0, erow = Ec / H, eunit = Ec - erow * H;
+        e_off[i] = ((long)(b0 + erow) * T * ND + d) * H + eunit;
+    }
+    // raw operands exactly as loaded, every load by every lane on every path (see lstm_bwd_p3); c_{t-+1} is the c of the
+    // neighbouring step's set.  A request past the end (s_ >= T) repeats step T-1: its gates may by then hold their owner's
+    // gradients, so that set is garbage by design - it only feeds fill_coef(s >= T), whose buffer no step reads, and as
+    // rn.c the factor cpm = 0 (c itself is never written by a backward).
+    struct Raw { uint2 g[CE]; unsigned dy[CE]; float c[CE]; };
+    auto load_raw = [&](int s_) -> Raw {
+        Raw r;
+        const long t = tix(min(s_, T - 1));
+#pragma unroll
+        for (int i = 0; i < CE; ++i) {
+            r.g[i] = *reinterpret_cast<const uint2*>(p.gates + 4 * (e_off[i] + t * c_ts));
+            r.dy[i] = p.y[e_off[i] + t * c_ts];
+            r.c[i] = p.c[e_off[i] + t * c_ts];
+        }
+        return r;
+    };
+    auto fill_coef = [&](int s_, const Raw& r, const Raw& rn) {
+        float* dst = coefs + (s_ & 1) * 7 * NE + ct;
+        const float cpm = (s_ + 1 < T) ? 1.f : 0.f;
+#pragma unroll
+        for (int i = 0; i < CE; ++i) {
+            const float gi = bf2f((unsigned short)(r.g[i].x & 0xFFFFu)), gf = bf2f((unsigned short)(r.g[i].x >> 16));
+            const float gg = bf2f((unsigned short)(r.g[i].y & 0xFFFFu)), go = bf2f((unsigned short)(r.g[i].y >> 16));
+            const Coef k = make_coef(bf2f((unsigned short)r.dy[i]), gi, gf, gg, go, r.c[i], rn.c[i] * cpm);
+            if (e_ok[i]) {
+                float* o = dst + 256 * i;
+                o[0] = k.dy; o[NE] = k.c1; o[2 * NE] = k.c2; o[3 * NE] = k.c3; o[4 * NE] = k.c4; o[5 * NE] = k.c5; o[6 * NE] = k.f;
+            }
+        }
+    };
+    Raw raw0, raw1, raw2, raw3;
+    if (tid < 256) {
+        raw0 = load_raw(0); raw1 = load_raw(1); raw2 = load_raw(2); raw3 = load_raw(3);
+        fill_coef(0, raw0, raw1);
+        fill_coef(1, raw1, raw2);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const bool local = xcd_consensus(reinterpret_cast<u64*>(p.abort_flag) + 8 + gid, P, p.allow_local, p.abort_flag);
+
+    if (tid >= 256) {
+        // ---- gather role: pairs gt, gt + 256 of the group's nb x H/4 ----
+        const int gt = tid - 256;
+        const int total2 = nb * (H >> 2);
+        int tile_off[CH], cnt = 0;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int idx = gt + 256 * i;
+            const int ic = idx < total2 ? idx : 0, row = ic / (H >> 2);
+            tile_off[i] = row * LD + 16 * (ic - row * (H >> 2));
+            if (idx < total2) cnt = i + 1;
+        }
+        float carry[CH][4];
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) carry[i][e] = 0.f;
+        LSTM_DIAG_DECL
+        for (int s = 0; s < T; ++s) {
+            if (cnt > 0) {
+                // coefficients of step s: in LDS since before the previous barrier
+                f32x4 kf[CH][7];
+                const float* ksrc = coefs + (s & 1) * 7 * NE + 4 * gt;
+#pragma unroll
+                for (int i = 0; i < CH; ++i)
+#pragma unroll
+                    for (int k = 0; k < 7; ++k) kf[i][k] = *reinterpret_cast<const f32x4*>(ksrc + k * NE + (i < cnt ? 1024 * i : 0));
+                u64 glo[CH], ghi[CH];
+#pragma unroll
+                for (int i = 0; i < CH; ++i) glo[i] = ghi[i] = 0ull;
+                if (s > 0) {
+                    for (int z = 0; z < p.poll_delay; ++z) __builtin_amdgcn_s_sleep(2);
+                    const u64* src = xg + (long)((s - 1) & 1) * BS * HG + 2 * gt;
+                    gather16<CH>(src, 512, cnt, BWD_MASK, bwd_want(seq_of(s - 1), p.epoch), glo, ghi, p.abort_flag);
+                }
+                LSTM_DIAG_MARK(0)
+                __bf16* tile = tiles + (s & 1) * 4 * LD;
+#pragma unroll
+                for (int i = 0; i < CH; ++i) {
+                    if (i < cnt) {
+                        const f32x4 dh = bwd_untag(glo[i], ghi[i]);
+                        uint2 o[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const Coef k{kf[i][0][e], kf[i][1][e], kf[i][2][e], kf[i][3][e], kf[i][4][e], kf[i][5][e], kf[i][6][e]};
+                            const CellGrad cg = cell_bwd(k, k.dy + dh[e], carry[i][e]);
+                            carry[i][e] = cg.carry;
+                            o[e] = dgates_bits(cg);
+                        }
+                        uint4* dst = reinterpret_cast<uint4*>(tile + tile_off[i]);
+                        dst[0] = make_uint4(o[0].x, o[0].y, o[1].x, o[1].y);
+                        dst[1] = make_uint4(o[2].x, o[2].y, o[3].x, o[3].y);
+                    }
+                }
+            }
+            LSTM_DIAG_MARK(1)
+            __syncthreads();
+            LSTM_DIAG_MARK(2)
+        }
+        LSTM_DIAG_DUMP(256, 72)
+        return;
+    }
+
+    // ---- compute role, part 2 ----
+    const int lane = tid & 63, w = tid >> 6;
+    const int n = lane & 15, q = lane >> 4;
+    const int kq = n >> 2;                                   // as A row: quarter of K held;  as B / D column: quarter of K summed
+    bf16x8 wreg[NKS];
+    {
+        // A operand row m = n = 4*u + kq: W_hh[k][j0 + 4w + u] over k = kq*H + kk, kk = 32 ks + 8 q + e, k = 4*unit + gate
+        const int ucol = j0 + 4 * w + (n >> 2), qa = n & 3;
+        float wf[NKS][8];
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int k = qa * H + min(ks * 32 + 8 * q + e, H - 1);
+                wf[ks][e] = p.whh[((long)d * 4 * H + (long)(k & 3) * H + (k >> 2)) * H + ucol];
+            }
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) wreg[ks][e] = (__bf16)((ks * 32 + 8 * q + e < H) ? wf[ks][e] : 0.f);
+    }
+    // the own element (row eb, unit j0 + ej) whose gate gradients this thread stores over the saved gates
+    const int eb = tid >> 4, ej = tid & 15;
+    const bool eok = eb < nb;
+    const int ebg = b0 + (eok ? eb : 0);
+    unsigned char* dump_wg = p.dump + (long)blockIdx.x * 512 * 16;
+    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(p.xbuf, 0, p.region_bytes, 0x00020000);
+    const unsigned dump_off = (unsigned)(dump_wg - reinterpret_cast<unsigned char*>(p.xbuf)) + (unsigned)tid * 16u;
+    unsigned short* ge = p.gates + ((long)ebg * T * ND + d) * 4 * H + (long)(j0 + ej) * 4;
+    const int own_off = (eok ? eb : 0) * LD + 4 * (j0 + ej);
+    const int frag_off = (n & 3) * LD + kq * H + 8 * q;
+    // the wave's four units of row n & 3 go out from lane (n, q = 0), n < nb
+    const bool pub = q == 0 && n < nb;
+    const unsigned pub_off = (unsigned)((reinterpret_cast<unsigned char*>(xg + (long)min(n, BS - 1) * HG + ((j0 + 4 * w) >> 1)))
+                                        - reinterpret_cast<unsigned char*>(p.xbuf));
+    const unsigned par_bytes = (unsigned)(BS * HG * 8);
+    LSTM_DIAG_DECL
+    int s = 0;
+
+#define BWDG_STEP(RCUR, RA, RB)                                                                                             \
+    {                                                                                                                       \
+        const __bf16* tile = tiles + (s & 1) * 4 * LD;                                                                      \
+        /* operands four steps ahead, requested IN FRONT of this step's stores: the coefficient fill below needs the set   \
+           requested one step ago, and behind the stores its counted wait would also wait for the publish to be acknowledged */ \
+        RCUR = load_raw(s + 4);                                                                                             \
+        LSTM_DIAG_MARK(7)                                                                                                   \
+        __syncthreads();                         /* gate-gradient tile of step s complete */                                \
+        LSTM_DIAG_MARK(0)                                                                                                   \
+        bf16x8 hb[NKS];                                                                                                     \
+        _Pragma("unroll") for (int ks = 0; ks < NKS; ++ks) hb[ks] = *reinterpret_cast<const bf16x8*>(tile + frag_off + ks * 32); \
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};                                                        \
+        _Pragma("unroll") for (int ks = 0; ks < NKS; ++ks) {             /* two independent accumulation chains */          \
+            if (ks & 1) acc2 = mma16(wreg[ks], hb[ks], acc2); else acc = mma16(wreg[ks], hb[ks], acc);                       \
+        }                                                                                                                   \
+        const float p0 = acc[0] + acc2[0], p1 = acc[1] + acc2[1], p2 = acc[2] + acc2[2], p3 = acc[3] + acc2[3];              \
+        float dhp = kq == 0 ? p0 : kq == 1 ? p1 : kq == 2 ? p2 : p3;                                                        \
+        dhp = row_ror_add<8>(dhp);                                                                                          \
+        dhp = row_ror_add<4>(dhp);               /* dh_{prev}[row n & 3][unit j0 + 4w + q], in all four lanes of the row */ \
+        LSTM_DIAG_MARK(1)                                                                                                   \
+        {                                                                                                                   \
+            const unsigned v0 = __float_as_uint(dhp);                                                                       \
+            const unsigned v1 = __shfl(v0, n + 16), v2 = __shfl(v0, n + 32), v3 = __shfl(v0, n + 48);                        \
+            const f32x4 quad = {dhp, __uint_as_float(v1), __uint_as_float(v2), __uint_as_float(v3)};                         \
+            u64 g0, g1;                                                                                                     \
+            bwd_granules(quad, bwd_want(seq_of(s), p.epoch), g0, g1);                                                       \
+            const unsigned off = (pub && s + 1 < T) ? pub_off + (unsigned)(s & 1) * par_bytes : dump_off;                   \
+            publish_pair(xrsrc, off, g0, g1, local);                                                                        \
+        }                                                                                                                   \
+        LSTM_DIAG_MARK(2)                                                                                                   \
+        /* the own units' gradients replace the saved gates; coefficients of step s+2 */                                   \
+        {                                                                                                                   \
+            const uint2 dg16 = *reinterpret_cast<const uint2*>(tile + own_off);                                             \
+            *(eok ? reinterpret_cast<uint2*>(ge + (long)tix(s) * g_ts) : reinterpret_cast<uint2*>(dump_wg + tid * 16)) = dg16; \
+        }                                                                                                                   \
+        LSTM_DIAG_MARK(3)                                                                                                   \
+        fill_coef(s + 2, RA, RB);                                                                                           \
+        LSTM_DIAG_MARK(4)                                                                                                   \
+        if (++s >= T) break;                                                                                                \
+    }
+
+    for (;;) { BWDG_STEP(raw0, raw2, raw3) BWDG_STEP(raw1, raw3, raw0) BWDG_STEP(raw2, raw0, raw1) BWDG_STEP(raw3, raw1, raw2) }
+#undef BWDG_STEP
+    LSTM_DIAG_DUMP(0, 64)
+}
+
 size_t fwd3_region_bytes(int H) { return (size_t)8 * 2 * 16 * (H / 4) * sizeof(u64); }
 size_t bwd3_dump_bytes(int H) { return (size_t)8 * (H / 16) * 512 * 16; }
+// the backward region is sized by the reduce-scatter form; the gather form's [8][2][BS][H/2] granules (64 BS H bytes against
+// 4 BS H^2) fit in front of the same dump area for every H >= 16, so one workspace serves either kernel
 size_t bwd3_region_bytes(int H, int BS) { const size_t P = H / 16; return (size_t)8 * 2 * P * P * BS * 8 * sizeof(u64) + bwd3_dump_bytes(H); }
+size_t bwdg3_exchange_bytes(int H, int BS) { return (size_t)8 * 2 * BS * (H / 2) * sizeof(u64); }
+size_t bwdg3_lds_bytes(int H, int NKS) { return (size_t)(2 * 4 * (4 * H + 8) + NKS * 32) * 2 + (size_t)2 * 7 * 4 * H * sizeof(float); }
 int slice_rows(int B, int ND) { const int NS = 8 / ND; return (B + NS - 1) / NS; }
+
+// ASR_LSTM3_BWD / asr_lstm16_set_bwd_form: 1 = gather form (lstm_bwd_g3) for groups of at most 4 rows, 0 = reduce-scatter form
+// (lstm_bwd_p3) everywhere.  The environment is read once; the setter is for A/B runs and tests within one process.
+constexpr int BWD_FORM_DEFAULT = 1;
+std::atomic<int> g_bwd_form{-1};
+int bwd_form() {
+    int f = g_bwd_form.load(std::memory_order_relaxed);
+    if (f >= 0) return f;
+    int unset = -1;                                          // a setter that got in first keeps its value
+    g_bwd_form.compare_exchange_strong(unset, env_int("ASR_LSTM3_BWD", BWD_FORM_DEFAULT) != 0 ? 1 : 0);
+    return g_bwd_form.load(std::memory_order_relaxed);
+}
 
 // every workgroup of the launch must be resident at the same time: the grid against what the device can hold beside
 // `reserved_cus` compute units that another stream may be using (data-parallel all-reduce kernels)
@@ -436,6 +713,7 @@ bool make_p3(P3& p, unsigned short* gates, const float* whh, unsigned short* y, 
     const int BS = slice_rows(B, ND);
     const size_t rbytes = bwd ? bwd3_region_bytes(H, BS) : fwd3_region_bytes(H);
     if (bwd && rbytes >= (1ull << 31)) return false;             // the publishes address the region through a buffer descriptor
+    if (bwd && bwdg3_exchange_bytes(H, BS) > rbytes - bwd3_dump_bytes(H)) return false;      // the gather form's granules end where the dump area starts
     const unsigned rot = bwd ? (epoch >> 4) % BWD_REGIONS : (epoch >> 2) % FWD_REGIONS;
     unsigned* hdr = (unsigned*)((char*)ws + (size_t)(epoch & 1u) * HDR_BYTES);
     unsigned* hdr_next = (unsigned*)((char*)ws + (size_t)((epoch + 1u) & 1u) * HDR_BYTES);
@@ -452,6 +730,15 @@ int launch_p3(KernelT kernel, const P3& p, size_t lds, int reserved_cus, hipStre
     const int groups = p.ND * ((p.B + p.BS - 1) / p.BS);
     if (!fits_resident(kernel, groups * p.P, lds, reserved_cus)) return 1;
     return launch_checked(kernel, dim3(8 * p.P), dim3(512), lds, st, name, p);
+}
+
+// the gather form's tile and coefficient buffers pass 64 KB of dynamic LDS from H = 240 on
+template <int NKS>
+int launch_bwdg3(const P3& p, int reserved_cus, hipStream_t st) {
+    static unsigned char attr_[32] = {0};
+    if (first_on_device(attr_))          // the widest H of the class (the kernel has static LDS too: not the whole 160 KB)
+        hipFuncSetAttribute((const void*)lstm_bwd_g3<NKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwdg3_lds_bytes(32 * NKS, NKS));
+    return launch_p3(lstm_bwd_g3<NKS>, p, bwdg3_lds_bytes(p.H, NKS), reserved_cus, st, "asr_lstm3_bwd");
 }
 
 }  // namespace
@@ -472,6 +759,15 @@ LstmPass lstm_gen3_pass(int B, int H, int ND, bool bwd) {
     }
 #define BWD3_CASE(NTO_) \
     if (nto <= NTO_) return launch_p3(lstm_bwd_p3<NTO_>, p, 0, reserved_cus, st, "asr_lstm3_bwd");
+#define BWDG3_CASE(NKS_) \
+    if (nks <= NKS_) return launch_bwdg3<NKS_>(p, reserved_cus, st);
+
+int lstm_gen3_set_bwd_form(int form) {
+    const int old = bwd_form();
+    if (form == 0 || form == 1) g_bwd_form.store(form);
+    return old;
+}
+bool lstm_gen3_bwd_gather(int B, int H, int ND) { return bwd_form() == 1 && lstm3_shape_ok(B, H, ND) && slice_rows(B, ND) <= 4 && H <= LSTM_G3_BWDG_MAX_H; }
 
 // Return ASR_OK when launched, 1 when the shape has no plan (or the grid would not be resident), negative on error.
 int lstm_persistent3(unsigned short* gates, const float* whh, unsigned short* y, float* c, bool bwd, int B, int T, int H, int ND,
@@ -479,6 +775,11 @@ int lstm_persistent3(unsigned short* gates, const float* whh, unsigned short* y,
     P3 p;
     if (!make_p3(p, gates, whh, y, c, B, T, H, ND, ws, ws_bytes, epoch, bwd)) return 1;
     const int nks = (H + 31) / 32, nto = (p.P + 3) / 4;
+    if (bwd && lstm_gen3_bwd_gather(B, H, ND)) {
+        // one workgroup per compute unit (LDS): where that grid is not resident beside `reserved_cus`, the reduce-scatter form may be
+        const int rc = [&]() -> int { LSTM_G3_BWDG_NKS(BWDG3_CASE) return 1; }();
+        if (rc != 1) return rc;
+    }
     if (bwd) { LSTM_G23_NTO(BWD3_CASE) }
     else { LSTM_G23_NKS(FWD3_CASE) }
     return 1;

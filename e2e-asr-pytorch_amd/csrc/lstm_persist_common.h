@@ -149,6 +149,29 @@ __device__ __forceinline__ void bwd_granules(f32x4 acc, u64 want, u64& v0, u64& 
     v1 = ((u64)(__float_as_uint(acc[2]) & ~7u) | ((u64)(__float_as_uint(acc[3]) & ~7u) << 32)) | want;
 }
 
+// ---- gather form of the third generation's backward (lstm_bwd_g3) ---------------------------------------------------------
+// v + v of the lane ROR places to the right within its row of 16 lanes (DPP row_ror): no LDS, no barrier
+template <int ROR>
+__device__ __forceinline__ float row_ror_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + ROR, 0xF, 0xF, false));
+}
+// the two tagged granules of a polled 16-byte pair -> four fp32 dh, tag bits cleared
+__device__ __forceinline__ f32x4 bwd_untag(u64 lo, u64 hi) {
+    f32x4 v;
+    v[0] = __uint_as_float((unsigned)lo & ~7u);
+    v[1] = __uint_as_float((unsigned)(lo >> 32) & ~7u);
+    v[2] = __uint_as_float((unsigned)hi & ~7u);
+    v[3] = __uint_as_float((unsigned)(hi >> 32) & ~7u);
+    return v;
+}
+// one element's gate-gradient quadruple as four bf16
+__device__ __forceinline__ uint2 dgates_bits(CellGrad cg) {
+    uint2 o;
+    o.x = (unsigned)f2bf_bits(cg.d0) | ((unsigned)f2bf_bits(cg.d1) << 16);
+    o.y = (unsigned)f2bf_bits(cg.d2) | ((unsigned)f2bf_bits(cg.d3) << 16);
+    return o;
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------
 // integer environment variable (poll delays: units of s_sleep(2) = 128 clocks; the callers read them once per process)
 inline int env_int(const char* name, int dflt) {
@@ -164,6 +187,10 @@ inline int poll_delays(const char* env_fwd, const char* env_bwd, int dflt_fwd, i
 // k-steps of the forward (H <= 32 NKS), NTO = output tiles per compute wave of the backward (H <= 64 NTO).
 #define LSTM_G23_NKS(X) X(1) X(2) X(4) X(6) X(8) X(10) X(12) X(16)
 #define LSTM_G23_NTO(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8)
+// ... and of the third generation's gather-form backward (NKS = k-steps of one quarter of K = 4H): H <= 384.  At NKS = 16 the
+// four operand sets of 8 elements per thread no longer fit the 256 registers of a wave (91 spilled, measured at build).
+#define LSTM_G3_BWDG_NKS(X) X(1) X(2) X(4) X(6) X(8) X(10) X(12)
+constexpr int LSTM_G3_BWDG_MAX_H = 384;
 
 // Launches kernel<<<grid, block, lds, st>>>(p); ASR_OK, or ASR_E_LAUNCH with the runtime's message under `name`.
 template <typename KernelT, typename ParamT>

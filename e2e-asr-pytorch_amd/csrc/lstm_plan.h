@@ -20,6 +20,12 @@ LstmPass lstm_gen2_pass(int B, int H, int ND, bool bf16, bool bwd);
 // `reserved_cus` is asked of the device at launch and is not part of the plan.
 LstmPass lstm_gen3_pass(int B, int H, int ND, bool bwd);
 
+// The third generation has two backward kernels: the gather form (lstm_bwd_g3: dh is exchanged, every workgroup recomputes the
+// cell backward) for groups of at most 4 batch rows, the reduce-scatter form (lstm_bwd_p3) for larger ones and wherever the
+// switch (ASR_LSTM3_BWD=0, lstm_gen3_set_bwd_form(0)) turns the gather form off.  lstm_gen3_pass(..., true).bytes serves both.
+bool lstm_gen3_bwd_gather(int B, int H, int ND);      // the form lstm_persistent3 plans for the shape under the current switch
+int lstm_gen3_set_bwd_form(int form);                 // 0 / 1 sets the switch, anything else only asks; returns the former value
+
 // The launchers, one per generation, both passes (forward: y = h out; backward: y = dy, read-only, bias2 unused).  Generations
 // 1 and 2 take a planned pass and clear its bytes of the workspace first: ASR_OK or a negative error.  Generation 3 also
 // returns 1: no plan for the shape / workspace, or the grid would not be resident.

@@ -204,6 +204,8 @@ _RESTYPES = {
     'asr_gemm16_route': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     'asr_gemm16_plan': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _P(_i)]),
     'asr_lstm16_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'asr_lstm16_set_bwd_form': (ctypes.c_int, [_i]),
+    'asr_lstm16_bwd_form': (ctypes.c_int, [_i, _i, _i]),
     'asr_ctc_loss_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_beam_step_wide_workspace_bytes': (_sz, [_i, _i]),
     'asr_ctc_beam_search_workspace_bytes': (_sz, [_i, _i, _i]),
@@ -398,7 +400,11 @@ _masked = {}
 def rec_units_for(hidden):
     """CUs per XCD the persistent recurrence of an H-wide layer wants: its H/16 workgroups per group, one per CU, while at
     least 8 units stay with the side stream; wider layers (H = 512: 32 workgroups) sit two per CU (lstm_persist3.hip
-    `fits_resident` admits two)."""
+    `fits_resident` admits two of `lstm_fwd_p3` / `lstm_bwd_p3`).  The gather form of the backward (`lstm_bwd_g3`, H <= 384) is
+    one workgroup per CU from H ~ 288 on (92-111 KB of LDS, 240-256 VGPRs), so it fits the mask this function derives with no
+    slack.  `fits_resident` counts the device's CUs, not the stream's mask: an ASR_REC_UNITS below H/16 therefore needs
+    ASR_LSTM3_BWD=0 as well, or the gather form's grid cannot be resident on the masked stream and the launch ends in the
+    abort word."""
     p = max(1, (int(hidden) + 15) // 16)
     return p if p <= 24 else min(24, (p + 1) // 2)
 

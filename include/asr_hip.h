@@ -137,6 +137,17 @@ int asr_lstm16_fwd(void* gates16, const float* whh, void* y16, float* c, int B, 
                    void* workspace, size_t workspace_bytes, unsigned epoch, int reserved_cus, asr_stream_t stream);
 int asr_lstm16_bwd(void* gates16, const float* whh, const void* dy16, const float* c, int B, int T, int H, int ND,
                    void* workspace, size_t workspace_bytes, unsigned epoch, int reserved_cus, asr_stream_t stream);
+/* asr_lstm16_bwd has two kernels.  Form 1 (default, "gather"): for batch slices of at most 4 rows (ceil(B / (8/ND)) <= 4) the
+ * workgroups exchange dh and each recomputes the elementwise cell backward of its whole slice.  Form 0 ("reduce-scatter"):
+ * partial products handed to the owners of their columns; it serves larger slices always, and every shape when selected by
+ * ASR_LSTM3_BWD=0 in the environment (read once) or asr_lstm16_set_bwd_form(0) (0 / 1 sets, anything else only asks; returns
+ * the former value; the switch is one atomic word, safe to set from any thread, and a launch reads it once).
+ * asr_lstm16_bwd_form: the form the PLAN names for a shape under the current switch - not what a launch will do: it ignores
+ * asr_lstm_set_persistent(0) (no third-generation kernel runs at all) and the residency fall-back (a gather-form grid that does
+ * not fit beside reserved_cus runs form 0).  What a launch did run is in its status block: it writes the form (1 reduce-scatter,
+ * 2 gather) into 64-bit word 34.  Both forms take the same workspace. */
+int asr_lstm16_set_bwd_form(int form);
+int asr_lstm16_bwd_form(int B, int H, int ND);
 /* asr_gemm on bf16 operands in HBM (same index conventions).  c_bf16 = 1: C bf16 = act(sum + bias), written;
  * c_bf16 = 0: C fp32, accumulated (accum / splits as asr_gemm), output row i stored at the reference row
  * (i / 4h)*4h + (i & 3)*h + (i % 4h >> 2) when perm_h = h > 0.  b_time_padded = 1 (with seqT, bshift): the reduction rows

@@ -1,7 +1,8 @@
 """Timing and in-kernel phase timers of the bf16-storage persistent LSTM (csrc/lstm_persist3.hip).
 usage: python tools/diag_lstm3.py [--diag] [B] [T]
   --diag : load lib/diag/libasr_hip_diag.so (make -C e2e-asr-pytorch_amd/csrc diag) and print the phase timers
-Poll delays: env ASR_LSTM3_POLL_DELAY_FWD / _BWD (x128 clocks), hand-off mode: ASR_LSTM_XCD_LOCAL=0 forces write-through."""
+Poll delays: env ASR_LSTM3_POLL_DELAY_FWD / _BWD (x128 clocks), hand-off mode: ASR_LSTM_XCD_LOCAL=0 forces write-through,
+backward kernel: ASR_LSTM3_BWD=0 forces the reduce-scatter form (the account printed is that of the form the launch reports)."""
 import os, sys, ctypes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'e2e-asr-pytorch_amd'))
@@ -30,11 +31,15 @@ wsf, wsb = torch.zeros(nf, dtype=torch.uint8).cuda(), torch.zeros(nb, dtype=torc
 NAMES = {'fwd': ['C: wait tile (barrier)', 'C: lds read+mfma+cell', 'C: shuffle+publish+y', 'C: bulk io', '-', '-', '-', 'C: looptop',
                  'G: sleep+poll', 'G: lds write', 'G: barrier', '-', '-', '-', '-', '-'],
          'bwd': ['C: wait sums (barrierA)', 'C: cell bwd+tile', 'C: barrierB', 'C: mfma+publish', 'C: bulk io+coef', '-', '-', 'C: looptop',
-                 'G: sleep+poll+sum', 'G: lds write', 'G: barrierA', 'G: barrierB', '-', '-', '-', '-']}
+                 'G: sleep+poll+sum', 'G: lds write', 'G: barrierA', 'G: barrierB', '-', '-', '-', '-'],
+         'bwd gather': ['C: wait tile (barrier)', 'C: lds read+mfma+dpp sum', 'C: shuffle+publish', 'C: own dgates store', 'C: coef fill+prefetch', '-', '-',
+                        'C: looptop', 'G: coef read+sleep+poll', 'G: cell bwd+tile write', 'G: barrier', '-', '-', '-', '-', '-']}
 
 
 def report(tag, ms, ws, epoch):
     st = ws[(epoch & 1) * 1024:][:1024].view(torch.int64).cpu().tolist()          # the launch's status block (parity of its epoch)
+    if tag == 'bwd' and st[34] == 2:                                              # the form the launch ran: 1 reduce-scatter, 2 gather
+        tag = 'bwd gather'
     print('%s: %.3f ms (%.3f us/step) abort=%d modes=%s' % (tag, ms, ms * 1e3 / T, st[0] & 0xffffffff, st[26:34]))
     if diag:
         for k, nm in enumerate(NAMES[tag]):
