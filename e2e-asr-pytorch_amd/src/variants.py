@@ -6,7 +6,8 @@ The shipped configs (LSTM, location-aware attention, one head, no decoder dropou
 (src/asr.py:131-170) with every arithmetic step a HIP kernel of csrc/variants.hip / the contraction kernels, chained by autograd.
 torch contributes the tape, views, `cat` / `permute().contiguous()` copies and the accumulation of a gradient that has several
 consumers - no arithmetic of the model.  A variant step is bound by its launches, like the reference's; it is a correctness path
-(parity: tests/test_variants.py against the CPU restatement and the reference's fixtures), not the measured one.
+(parity: tests/test_variants.py against the CPU restatement and the reference's fixtures; the chain between the kernels against
+float64 at its edges: tests/test_hip_variant_decoder_vs_float64.py), not the measured one.
 """
 import torch
 import torch.nn as nn
@@ -349,6 +350,14 @@ def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, 
         if emb_p > 0:
             from src.functions import DropoutFn
             teacher_emb = DropoutFn.apply(teacher_emb, emb_p, ctx.next_seed())
+    # what the loop fed, <sos> first (column t + 1 = the token chosen after step t), and the optional fixed teacher / sample
+    # decisions, one bool per step in place of the host draw - both as att_decoder_forward_sampled has them (tests)
+    decisions = getattr(model, '_tf_decisions', None)
+    fed = torch.zeros((B, int(decode_step)), dtype=torch.int64, device=dev)
+
+    def feed(t, tokens):
+        if t + 1 < fed.shape[1]:
+            fed[:, t + 1].copy_(tokens.view(B))
     outputs, att_seq, states = [], [], []
     for t in range(int(decode_step)):
         # ---- attend (the query is the state of all layers, :251-257)
@@ -385,8 +394,13 @@ def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, 
         cur_char = LinearActFn.apply(anchor, xo, dec.char_trans.weight, dec.char_trans.bias, H.ACT_NONE, prec)
         # ---- next input (:145-166)
         if teacher is not None:
-            if tf_rate == 1 or torch.rand(1).item() <= tf_rate:
+            if decisions is not None and tf_rate != 1:
+                use_teacher = bool(decisions[t]) if t < len(decisions) else True      # past the list: the teacher's token
+            else:
+                use_teacher = tf_rate == 1 or torch.rand(1).item() <= tf_rate
+            if use_teacher:
                 last_char = teacher_emb[:, t, :]
+                feed(t, teacher[:, t])
             else:
                 with torch.no_grad():
                     sampled = torch.empty((B,), dtype=torch.int64, device=dev)
@@ -395,6 +409,7 @@ def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, 
                     H.call('asr_sample_tokens', H.ptr(cur_char.detach()), cur_char.shape[1], H.ptr(sampled), 1, B, cur_char.shape[1], seed,
                            H.stream_ptr())
                 last_char = EmbeddingFn.apply(anchor, sampled, model.pre_embed)
+                feed(t, sampled)
                 if emb_p > 0:
                     last_char = dropout(last_char, emb_p, ctx.next_seed())
         elif emb_decoder is not None:
@@ -402,16 +417,20 @@ def variant_decoder(model, anchor, enc, enc_len, decode_step, teacher, tf_rate, 
             nxt = torch.empty((B,), dtype=torch.int64, device=dev)
             cur_char = emb_decoder.fuse_rows(d_state.detach(), cur_char.detach().contiguous(), argmax=nxt, argmax_ld=1)
             last_char = EmbeddingFn.apply(anchor, nxt, model.pre_embed)
+            feed(t, nxt)
         else:
             with torch.no_grad():
                 cand = torch.empty((B, 1), dtype=torch.int32, device=dev)
                 H.call('asr_beam_candidates', H.ptr(cur_char.detach().contiguous()), H.ptr(cand), B, cur_char.shape[1], 1, H.stream_ptr())
-            last_char = EmbeddingFn.apply(anchor, cand.view(B).long(), model.pre_embed)
+            nxt = cand.view(B).long()
+            last_char = EmbeddingFn.apply(anchor, nxt, model.pre_embed)
+            feed(t, nxt)
         outputs.append(cur_char)
         att_seq.append(attn)
         states.append(d_state)
     att_output = torch.stack(outputs, dim=1)          # (B,L,V)
     att_seq = torch.stack(att_seq, dim=2)             # (B,NH,L,T)
+    model._last_tokens = fed
     return att_output, att_seq, torch.stack(states, dim=1)
 
 
